@@ -12,10 +12,13 @@ N>1   configs[3]: one independent 1M-point frame stream per GPU (no data-path co
       environment) with --gpus N, the script launches the N ranks itself; it never reports fewer GPUs
       than it was asked for.
 
-Prints ONE JSON line on rank 0.  Besides the headline the line carries (N=1): per-kernel times and
-rooflines, `with_h2d` (a fresh cloud + fresh detections every frame, host->device copy included),
-`lidar_like`, `beyond_l3` (config 5 on one GPU: working set past the 256 MiB Infinity Cache), PMC
-traffic measured in this very run (rocprofv3 child passes) and the CPU baselines.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (--warmup W frames), times ONE region of
+exactly --steps K frames, optionally writes what the last frame produced (--dump-outputs DIR) and prints the
+headline.  With --full the line also carries what takes runs of its own: the K-step region repeated
+(median reported), per-kernel times and rooflines, and (N=1) `with_h2d` (a fresh cloud + fresh detections
+every frame, host->device copy included), `tick`, `pca_path`, `lidar_like`, `beyond_l3` (config 5 on one
+GPU: working set past the 256 MiB Infinity Cache), PMC traffic measured in this very run (rocprofv3 child
+passes) and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -53,11 +56,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=0, help="0 = 3 at N=1 / 4 at N>1; 5 = one sharded 10M-point frame")
     ap.add_argument("--cloud", choices=["uniform", "lidar"], default="uniform")
-    ap.add_argument("--plain", action="store_true", help="headline + stage times only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repetitions, stage times, rooflines, PMC passes, extra legs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step produced as DIR/<name>.npy (float32)")
+    ap.add_argument("--plain", action="store_true",
+                    help="repetitions of the timed region + stage times only, even with --full (profiling runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 child passes (traffic = null)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--min-reps", type=int, default=5, help="repetitions of the K-step timed region (median reported)")
+    ap.add_argument("--min-reps", type=int, default=5,
+                    help="with --full or --plain: repetitions of the K-step timed region (median reported)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="config 5 through the sharded (RCCL) frame even with one rank: rehearses the code path on one GPU")
     ap.add_argument("--slice-of", type=int, default=0,
@@ -737,6 +746,26 @@ def pmc_child_passes(config, budget_note, sharded_world=0):
     return (res or None), ("; ".join(errs) if errs else None)
 
 
+# ------------------------------------------------------------------------------- outputs --
+DUMP_CAP = 1 << 21   # elements per array: six float32 arrays are at most 48 MiB of data
+
+
+def dump_outputs(h, out_dir, grid_only):
+    """What the timed frame returned in its last step, as float32 DIR/<name>.npy: the grid layers (log-odds,
+    occupancy, the int8 occupancy grid) and, unless the frame is sharded (whose counts stay per band), the int32
+    hit counts, the miss grid and the per-point bbox ids.  Counts and ids are below 2^24 (at most 10 M points), so
+    float32 holds them exactly.  An array longer than DUMP_CAP is a fixed seeded sample of its positions (sorted;
+    the same positions for every array of that length), so that two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    outs = {"log_odds": h.log_odds(), "occupancy": h.occupancy(), "occupancy_grid": h.to_occupancy_grid()[0]}
+    if not grid_only:
+        outs.update(hits=h.hits(), miss=h.miss(), bbox_id=h.bbox_id())
+    for name, v in outs.items():
+        if v.size > DUMP_CAP:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, DUMP_CAP, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), v.astype(np.float32))
+
+
 # ------------------------------------------------------------------------------ launcher --
 def free_port():
     s = socket.socket()
@@ -852,15 +881,18 @@ def main():
         else:
             h.enqueue_frame()
 
-    # W untimed warm-up steps, then repetitions of EXACTLY K steps, each bracketed by barrier +
-    # synchronize on both sides and reduced by MAX over ranks; `value` is the median repetition (a single
-    # K = 20 region is ~1 ms long and inherits whatever clock state the warm-up left: round-2 verdict), the
-    # spread is printed next to it.  At least 5 repetitions, more until 0.25 s have been timed (at most 200).
+    # W untimed warm-up steps, then a region of EXACTLY K steps bracketed by barrier + synchronize on both
+    # sides and reduced by MAX over ranks.  A plain run times that one region.  With --full (or --plain) the
+    # region is repeated and `value` is the median repetition (a single K = 20 region is ~1 ms long and
+    # inherits whatever clock state the warm-up left: round-2 verdict), the spread is printed next to it: at
+    # least --min-reps repetitions, more until 0.25 s have been timed (at most 200).
+    extra = a.full or a.plain           # repetitions, stage times, kernel rooflines, sharded step times
+    everything = a.full and not a.plain   # + PMC passes, copy rate, the other legs, CPU baselines
     for _ in range(a.warmup):
         step()
     barrier()
     reps = []
-    while len(reps) < a.min_reps or (sum(reps) < 0.25 and len(reps) < 200):
+    while not reps or (extra and (len(reps) < a.min_reps or (sum(reps) < 0.25 and len(reps) < 200))):
         t0 = time.perf_counter()
         for _ in range(a.steps):
             step()
@@ -874,8 +906,10 @@ def main():
     dt = float(np.median(reps))
     frames = a.steps if sharded else a.steps * world   # sharded: all ranks work on the same frame
     fps = frames / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(h, a.dump_outputs, grid_only=sharded)
     shard_extra = None
-    if sharded:
+    if sharded and extra:
         # collective extras: per-step device times (frames one at a time) and the H2D-inclusive rate -- every rank
         # uploads only ITS N / world slice per frame, so the ingest bandwidth of the job is `world` PCIe links
         steps_ms = h.time_frame_sharded_stages(5)
@@ -908,13 +942,6 @@ def main():
 
     out = None
     if rank == 0:
-        # per-kernel device time (gv_time_frame_stages: serial frames, so every kernel runs alone): each kernel
-        # carries a start and an end HIP event on its own dispatch packet (hipExtLaunchKernelGGL), so the
-        # figure is the kernel's duration as rocprofv3 reports it (profiles/rNN/serial_kernel_stats.csv), not
-        # an interval between event records.  In the timed region two frames run side by side and every kernel
-        # is stretched by its neighbours (profiles/rNN/pipelined_kernel_stats.csv); `value` comes from there.
-        stages = h.time_frame_stages(max(10, min(a.steps, 50)))
-        n_rays, n_visits = h.ray_stats()
         bytes_frame = 12.0 * N + 13.0 * G
         # Algorithmic bytes per launch.  SURVEY 8(d): 12 B/point in, 13 B/cell
         # grid traffic; the int32 hit counts are row X1's output (4 B/cell).  The ray stage moves no
@@ -940,68 +967,76 @@ def main():
             "mpoints_per_s": N_total * fps / 1e6,
             "frame_roofline": {"algorithmic_bytes": bytes_frame, "achieved_GBps": bytes_frame * fps / world / 1e9,
                                "frac_of_hbm_peak": bytes_frame * fps / world / 1e9 / HBM_PEAK_GBPS},
-            "stage_ms": stages, "stage_ms_sum": sum(stages.values()),
-            "ray_march": {"rays": n_rays, "equivalent_cell_visits": n_visits,
-                          "mcell_visits_per_s": (n_visits / (stages["ray_march"] * 1e-3) / 1e6) if stages["ray_march"] > 0 else None},
         }
         if rehearsal:
             out["rehearsal"] = True
-        if shard_extra:
-            shard_extra["rccl_ranks"] = int(infos[0][0])
-            shard_extra["rccl"] = [{"rank": int(i[1]), "device": int(i[2]), "ranks_seen": int(i[0])} for i in infos]
-            out["sharded"] = shard_extra
-        pmc, pmc_err = (None, "skipped")
-        if not a.plain and not a.no_pmc and not rehearsal:
-            # (at N > 1 too: the other ranks idle at the closing barrier while rank 0's children profile the same
-            #  workload on its own GPU, so that the roofline object is filled at every N)
-            h.synchronize()
-            pmc, pmc_err = pmc_child_passes(3 if config == 4 else config, "", sharded_world=world if sharded else 0)
-        kernels = []
-        for st, ms in stages.items():
-            if st == "detections":
-                continue   # the rectangles ride the partition launch: no kernel of their own (the slot times two event records)
-            kn = KERNEL_OF[st]
-            c = (pmc or {}).get(kn, {})
-            e = {"stage": st, "kernel": kn, "ms": ms, "traffic": c.get("hbm_bytes"),
-                 "fetch_bytes": c.get("fetch_bytes"), "write_bytes": c.get("write_bytes")}
-            if st == "ray_march":
-                # LDS / issue / latency kernel: no algorithmic HBM bytes; fraction of the VALU issue peak
-                iv = c.get("SQ_INSTS_VALU")
-                e.update({"bound": "valu-issue/lds", "unit": "Gwave-instr/s", "peak": VALU_PEAK_GWIPS,
-                          "achieved": (iv / (ms * 1e-3) / 1e9) if iv and ms > 0 else None,
-                          "valu_wave_instructions": iv,
-                          "lds_bank_conflict_ratio": (c["SQ_LDS_BANK_CONFLICT"] / c["SQ_LDS_IDX_ACTIVE"])
-                          if c.get("SQ_LDS_IDX_ACTIVE") else None,
-                          "mcell_visits_per_s": out["ray_march"]["mcell_visits_per_s"]})
-            else:
-                e.update({"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBPS, "algorithmic_bytes": alg[st],
-                          "achieved": alg[st] / (ms * 1e-3) / 1e9 if ms > 0 else None})
-            e["frac"] = (e["achieved"] / e["peak"]) if e.get("achieved") else None
-            kernels.append(e)
-        out["kernels"] = kernels
-        dom = max(kernels, key=lambda k: k["ms"])
-        out["roofline"] = {k: dom.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic")}
-        out["roofline"]["kernel_ms"] = dom["ms"]
-        out["roofline"]["note"] = ("dominant kernel by HIP-event time; traffic = PMC HBM bytes per launch measured in this run "
-                                   "(rocprofv3 child passes, FETCH_SIZE doubled)" + (f"; pmc: {pmc_err}" if pmc_err else ""))
-        hbm = [k for k in kernels if k["bound"] == "hbm" and k["stage"] != "detections"]
-        # the HBM roofline entry: the kernel that moves the most algorithmic bytes (the grid pass, 13 B/cell); the
-        # partition and tile passes are priced against HBM too in kernels[] but are issue / latency bound
-        dom_hbm = max(hbm, key=lambda k: k["algorithmic_bytes"])
-        out["roofline_hbm"] = {k: dom_hbm.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic")}
-        out["roofline_hbm"]["kernel_ms"] = dom_hbm["ms"]
-        out["roofline_hbm"]["algorithmic_bytes"] = dom_hbm["algorithmic_bytes"]
-        # three lanes x ~50 MB per frame sit in the 256 MiB Infinity Cache at config 3 (FETCH_SIZE counts its hits): the
-        # fraction is then an L3-resident one; config 5 (beyond_l3 leg, ~0.5 GB per frame) is the HBM figure
-        out["roofline_hbm"]["l3_resident"] = bool(bytes_frame * 4 < 256 * 2 ** 20)
-        if not a.plain:
+        if sharded:
+            # what RCCL reported on every rank (gathered at set-up): proof of how many ranks took part
+            out["sharded"] = dict(shard_extra or {}, rccl_ranks=int(infos[0][0]),
+                                  rccl=[{"rank": int(i[1]), "device": int(i[2]), "ranks_seen": int(i[0])} for i in infos])
+        if extra:
+            # per-kernel device time (gv_time_frame_stages: serial frames, so every kernel runs alone): each kernel
+            # carries a start and an end HIP event on its own dispatch packet (hipExtLaunchKernelGGL), so the
+            # figure is the kernel's duration as rocprofv3 reports it (profiles/rNN/serial_kernel_stats.csv), not
+            # an interval between event records.  In the timed region two frames run side by side and every kernel
+            # is stretched by its neighbours (profiles/rNN/pipelined_kernel_stats.csv); `value` comes from there.
+            stages = h.time_frame_stages(max(10, min(a.steps, 50)))
+            n_rays, n_visits = h.ray_stats()
+            out["stage_ms"], out["stage_ms_sum"] = stages, sum(stages.values())
+            out["ray_march"] = {"rays": n_rays, "equivalent_cell_visits": n_visits,
+                                "mcell_visits_per_s": (n_visits / (stages["ray_march"] * 1e-3) / 1e6) if stages["ray_march"] > 0 else None}
+            pmc, pmc_err = (None, "skipped")
+            if everything and not a.no_pmc and not rehearsal:
+                # (at N > 1 too: the other ranks idle at the closing barrier while rank 0's children profile the same
+                #  workload on its own GPU, so that the roofline object is filled at every N)
+                h.synchronize()
+                pmc, pmc_err = pmc_child_passes(3 if config == 4 else config, "", sharded_world=world if sharded else 0)
+            kernels = []
+            for st, ms in stages.items():
+                if st == "detections":
+                    continue   # the rectangles ride the partition launch: no kernel of their own (the slot times two event records)
+                kn = KERNEL_OF[st]
+                c = (pmc or {}).get(kn, {})
+                e = {"stage": st, "kernel": kn, "ms": ms, "traffic": c.get("hbm_bytes"),
+                     "fetch_bytes": c.get("fetch_bytes"), "write_bytes": c.get("write_bytes")}
+                if st == "ray_march":
+                    # LDS / issue / latency kernel: no algorithmic HBM bytes; fraction of the VALU issue peak
+                    iv = c.get("SQ_INSTS_VALU")
+                    e.update({"bound": "valu-issue/lds", "unit": "Gwave-instr/s", "peak": VALU_PEAK_GWIPS,
+                              "achieved": (iv / (ms * 1e-3) / 1e9) if iv and ms > 0 else None,
+                              "valu_wave_instructions": iv,
+                              "lds_bank_conflict_ratio": (c["SQ_LDS_BANK_CONFLICT"] / c["SQ_LDS_IDX_ACTIVE"])
+                              if c.get("SQ_LDS_IDX_ACTIVE") else None,
+                              "mcell_visits_per_s": out["ray_march"]["mcell_visits_per_s"]})
+                else:
+                    e.update({"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBPS, "algorithmic_bytes": alg[st],
+                              "achieved": alg[st] / (ms * 1e-3) / 1e9 if ms > 0 else None})
+                e["frac"] = (e["achieved"] / e["peak"]) if e.get("achieved") else None
+                kernels.append(e)
+            out["kernels"] = kernels
+            dom = max(kernels, key=lambda k: k["ms"])
+            out["roofline"] = {k: dom.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic")}
+            out["roofline"]["kernel_ms"] = dom["ms"]
+            out["roofline"]["note"] = ("dominant kernel by HIP-event time; traffic = PMC HBM bytes per launch measured in this run "
+                                       "(rocprofv3 child passes, FETCH_SIZE doubled)" + (f"; pmc: {pmc_err}" if pmc_err else ""))
+            hbm = [k for k in kernels if k["bound"] == "hbm" and k["stage"] != "detections"]
+            # the HBM roofline entry: the kernel that moves the most algorithmic bytes (the grid pass, 13 B/cell); the
+            # partition and tile passes are priced against HBM too in kernels[] but are issue / latency bound
+            dom_hbm = max(hbm, key=lambda k: k["algorithmic_bytes"])
+            out["roofline_hbm"] = {k: dom_hbm.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic")}
+            out["roofline_hbm"]["kernel_ms"] = dom_hbm["ms"]
+            out["roofline_hbm"]["algorithmic_bytes"] = dom_hbm["algorithmic_bytes"]
+            # three lanes x ~50 MB per frame sit in the 256 MiB Infinity Cache at config 3 (FETCH_SIZE counts its hits): the
+            # fraction is then an L3-resident one; config 5 (beyond_l3 leg, ~0.5 GB per frame) is the HBM figure
+            out["roofline_hbm"]["l3_resident"] = bool(bytes_frame * 4 < 256 * 2 ** 20)
+        if everything:
             try:
                 copy_gbps = measured_copy_rate(torch)
                 out["frame_roofline"]["measured_copy_GBps"] = copy_gbps
                 out["frame_roofline"]["frac_of_measured_copy"] = bytes_frame * fps / world / 1e9 / copy_gbps
             except Exception as e:   # never fail the bench line over the auxiliary peak
                 print("copy-rate measurement failed:", e, file=sys.stderr)
-        if not a.plain and world == 1 and config == 3:
+        if everything and world == 1 and config == 3:
             # the legs below make handles of their own: the headline's handle goes first, or its five streams keep
             # sharing the process's four hardware queues with theirs (measured: the lidar-like leg 17.7 k instead of
             # 21.5 k frames/s with both handles alive)
@@ -1044,7 +1079,7 @@ def main():
                 out["beyond_l3"] = leg
             except Exception as e:
                 out["beyond_l3"] = {"error": str(e)}
-        if not a.plain and not a.no_cpu_baseline and world == 1:
+        if everything and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(config, cloud_fn, tfs, bboxes, poses, a.cpu_seconds)
             out["gpu_over_cpu"] = fps / out["cpu_baseline"]["value"]
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(config, cloud_fn, tfs, bboxes, poses, a.cpu_seconds)

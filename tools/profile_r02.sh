@@ -5,7 +5,7 @@ set -o pipefail
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profile_r02
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-timeout -k 10 500 python bench.py > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
+timeout -k 10 500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
 cd /tmp && export TMPDIR=/tmp
 GV_PIPELINE=0 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_serial -- python3 $GRAFT_REPO_ROOT/bench.py --steps 100 --warmup 10 --plain > $OUT/stats_serial.log 2>&1 || echo "serial stats failed"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_pipelined -- python3 $GRAFT_REPO_ROOT/bench.py --steps 100 --warmup 10 --plain > $OUT/stats_pipelined.log 2>&1 || echo "pipelined stats failed"
