@@ -227,6 +227,11 @@ struct gv_context {
     bool pca_ran = false, vision_ran = false, knn_ran = false;
     size_t off_depth = 0, off_pose = 0, off_vout = 0;
     std::vector<gv_bbox> st_boxes;   // the static boxes (host copy: convertPixelsTo3D after the wait)
+    // the handle's state at enqueue that the wait reads: uploads and gv_set_transforms may come in between
+    size_t n = 0;                    // points of the cloud the tick reads ("empty segmented cloud" is m == n)
+    int cloud = -1;                  // its cloud set: an upload into it waits for `done` on the device
+    gv_transform tf_bc{};            // camera->base of the poses and base points
+    Xform64 x_bc{};
     hipEvent_t done = nullptr;       // public stream: everything the tick enqueued has finished
     hipEvent_t fork = nullptr, join = nullptr;   // the kNN depth on a lane beside the pose branch
   } tick;
@@ -1716,7 +1721,8 @@ int gv_host_free(void *ptr)
 namespace {
 
 // The next cloud set in rotation (read two uploads ago at the latest), grown to n points, with the copy
-// stream ordered after the last frame that read it.
+// stream ordered after the last frame that read it, and after a pending tick that reads it: the tick's use_device
+// forgot every earlier reader, and the third upload after gv_tick_enqueue comes back to the tick's set.
 int begin_cloud_upload(gv_context *h, size_t n, int &target)
 {
   int rc = set_device_only(h);
@@ -1725,8 +1731,10 @@ int begin_cloud_upload(gv_context *h, size_t n, int &target)
   target = (h->cloud_cur + 1) % 3;
   h->quiet_frames = 0;   // the upload stream is in use: the frames stay off it for a while
   CloudSet &c = h->cloud[target];
+  const bool tick_reads = h->tick.pending && h->tick.cloud == target;
   if (n > c.cap) {
     if (c.release_slot >= 0) GV_HIP(hipEventSynchronize(h->ev_fin[c.release_slot]));
+    if (tick_reads) GV_HIP(hipEventSynchronize(h->tick.done));   // the tick's kernels read the block freed here
     GV_HIP(hipEventSynchronize(c.ready));
     if (c.base) GV_HIP(hipFree(c.base));
     c.base = nullptr;
@@ -1745,6 +1753,7 @@ int begin_cloud_upload(gv_context *h, size_t n, int &target)
   // satisfied would still put a barrier packet -- ~6 us of queue time -- in front of every copy)
   if (c.release_slot >= 0 && hipEventQuery(h->ev_fin[c.release_slot]) != hipSuccess)
     GV_HIP(hipStreamWaitEvent(h->stream_copy, h->ev_fin[c.release_slot], 0));
+  if (tick_reads) GV_HIP(hipStreamWaitEvent(h->stream_copy, h->tick.done, 0));   // on the device: the upload stays asynchronous
   c.release_slot = -1;
   return GV_OK;
 }
@@ -1974,8 +1983,10 @@ int gv_extract_cloud_per_bbox(gv_handle h, const gv_bbox *bboxes, int32_t nb, in
   GV_CATCH
 }
 
-// convertPixelsTo3D (grid_vision_node.cpp:309-335): B points, fp64, on the host
-static void convert_pixels_host(const gv_context *h, const gv_bbox *bboxes, const float *depths, int32_t nb, double *base_points_xyz)
+// convertPixelsTo3D (grid_vision_node.cpp:309-335): B points, fp64, on the host, with the given K^-1 and camera->base
+// transform (the tick's wait passes the transform it was enqueued with)
+static void convert_pixels_host(const double Kinv[9], const Xform64 &x_bc, const gv_bbox *bboxes, const float *depths, int32_t nb,
+                                double *base_points_xyz)
 {
   for (int32_t i = 0; i < nb; ++i) {
     // grid_vision_node.cpp:320-322 pixel centre (cv::Point2f), :325 pixelTo3D, :328-329 to base
@@ -1985,8 +1996,8 @@ static void convert_pixels_host(const gv_context *h, const gv_bbox *bboxes, cons
     const double d = depths[i];
     double cam[3];
     for (int r = 0; r < 3; ++r)
-      cam[r] = d * ((h->Kinv[r * 3] * hx + h->Kinv[r * 3 + 1] * hy) + h->Kinv[r * 3 + 2] * hz);   // cloud_detections.cpp:95
-    host::apply(h->x_bc, cam, &base_points_xyz[3 * i]);
+      cam[r] = d * ((Kinv[r * 3] * hx + Kinv[r * 3 + 1] * hy) + Kinv[r * 3 + 2] * hz);   // cloud_detections.cpp:95
+    host::apply(x_bc, cam, &base_points_xyz[3 * i]);
   }
 }
 
@@ -2007,7 +2018,7 @@ int gv_convert_pixels_to_3d(gv_handle h, const gv_bbox *bboxes, const float *dep
   if (!h || nb < 0 || (nb && (!bboxes || !depths || !base_points_xyz))) return GV_ERR_BAD_ARG;
   if (!h->has_bc) return GV_ERR_TF;
   GV_TRY
-  convert_pixels_host(h, bboxes, depths, nb, base_points_xyz);
+  convert_pixels_host(h->Kinv, h->x_bc, bboxes, depths, nb, base_points_xyz);
   return GV_OK;
   GV_CATCH
 }
@@ -3131,6 +3142,10 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   T.flags = d->flags;
   T.n_all = n_all; T.n_static = ns; T.n_dynamic = nd;
   T.st_boxes.assign(cat.begin() + n_all, cat.begin() + n_all + ns);
+  T.n = n;
+  T.cloud = h->cloud_cur;
+  T.tf_bc = h->tf_bc;
+  T.x_bc = h->x_bc;
   T.pending = true;
   return GV_OK;
   GV_CATCH
@@ -3155,14 +3170,14 @@ int gv_tick_wait(gv_handle h, gv_tick_result *r)
     const float *dep = reinterpret_cast<const float *>(blk + T.off_depth);
     if (r->static_bboxes) std::memcpy(r->static_bboxes, T.st_boxes.data(), (size_t)T.n_static * sizeof(gv_bbox));
     if (r->depths) std::memcpy(r->depths, dep, (size_t)T.n_static * sizeof(float));
-    if (r->base_points_xyz) convert_pixels_host(h, T.st_boxes.data(), dep, T.n_static, r->base_points_xyz);   // :180
+    if (r->base_points_xyz) convert_pixels_host(h->Kinv, T.x_bc, T.st_boxes.data(), dep, T.n_static, r->base_points_xyz);   // :180
   }
   if (T.vision_ran) {
     const VisionOut *vo = reinterpret_cast<const VisionOut *>(blk + T.off_vout);
     for (int32_t i = 0; i < T.n_dynamic; ++i) {
       if (!vo[i].valid) continue;   // vision_orientation.cpp:496-499
       gv_lshape_pose p = pose_of_vision_out(vo[i]);
-      host::transform_pose(h->tf_bc, p);   // transformLShapeObjects (:204)
+      host::transform_pose(T.tf_bc, p);   // transformLShapeObjects (:204)
       if (r->poses) r->poses[r->n_poses] = p;
       r->n_poses++;
     }
@@ -3172,12 +3187,12 @@ int gv_tick_wait(gv_handle h, gv_tick_result *r)
     std::memcpy(&st, blk + T.off_pose + (size_t)T.n_all * sizeof(gv_lshape_pose), sizeof(st));
     const uint8_t *valid = blk + T.off_pose + pose_block_valid_off(T.n_all);
     const uint64_t m = st.best_count ? st.n_inliers : 0;
-    if (m == 0 || (size_t)m == h->n) r->pca_empty = 1;   // empty segmented cloud: computeBBoxPose returns {} (:307-309)
+    if (m == 0 || (size_t)m == T.n) r->pca_empty = 1;   // empty segmented cloud: computeBBoxPose returns {} (:307-309)
     else
       for (int32_t b = 0; b < T.n_all; ++b) {
         if (!valid[b]) continue;   // :174-175
         gv_lshape_pose p = ps[b];
-        host::transform_pose(h->tf_bc, p);   // transformLShapeObjects (:227)
+        host::transform_pose(T.tf_bc, p);   // transformLShapeObjects (:227)
         if (r->poses) r->poses[r->n_poses] = p;
         r->n_poses++;
       }

@@ -349,7 +349,11 @@ typedef struct {
 /* One tick at a time (the reference's timer is single threaded): a second gv_tick_enqueue before gv_tick_wait returns
  * GV_ERR_STATE, and so do, between the two, the synchronous calls that would reuse the tick's result block or its
  * detection set (gv_compute_depth_for_bboxes, gv_compute_bbox_pose*, gv_segment_ground_plane, gv_extract_cloud_per_bbox,
- * ...).  Cloud uploads, gv_frame_* and the grid getters may be called; they are ordered behind the tick on gv_stream(h). */
+ * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map* and
+ * gv_set_transforms may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
+ * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
+ * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform set in
+ * between applies from the next tick on.  (tests/test_gpu_tick.py) */
 int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d);
 int gv_tick_wait(gv_handle h, gv_tick_result *r);
 int gv_tick(gv_handle h, const gv_tick_desc *d, gv_tick_result *r);   /* = enqueue + wait */
