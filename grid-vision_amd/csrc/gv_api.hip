@@ -142,6 +142,10 @@ struct gv_context {
   // grid state (resident across frames)
   float *log_odds = nullptr, *occupancy = nullptr;
   int8_t *occ_i8 = nullptr;
+  // [EXTENSION] X3 ego motion (gv_grid_move): the current base frame in the frame the layers are registered in, and
+  // the scratch copy of the three layers the resample gathers into (allocated by the first applied move)
+  host::Se2 move_residue{0.0, 0.0, 0.0};
+  uint8_t *move_scratch = nullptr;
   // per-frame count grids
   int32_t *hits_s[kStreams]{};                     // per stream (public, lane 0, lane 1); tile path: every cell written by every BIN frame
   int32_t *hits = nullptr;                  // = hits_s[stream of the last frame]
@@ -1610,7 +1614,7 @@ int gv_destroy(gv_handle h)
   for (auto &e : h->sh_t)
     if (e) (void)hipEventDestroy(e);
   if (h->stream_x) (void)hipStreamDestroy(h->stream_x);
-  void *bufs[] = {h->log_odds, h->occupancy, h->occ_i8, h->clip_end, h->miss8, h->sh_xchg, h->ray_list, h->ray_count, h->scratch_i32,
+  void *bufs[] = {h->log_odds, h->occupancy, h->occ_i8, h->move_scratch, h->clip_end, h->miss8, h->sh_xchg, h->ray_list, h->ray_count, h->scratch_i32,
                   h->tx, h->ty, h->tz, h->d_pts, h->knn_partial,
                   h->d_nodes, h->d_keep, h->d_ticket_of, h->d_pca_acc, h->d_pca_ext, h->d_pca_ticket, h->d_cellcnt, h->d_cellpre, h->d_celloff, h->d_planes,
                   h->d_plane_counts, h->d_ground, h->d_rscratch, h->d_rstate, h->d_res_ticket};
@@ -1687,6 +1691,7 @@ int gv_reset(gv_handle h)
   GV_HIP(hipMemsetAsync(h->occ_i8, 50, G, h->stream));
   GV_HIP(hipGetLastError());
   GV_HIP(hipStreamSynchronize(h->stream));
+  h->move_residue = host::Se2{0.0, 0.0, 0.0};
   return GV_OK;
   GV_CATCH
 }
@@ -2252,7 +2257,48 @@ int gv_set_log_odds(gv_handle h, const float *in)
   if (rc) return rc;
   GV_HIP(hipMemcpyAsync(h->log_odds, in, (size_t)h->g.G * sizeof(float), hipMemcpyHostToDevice, h->stream));
   GV_HIP(hipStreamSynchronize(h->stream));
+  h->move_residue = host::Se2{0.0, 0.0, 0.0};
   return GV_OK;
+}
+
+// [EXTENSION] X3: the planner (gv_host_math.hpp) picks the whole-cell resample S and keeps the rest as residue; the
+// resample is two kernels on the public stream, so it sits between the grid passes of the frames around it and
+// behind a pending tick's grid download.  No host wait (the scratch allocation of the first applied move aside).
+int gv_grid_move(gv_handle h, const gv_transform *motion, gv_grid_move_info *info)
+{
+  if (!h || !motion) return GV_ERR_BAD_ARG;
+  GV_TRY
+  host::Se2 d;
+  if (!host::se2_from_motion(*motion, d)) return GV_ERR_BAD_ARG;
+  if (h->world > 1) { h->err = "gv_grid_move: ranks own row bands of the grid, a move crosses them"; return GV_ERR_STATE; }
+  const host::GridMoveStep st = host::plan_grid_move(h->move_residue, d, h->g);
+  if (!std::isfinite(st.residue.x) || !std::isfinite(st.residue.y) || !std::isfinite(st.tx) || !std::isfinite(st.ty))
+    return GV_ERR_BAD_ARG;   // finite fields whose sum overflows
+  if (st.applied) {
+    int rc = set_device_only(h);
+    if (rc) return rc;
+    const size_t G = (size_t)h->g.G, fbytes = (G * sizeof(float) + 255) & ~(size_t)255;
+    if (!h->move_scratch) GV_HIP(hipMalloc(reinterpret_cast<void **>(&h->move_scratch), 2 * fbytes + G));
+    GridMoveArgs a{};
+    a.g = h->g;
+    a.c = st.c; a.s = st.s; a.tx = st.tx; a.ty = st.ty;
+    a.lo = h->log_odds; a.occ = h->occupancy; a.i8 = h->occ_i8;
+    a.lo_out = reinterpret_cast<float *>(h->move_scratch);
+    a.occ_out = reinterpret_cast<float *>(h->move_scratch + fbytes);
+    a.i8_out = reinterpret_cast<int8_t *>(h->move_scratch + 2 * fbytes);
+    launch_grid_move(a, h->stream);
+    launch_grid_move_copy_back(a, h->stream);
+    GV_HIP(hipGetLastError());
+  }
+  h->move_residue = st.residue;
+  if (info) {
+    info->applied = st.applied ? 1 : 0;
+    info->cos_yaw = st.c; info->sin_yaw = st.s;
+    info->tx = st.tx; info->ty = st.ty;
+    info->res_yaw = st.residue.yaw; info->res_x = st.residue.x; info->res_y = st.residue.y;
+  }
+  return GV_OK;
+  GV_CATCH
 }
 
 int gv_frame_set_detections(gv_handle h, const gv_frame_desc *d)

@@ -227,5 +227,82 @@ inline bool get_index(const GridParams &g, double x, double y, int &ix, int &iy)
   return true;
 }
 
+// ---- [EXTENSION] ego-motion compensation (gv_grid_move) ----
+// Planar rigid motion (yaw, x, y) in fp64.
+struct Se2 {
+  double yaw, x, y;
+};
+
+// (-pi, pi] for an angle in (-2pi, 2pi] (the sum of two wrapped angles)
+constexpr double kPi = 3.14159265358979323846;
+inline double wrap_pi(double a)
+{
+  if (a > kPi) a -= 2.0 * kPi;
+  else if (a <= -kPi) a += 2.0 * kPi;
+  return a;
+}
+
+// a o b: rotation a.yaw + b.yaw, translation a.t + R(a.yaw) b.t
+inline Se2 se2_compose(const Se2 &a, const Se2 &b)
+{
+  const double c = std::cos(a.yaw), s = std::sin(a.yaw);
+  return Se2{wrap_pi(a.yaw + b.yaw), a.x + (c * b.x - s * b.y), a.y + (s * b.x + c * b.y)};
+}
+
+// The planar part of a motion: yaw of the fp64-normalised quaternion, tx, ty (z, roll and pitch are dropped).
+// false when a field, or the result, is not finite (a zero quaternion among them).
+inline bool se2_from_motion(const gv_transform &m, Se2 &out)
+{
+  const double f[7] = {m.qx, m.qy, m.qz, m.qw, m.tx, m.ty, m.tz};
+  for (double v : f)
+    if (!std::isfinite(v)) return false;
+  const double n = std::sqrt(((m.qx * m.qx + m.qy * m.qy) + m.qz * m.qz) + m.qw * m.qw);
+  const double qx = m.qx / n, qy = m.qy / n, qz = m.qz / n, qw = m.qw / n;
+  const double yaw = std::atan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz));
+  if (!std::isfinite(yaw)) return false;
+  out = Se2{yaw, m.tx, m.ty};
+  return true;
+}
+
+// Largest distance from the base origin to a map corner (pos +- len/2).
+inline double map_corner_radius(const GridParams &g)
+{
+  double r = 0.0;
+  for (int i = 0; i < 4; ++i) {
+    const double x = (i & 1) ? g.pos_x + g.off_x : g.pos_x - g.off_x;
+    const double y = (i & 2) ? g.pos_y + g.off_y : g.pos_y - g.off_y;
+    r = std::max(r, std::sqrt(x * x + y * y));
+  }
+  return r;
+}
+
+// One gv_grid_move: the resample S the layers take and the residue left for the next call.
+struct GridMoveStep {
+  bool applied;        // S is not the identity
+  double yaw;          // S's rotation ...
+  double c, s;         // ... as the kernel uses it: cos / sin (exactly 1, 0 without rotation)
+  double tx, ty;       // S's translation: whole multiples of res
+  Se2 residue;         // E after the call
+};
+
+// residue E = L <- base_prev, motion D = base_prev <- base_now.  E <- E o D; S = (yaw_s, t_s) with yaw_s = yaw_E where
+// |yaw_E| * r_max >= res/2 (the rotation moves some cell centre of the map by half a cell) and 0 otherwise,
+// t_s = res * round(t_E / res); then E <- S^-1 o E.  Motion below a cell stays in E until it adds up.
+inline GridMoveStep plan_grid_move(const Se2 &residue, const Se2 &motion, const GridParams &g)
+{
+  const Se2 e = se2_compose(residue, motion);
+  GridMoveStep st;
+  st.yaw = (std::fabs(e.yaw) * map_corner_radius(g) >= 0.5 * g.res) ? e.yaw : 0.0;
+  st.tx = g.res * std::round(e.x / g.res);
+  st.ty = g.res * std::round(e.y / g.res);
+  st.c = st.yaw == 0.0 ? 1.0 : std::cos(st.yaw);
+  st.s = st.yaw == 0.0 ? 0.0 : std::sin(st.yaw);
+  st.applied = st.yaw != 0.0 || st.tx != 0.0 || st.ty != 0.0;
+  // S^-1 o E: rotation yaw_E - yaw_s, translation R(-yaw_s) (t_E - t_s)
+  const double dx = e.x - st.tx, dy = e.y - st.ty;
+  st.residue = Se2{wrap_pi(e.yaw - st.yaw), st.c * dx + st.s * dy, st.c * dy - st.s * dx};
+  return st;
+}
+
 }  // namespace host
 }  // namespace gv

@@ -92,6 +92,19 @@ struct FinalizeArgs {
 void launch_finalize(const FinalizeArgs &a, hipStream_t s);
 
 void launch_fill_f32(float *p, float v, size_t n, hipStream_t s);
+
+// [EXTENSION] X3 ego motion (gv_gridmove.hip): the three layers resampled under the planar transform S into a scratch
+// copy, then copied back into place (the resident pointers stay the same)
+struct GridMoveArgs {
+  GridParams g;
+  double c, s, tx, ty;        // S: cos / sin of its yaw, translation in metres
+  float *lo, *occ;            // resident layers
+  int8_t *i8;
+  float *lo_out, *occ_out;    // scratch copy (16-byte aligned)
+  int8_t *i8_out;
+};
+void launch_grid_move(const GridMoveArgs &a, hipStream_t s);             // resident -> scratch
+void launch_grid_move_copy_back(const GridMoveArgs &a, hipStream_t s);   // scratch -> resident
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

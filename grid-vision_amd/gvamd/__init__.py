@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "gv_host_free", "gv_frame_set_detections_async", "gv_frame_fence",
     "gv_to_occupancy_grid_async", "gv_frame_enqueue_sharded", "gv_time_frame_sharded_stages", "gv_shard_band_rows",
     "gv_shard_slice_words", "gv_device_layers", "gv_tick_enqueue", "gv_tick_wait", "gv_tick",
-    "gv_comm_info", "gv_publish_grid_async",
+    "gv_comm_info", "gv_publish_grid_async", "gv_grid_move",
 ]
 
 
@@ -66,6 +66,12 @@ class Transform(C.Structure):
 class GridInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("resolution", C.c_double),
                 ("origin_x", C.c_double), ("origin_y", C.c_double)]
+
+
+class GridMoveInfo(C.Structure):
+    """gv_grid_move_info: what one gv_grid_move did"""
+    _fields_ = [("applied", C.c_int32), ("cos_yaw", C.c_double), ("sin_yaw", C.c_double), ("tx", C.c_double),
+                ("ty", C.c_double), ("res_yaw", C.c_double), ("res_x", C.c_double), ("res_y", C.c_double)]
 
 
 class FrameDesc(C.Structure):
@@ -413,6 +419,17 @@ class GridVisionHIP:
         a = _f32(a)
         assert a.size == self.G
         self._ck(self._lib.gv_set_log_odds(self._h, _ptr(a)), "set_log_odds")
+
+    # ---- [EXTENSION] ego motion
+    def grid_move(self, motion):
+        """motion: base_prev <- base_now as a 7-vector (qx, qy, qz, qw, tx, ty, tz), like make_tf.  Asynchronous on
+        stream(); returns the GridMoveInfo fields as a dict (applied as a bool)."""
+        m = make_tf(motion)
+        info = GridMoveInfo()
+        self._ck(self._lib.gv_grid_move(self._h, C.byref(m), C.byref(info)), "gv_grid_move")
+        out = {k: getattr(info, k) for k, _ in GridMoveInfo._fields_}
+        out["applied"] = bool(out["applied"])
+        return out
 
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):

@@ -28,6 +28,9 @@ struct FlowParams {
   // (gv_tick_*): the poses go from the kernel that computes them into the grid pass without leaving the device.
   // false: the reference's call-by-call sequence over the mirror (one synchronous call per reference function).
   bool fused = true;
+  // [EXTENSION] X3: move the grid with the vehicle -- every tick first resamples the layers by TickInput::motion
+  // (gv_grid_move) so that they stay registered to the current base frame.  false: the reference's fixed grid.
+  bool ego_motion = false;
 };
 
 // what one tick of the 50 ms timer (grid_vision_node.cpp:49-50) has to work with
@@ -43,6 +46,9 @@ struct TickInput {
   // the orientation network (VisionOrientation::runInference, :193): called with the dynamic boxes, fills
   // orient[n * 4], conf[n * 2], dims[n * 3]; only used when use_vision_orientation
   std::function<void(const std::vector<BoundingBox> &, std::vector<float> &, std::vector<float> &, std::vector<float> &)> orientation_net;
+  // [EXTENSION] X3 (FlowParams::ego_motion): base_prev <- base_now since the previous tick, the tf2 lookup
+  // lookupTransform(base, t_prev, base, t_now, odom); nullptr: no motion known this tick
+  const gv_transform *motion = nullptr;
 };
 
 enum class TickBranch {
@@ -75,6 +81,8 @@ public:
   TickResult tick(const TickInput &in)
   {
     TickResult r;
+    // the vehicle moved whatever this tick goes on to do: the grid follows first, ahead of the map update
+    if (p_.ego_motion && in.motion) grid_.moveMap(*in.motion);
     // :111 -- the reference tests `init_image_.empty() && cloud_.empty()` (both missing); kept as it is
     if (!in.have_image && !in.have_cloud) {
       r.branch = TickBranch::MissingInputs;

@@ -194,6 +194,14 @@ public:
     gv::check(gv_update_map_points(ctx_.handle(), reinterpret_cast<const double *>(base_points.data()), bboxes.data(),
                                    (int32_t)bboxes.size()), ctx_.handle(), "gv_update_map_points");
   }
+  // [EXTENSION] X3 grid_map's GridMap::move() for the base-frame grid: motion = base_prev <- base_now (tf2's
+  // time-travel lookup through odom).  Asynchronous on the context's stream, like the frame calls.
+  gv_grid_move_info moveMap(const gv_transform &motion)
+  {
+    gv_grid_move_info info{};
+    gv::check(gv_grid_move(ctx_.handle(), &motion, &info), ctx_.handle(), "gv_grid_move");
+    return info;
+  }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {

@@ -20,8 +20,8 @@
  *     one thread at a time; handles are independent;
  *   - host pointers are caller owned and may be pageable; every call returns
  *     after its results are complete in the caller's buffers (synchronous),
- *     except the streaming calls gv_frame_enqueue, gv_cloud_upload_*_async and
- *     gv_frame_set_detections_async (see there);
+ *     except the streaming calls gv_frame_enqueue, gv_cloud_upload_*_async,
+ *     gv_frame_set_detections_async and gv_grid_move (see there);
  *   - grid layers use the reference's storage order: grid_map's column-major
  *     Eigen::MatrixXf(size0,size1) with row = x index, i.e. linear = iy*nx+ix;
  *   - [EXTENSION] marks what north_star asks for and the reference lacks.
@@ -251,6 +251,35 @@ int gv_get_occupancy(gv_handle h, float *out);
 /* Layer write (tests / checkpoint restore): G floats */
 int gv_set_log_odds(gv_handle h, const float *in);
 
+/* ------------------------------------------------ [EXTENSION] ego motion -- */
+/* The reference keeps its grid fixed in base_link (src/occupancy_grid.cpp:4-14): nothing moves it when the vehicle
+ * moves.  gv_grid_move is grid_map's GridMap::move() for that grid: it resamples the three layers (log_odds,
+ * occupancy, the packed int8) so that they stay registered to the current base frame.
+ *
+ * motion = pose of the current base frame in the previous one (base_prev <- base_now), i.e. what
+ * tf2 lookupTransform(base, t_prev, base, t_now, odom) returns.  Planar: only the yaw of the normalised quaternion,
+ * atan2(2(qw qz + qx qy), 1 - 2(qy^2 + qz^2)), and tx, ty are used; z, roll and pitch are ignored.
+ * The handle keeps an fp64 SE(2) residue E (the current base frame in the frame the layers are registered in; the
+ * identity after gv_create, gv_reset and gv_set_log_odds).  Each call composes E <- E o motion and picks the resample
+ * S: its rotation is E's where that moves a map corner by at least half a cell (|yaw| * r_max >= res/2, r_max the
+ * largest distance from the base origin to a corner), 0 otherwise; its translation is E's rounded to whole cells.
+ * E <- S^-1 o E keeps what is left, so sub-cell motion adds up over calls instead of being rounded away.
+ * New cell (ix, iy) takes, bit for bit, all three layers of the old cell that contains S applied to its centre;
+ * cells whose source lies off the map get the constructor state (0.0, 0.5, 50).  No new float value is created.
+ * Asynchronous: the resample is enqueued on gv_stream(h) (nothing when S is the identity) and the call returns
+ * without a host wait; it executes between the grid passes of the frames enqueued before and after it.  Allowed
+ * between gv_tick_enqueue and gv_tick_wait (the tick's grid_out still receives the grid before the move).
+ * gv_device_layers keeps returning the same pointers.  GV_ERR_BAD_ARG for a null handle or motion or a non-finite
+ * field; GV_ERR_STATE with a communicator of more than one rank (ranks own row bands, a rotation crosses them). */
+typedef struct {
+  int32_t applied;              /* 1 = the layers were resampled, 0 = motion kept as residue only */
+  double cos_yaw, sin_yaw;      /* rotation of the applied resample S (1, 0 when none)            */
+  double tx, ty;                /* translation of S in metres: whole multiples of resolution       */
+  double res_yaw, res_x, res_y; /* residue carried to the next call                                */
+} gv_grid_move_info;
+/* info may be NULL */
+int gv_grid_move(gv_handle h, const gv_transform *motion, gv_grid_move_info *info);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
@@ -349,8 +378,8 @@ typedef struct {
 /* One tick at a time (the reference's timer is single threaded): a second gv_tick_enqueue before gv_tick_wait returns
  * GV_ERR_STATE, and so do, between the two, the synchronous calls that would reuse the tick's result block or its
  * detection set (gv_compute_depth_for_bboxes, gv_compute_bbox_pose*, gv_segment_ground_plane, gv_extract_cloud_per_bbox,
- * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map* and
- * gv_set_transforms may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
+ * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map*,
+ * gv_grid_move and gv_set_transforms may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
  * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
  * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform set in
  * between applies from the next tick on.  (tests/test_gpu_tick.py) */
