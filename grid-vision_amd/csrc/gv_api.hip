@@ -146,6 +146,9 @@ struct gv_context {
   // the scratch copy of the three layers the resample gathers into (allocated by the first applied move)
   host::Se2 move_residue{0.0, 0.0, 0.0};
   uint8_t *move_scratch = nullptr;
+  // [EXTENSION] X4 height band of the lidar map update (gv_set_height_band): handle configuration, copied into the
+  // kernel arguments of every binning launch at enqueue
+  HeightBand band{-INFINITY, INFINITY, 0};
   // per-frame count grids
   int32_t *hits_s[kStreams]{};                     // per stream (public, lane 0, lane 1); tile path: every cell written by every BIN frame
   int32_t *hits = nullptr;                  // = hits_s[stream of the last frame]
@@ -796,6 +799,7 @@ int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, siz
   a.keys = h->bin_keys[k];
   a.tab = h->bin_tab[k];
   a.tile_total = h->bin_total[k][h->bin_parity[k]];
+  a.band = h->band;
   if (fold_rects) {   // the frame's rectangles ride the partition launch
     a.rect_poses = D.poses;
     a.n_rect_poses = D.n_poses;
@@ -1076,6 +1080,7 @@ int enqueue_frame_generic(gv_context *h, bool stage_events)
     a.cell_idx = keep_cell ? h->cell_idx : nullptr;
     a.bbox_id = h->bbox_id;
     a.do_bin = do_bin; a.do_ray = do_ray; a.do_bbox = do_bbox;
+    a.band = h->band;
     launch_points(a, s);
   }
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStagePoints + 1], s));
@@ -2299,6 +2304,22 @@ int gv_grid_move(gv_handle h, const gv_transform *motion, gv_grid_move_info *inf
   }
   return GV_OK;
   GV_CATCH
+}
+
+// [EXTENSION] X4: handle configuration only, no device work.  Every binning launch copies h->band into its kernel
+// arguments, so frames and ticks already enqueued keep the band they were enqueued with.
+int gv_set_height_band(gv_handle h, const gv_height_band *band)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  if (!band) {
+    h->band = HeightBand{-INFINITY, INFINITY, 0};
+    return GV_OK;
+  }
+  if (std::isnan(band->z_ground) || std::isnan(band->z_max) || band->z_ground > band->z_max ||
+      (band->ground_clears != 0 && band->ground_clears != 1))
+    return GV_ERR_BAD_ARG;
+  h->band = HeightBand{band->z_ground, band->z_max, band->ground_clears};
+  return GV_OK;
 }
 
 int gv_frame_set_detections(gv_handle h, const gv_frame_desc *d)

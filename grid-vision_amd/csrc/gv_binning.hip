@@ -131,14 +131,19 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
     {
       const Mat34f mb = GV_KARG(m_base);   // constants are fetched where they are used (gv_device.hpp, load_karg)
       const GridParams g = GV_KARG(g);
+      const HeightBand hb = GV_KARG(band);
       double dx[PP], dy[PP], qx[PP], qy[PP];
-      bool fin[PP], in0[PP], rx[PP], ry[PP];
+      bool fin[PP], in0[PP], rx[PP], ry[PP], obs[PP], gnd[PP];
       bool any_risky = false;
 #pragma unroll
       for (int u = 0; u < PP; ++u) {
         float bx, by, bz;
         xform34(mb, px[u], py[u], pz[u], bx, by, bz);
         fin[u] = live[u] & isfinite(bx) & isfinite(by) & isfinite(bz);   // (bitwise: no short-circuit branches)
+        // X4 height band on the fp32 base-frame z: z_ground <= bz <= z_max is an obstacle, bz < z_ground a ground
+        // return that ends a free-space ray when the band clears (band off: every finite point is an obstacle)
+        obs[u] = !(bz < hb.z_ground) & !(bz > hb.z_max);
+        gnd[u] = (bz < hb.z_ground) & (hb.clears != 0);
         // get_index_fast (gv_device.hpp), flattened
         const double x = (double)bx, y = (double)by;
         const double tx = -((x - g.pos_x) - g.off_x);
@@ -167,8 +172,13 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
         const bool inside = in0[u] & (jx >= 0) & (jy >= 0) & (jx < g.nx) & (jy < g.ny);
         const unsigned tile = (unsigned)((jy >> kBinTileLog) * a.tiles_x + (jx >> kBinTileLog));
         const unsigned key = (tile << 16) | (unsigned)(((jy & (kBinTile - 1)) << kBinTileLog) | (jx & (kBinTile - 1)));
-        const unsigned st = inside ? key : ((RAY & fin[u] & (a.org.valid != 0)) ? kStagedOutside : kStagedNone);
-        if (inside) atomicAdd(&hist[tile], 1u);
+        // in map: an obstacle is a hit key; a clearing ground return a ray end at its own cell, own cell included
+        // (the clipped-end key kind).  Out of map: the clipped end of an obstacle or a clearing ground return.
+        const bool ray = RAY & fin[u] & (a.org.valid != 0);
+        const bool hit = inside & obs[u];
+        const bool gend = ray & inside & gnd[u];
+        const unsigned st = hit ? key : (gend ? (key | kKeyClip) : ((ray & !inside & (obs[u] | gnd[u])) ? kStagedOutside : kStagedNone));
+        if (hit | gend) atomicAdd(&hist[tile], 1u);
         staged[k] = st;
         if (RAY) {
           // out-of-map points (a minority) need the fp64 slab clip, ~10x the work of an in-map point: their

@@ -63,14 +63,21 @@ __global__ void __launch_bounds__(BIN ? 1024 : 256) k_points(PointsArgs a)
       int cell = -1;
       bool outside = false;
       if (live && isfinite(bx) && isfinite(by) && isfinite(bz)) {
+        // X4 height band (gv_binning.hip, k_bin_partition): obstacles are hits, clearing ground returns ray ends
+        const bool obs = !(bz < a.band.z_ground) && !(bz > a.band.z_max);
+        const bool gnd = RAY && a.org.valid && bz < a.band.z_ground && a.band.clears;
         int ix, iy;
         if (get_index_fast(a.g, (double)bx, (double)by, ix, iy)) {
           cell = iy * a.g.nx + ix;
-          const unsigned slot = ((unsigned)cell * 2654435761u) >> 20;   // 12 bits
-          const unsigned old = atomicCAS(&s_key[slot], kHitEmpty, (unsigned)cell);
-          if (old == kHitEmpty || old == (unsigned)cell) atomicAdd(&s_cnt[slot], 1u);
-          else atomicAdd(&a.hits[cell], 1);   // no-return global_atomic_add
-        } else if (RAY && a.org.valid) {
+          if (obs) {
+            const unsigned slot = ((unsigned)cell * 2654435761u) >> 20;   // 12 bits
+            const unsigned old = atomicCAS(&s_key[slot], kHitEmpty, (unsigned)cell);
+            if (old == kHitEmpty || old == (unsigned)cell) atomicAdd(&s_cnt[slot], 1u);
+            else atomicAdd(&a.hits[cell], 1);   // no-return global_atomic_add
+          } else if (gnd) {
+            a.clip_end[cell] = 1;   // ray end at its own cell, own cell included (idempotent byte store)
+          }
+        } else if (RAY && a.org.valid && (obs || gnd)) {
           outside = true;
         }
       }

@@ -44,6 +44,7 @@ struct PointsArgs {
   int32_t *cell_idx;   // N or null
   int16_t *bbox_id;    // N or null
   bool do_bin, do_ray, do_bbox;
+  HeightBand band;     // X4: which binned points count as hits / ray ends (off: {-inf, +inf, 0})
 };
 void launch_points(const PointsArgs &a, hipStream_t s);
 // float thresholds + 16x16-pixel tile candidate masks of the bbox test, from the device copy of the bboxes
@@ -141,6 +142,7 @@ struct BinArgs {
   Rect *rects_out;
   unsigned long long *dbg; // diagnostic build: 16 clock stamps per workgroup (null in production)
   unsigned long long *tl;  // diagnostic build: {first workgroup in, last workgroup out} of this launch (GV_TIMELINE)
+  HeightBand band;         // X4: runtime thresholds (GV_KARG), not a template parameter (off: {-inf, +inf, 0})
 };
 constexpr size_t kBinBBoxLdsMax = 24 * 1024;   // LDS the partition kernel may spend on the bbox-test tables
 uint32_t bin_chunk_for(size_t n);

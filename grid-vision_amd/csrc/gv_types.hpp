@@ -43,6 +43,14 @@ struct RayOrigin {
   int32_t valid;      // 0: origin outside the map -> no rays this frame
 };
 
+// [EXTENSION] X4 height band of the lidar map update (gv_set_height_band).  Base-frame z < z_ground: ground return
+// (the end of a free-space ray, own cell included, when clears; else dropped), z > z_max: dropped.  Off is
+// {-inf, +inf, 0}: every finite point is an obstacle, as without the band.
+struct HeightBand {
+  float z_ground, z_max;
+  int32_t clears;
+};
+
 // Inclusive index rectangle of one object (updateGridCellsFast block).
 struct Rect {
   int32_t x0, y0, x1, y1;

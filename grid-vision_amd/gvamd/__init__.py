@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "gv_host_free", "gv_frame_set_detections_async", "gv_frame_fence",
     "gv_to_occupancy_grid_async", "gv_frame_enqueue_sharded", "gv_time_frame_sharded_stages", "gv_shard_band_rows",
     "gv_shard_slice_words", "gv_device_layers", "gv_tick_enqueue", "gv_tick_wait", "gv_tick",
-    "gv_comm_info", "gv_publish_grid_async", "gv_grid_move",
+    "gv_comm_info", "gv_publish_grid_async", "gv_grid_move", "gv_set_height_band",
 ]
 
 
@@ -72,6 +72,11 @@ class GridMoveInfo(C.Structure):
     """gv_grid_move_info: what one gv_grid_move did"""
     _fields_ = [("applied", C.c_int32), ("cos_yaw", C.c_double), ("sin_yaw", C.c_double), ("tx", C.c_double),
                 ("ty", C.c_double), ("res_yaw", C.c_double), ("res_x", C.c_double), ("res_y", C.c_double)]
+
+
+class HeightBand(C.Structure):
+    """gv_height_band: obstacle height band of the lidar map update"""
+    _fields_ = [("z_ground", C.c_float), ("z_max", C.c_float), ("ground_clears", C.c_int32)]
 
 
 class FrameDesc(C.Structure):
@@ -430,6 +435,18 @@ class GridVisionHIP:
         out = {k: getattr(info, k) for k, _ in GridMoveInfo._fields_}
         out["applied"] = bool(out["applied"])
         return out
+
+    # ---- [EXTENSION] height band of the lidar map update
+    def set_height_band(self, z_ground, z_max=None, ground_clears=True):
+        """base-frame z < z_ground: ground return (a free-space ray end when ground_clears), z > z_max: ignored;
+        set_height_band(None) turns the band off.  Thresholds are rounded to float32 as the C struct holds them;
+        ground_clears may also be an int (anything but 0 / 1 is the library's GV_ERR_BAD_ARG)."""
+        if z_ground is None:
+            self._ck(self._lib.gv_set_height_band(self._h, None), "gv_set_height_band")
+            return
+        clears = int(ground_clears) if not isinstance(ground_clears, bool) else (1 if ground_clears else 0)
+        b = HeightBand(float(z_ground), float(z_max), clears)
+        self._ck(self._lib.gv_set_height_band(self._h, C.byref(b)), "gv_set_height_band")
 
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):

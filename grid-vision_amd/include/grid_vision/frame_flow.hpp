@@ -31,6 +31,13 @@ struct FlowParams {
   // [EXTENSION] X3: move the grid with the vehicle -- every tick first resamples the layers by TickInput::motion
   // (gv_grid_move) so that they stay registered to the current base frame.  false: the reference's fixed grid.
   bool ego_motion = false;
+  // [EXTENSION] X4: obstacle height band of the lidar map update (gv_set_height_band), set once by the constructor.
+  // Base-frame z below lidar_ground_z is ground (it clears free space when lidar_ground_clears), above
+  // lidar_max_obstacle_z it is ignored.  false: every lidar return is an obstacle.
+  bool lidar_height_band = false;
+  double lidar_ground_z = 0.3;
+  double lidar_max_obstacle_z = 2.5;
+  bool lidar_ground_clears = true;
 };
 
 // what one tick of the 50 ms timer (grid_vision_node.cpp:49-50) has to work with
@@ -73,7 +80,10 @@ struct TickResult {
 
 class FrameFlow {
 public:
-  FrameFlow(GridVisionContext &ctx, OccupancyGridMap &grid, const FlowParams &p) : ctx_(ctx), grid_(grid), vision_(ctx), p_(p) {}
+  FrameFlow(GridVisionContext &ctx, OccupancyGridMap &grid, const FlowParams &p) : ctx_(ctx), grid_(grid), vision_(ctx), p_(p)
+  {
+    if (p_.lidar_height_band) grid_.setHeightBand(p_.lidar_ground_z, p_.lidar_max_obstacle_z, p_.lidar_ground_clears);
+  }
 
   // base <- camera and camera <- lidar known (transformLidarToCamera's lookup, :280-307)
   void setTransformsAvailable(bool ok) { have_tf_ = ok; }

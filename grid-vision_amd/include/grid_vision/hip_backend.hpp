@@ -202,6 +202,15 @@ public:
     gv::check(gv_grid_move(ctx_.handle(), &motion, &info), ctx_.handle(), "gv_grid_move");
     return info;
   }
+  // [EXTENSION] X4 obstacle height band of the lidar map update (base-frame z, metres; rounded to float): below
+  // ground_z a return is ground -- it clears free space when ground_clears --, above max_obstacle_z it is ignored.
+  // Applies to the frames and ticks enqueued afterwards.
+  void setHeightBand(double ground_z, double max_obstacle_z, bool ground_clears = true)
+  {
+    const gv_height_band b{(float)ground_z, (float)max_obstacle_z, ground_clears ? 1 : 0};
+    gv::check(gv_set_height_band(ctx_.handle(), &b), ctx_.handle(), "gv_set_height_band");
+  }
+  void clearHeightBand() { gv::check(gv_set_height_band(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_height_band"); }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {

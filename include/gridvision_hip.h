@@ -280,6 +280,29 @@ typedef struct {
 /* info may be NULL */
 int gv_grid_move(gv_handle h, const gv_transform *motion, gv_grid_move_info *info);
 
+/* ------------------------------------------------ [EXTENSION] height band -- */
+/* The lidar map update (X1/X2: gv_frame_*, gv_tick with GV_TICK_LIDAR_BIN) counts every finite point as an obstacle.
+ * The band classifies each point by its fp32 base-frame z (base<-lidar, the same transform and operation order as its
+ * cell index), compared in fp32 exactly as written below, so z == z_ground and z == z_max are obstacles:
+ *   z_ground <= z <= z_max   obstacle: a hit in map, a clipped ray end out of map (as without the band);
+ *   z <  z_ground            ground return: with ground_clears, the end of a free-space ray that includes its own cell
+ *                            (in map) or the clipped end on the border (out of map), never a hit; without, ignored;
+ *   z >  z_max               ignored (overhangs, tree tops).
+ * cell_idx stays the geometric cell of every point; bbox_id and the camera-side calls ignore the band.  gv_get_hits
+ * counts the obstacles; gv_get_miss and gv_get_ray_stats describe the ends that were marched.
+ * Handle configuration like the transforms: kept through gv_reset, gv_set_log_odds and gv_grid_move, applied to the
+ * frames and ticks enqueued after the call (those in flight keep theirs); allowed between gv_tick_enqueue and
+ * gv_tick_wait.  {-inf, +inf, any} gives the same bytes as the band off.  GV_ERR_BAD_ARG (band unchanged) for a null
+ * handle, a NaN threshold, z_ground > z_max or ground_clears not in {0, 1}; +-inf are allowed. */
+typedef struct {
+  float z_ground;          /* base-frame z: a point with z <  z_ground is a ground return          */
+  float z_max;             /* base-frame z: a point with z >  z_max    is above the band (ignored)  */
+  int32_t ground_clears;   /* 1: a ground return ends a free-space ray that includes its own cell  */
+                           /* 0: a ground return is ignored like a point above the band            */
+} gv_height_band;
+/* NULL turns the band off (the state after gv_create). */
+int gv_set_height_band(gv_handle h, const gv_height_band *band);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
@@ -379,10 +402,10 @@ typedef struct {
  * GV_ERR_STATE, and so do, between the two, the synchronous calls that would reuse the tick's result block or its
  * detection set (gv_compute_depth_for_bboxes, gv_compute_bbox_pose*, gv_segment_ground_plane, gv_extract_cloud_per_bbox,
  * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map*,
- * gv_grid_move and gv_set_transforms may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
+ * gv_grid_move, gv_set_transforms and gv_set_height_band may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
  * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
- * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform set in
- * between applies from the next tick on.  (tests/test_gpu_tick.py) */
+ * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform or height
+ * band set in between applies from the next tick on.  (tests/test_gpu_tick.py) */
 int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d);
 int gv_tick_wait(gv_handle h, gv_tick_result *r);
 int gv_tick(gv_handle h, const gv_tick_desc *d, gv_tick_result *r);   /* = enqueue + wait */

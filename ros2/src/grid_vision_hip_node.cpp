@@ -83,7 +83,12 @@ public:
     fp.use_vision_orientation = use_vision_orientation_;
     fp.lidar_binning = lidar_binning_;
     fp.lidar_raymarch = lidar_raymarch_;
-    flow_ = std::make_unique<grid_vision::FrameFlow>(*ctx_, *occ_grid_, fp);
+    // [EXTENSION] X4 obstacle height band (base-frame z, metres; the library takes them as float)
+    fp.lidar_height_band = declare_parameter("lidar_height_band", false);
+    fp.lidar_ground_z = declare_parameter("lidar_ground_z", 0.3);
+    fp.lidar_max_obstacle_z = declare_parameter("lidar_max_obstacle_z", 2.5);
+    fp.lidar_ground_clears = declare_parameter("lidar_ground_clears", true);
+    flow_ =std::make_unique<grid_vision::FrameFlow>(*ctx_, *occ_grid_, fp);
 
     if (image_topic_.empty() || lidar_topic_.empty()) {
       RCLCPP_ERROR(get_logger(), "Check if topic name or weight file is assigned");
