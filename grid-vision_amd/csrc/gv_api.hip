@@ -2696,8 +2696,8 @@ static size_t pose_block_bytes(int32_t nb) { return pose_block_valid_off(nb) + (
 // without a host wait in between; only the nb poses come back.  with_ground: the points of the refined RANSAC
 // plane in *d_rstate are dropped first (computeBBoxPose, cloud_detections.cpp:300-321), and the "empty segmented
 // cloud" outcomes (:307-309) are decided on the device.
-// poses_dev (optional): the camera-frame poses also go to device memory (length < 0 marks "no pose": what
-// k_rects_from_poses skips), for a map update enqueued right behind this without a trip to the host.
+// poses_dev (optional): the camera-frame poses also go to device memory (a NaN length marks "no pose": its
+// corners fail getIndex, so k_rects_from_poses gives it no cells), for a map update enqueued right behind this without a trip to the host.
 static int enqueue_bbox_pose(gv_context *h, int32_t nb, bool with_ground, float thr_f, uint8_t *out, const CallDone &done,
                              gv_lshape_pose *poses_dev = nullptr)
 {

@@ -1295,7 +1295,7 @@ __global__ void __launch_bounds__(256) k_pca_extent(const CellNode *__restrict__
       double2 *dd = reinterpret_cast<double2 *>(poses_dev + b0);
       for (int i = threadIdx.x; i < nbc * 5; i += 256) {
         double2 v = src[i];
-        if (i % 5 == 3 && !s_ok[i / 5]) v.y = -1.0;   // length (double 7 of 10) = -1: k_rects_from_poses skips the box
+        if (i % 5 == 3 && !s_ok[i / 5]) v.y = __builtin_nan("");   // length (double 7 of 10) = NaN: no pose, no cells
         dd[i] = v;
       }
     }

@@ -185,10 +185,9 @@ __device__ __forceinline__ Rect rect_from_pose(const GridParams &g, const gv_lsh
 {
   const double hx = p.length / 2.0, hy = p.width / 2.0;
   const double c[8] = {p.px - hx, p.py - hy, p.px + hx, p.py - hy, p.px + hx, p.py + hy, p.px - hx, p.py + hy};
-  Rect r = rect_from_corners(g, c);
-  // a pose the vision kernel marked invalid carries length < 0
-  if (!(p.length >= 0.0)) r.valid = 0;
-  return r;
+  // a negative length or width fills the same block as its absolute value (min / max of the corner indices, as the
+  // reference does); "no pose" (k_vision, the tick's PCA poses) is a NaN length, whose corners fail getIndex
+  return rect_from_corners(g, c);
 }
 
 // extractCloudPerBBox (src/cloud_detections.cpp:264-288) for one camera-frame point: index of

@@ -314,7 +314,7 @@ size_t pca_ext_words(int nb);   // 32-bit words of ext
 // (pca_acc_words / pca_ext_words) / *ticket are zero on entry and left zero.  n_sel: device address of the number of
 // selected points (blk_off[n_buckets / 4096] of the bucket scan).  st_copy (optional): *st is copied there (one read-back
 // block for poses, flags and state); poses_dev (optional, device memory): a second copy of the camera-frame poses with
-// length = -1 where valid[b] == 0
+// a NaN length where valid[b] == 0 (no pose: its corners fail getIndex, so k_rects_from_poses gives no cells)
 void launch_pca_rect(const CellNode *sorted, const uint32_t *n_sel, uint32_t n, const uint8_t *keep, long long *acc, unsigned *ext,
                      unsigned *ticket, int nb, const RansacState *st, bool use_plane, gv_lshape_pose *poses, uint8_t *valid,
                      RansacState *st_copy, const CallDone &done, hipStream_t s, gv_lshape_pose *poses_dev = nullptr);

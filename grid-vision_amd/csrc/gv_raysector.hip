@@ -1132,7 +1132,9 @@ bool launch_ray_sectors(const SectorArgs &a, hipStream_t s, hipEvent_t done, hip
 // ------------------------------------------------------ tile grid pass -----
 __device__ __forceinline__ float sigmoid_ref_t(float l)
 {
-  const float e = (float)exp((double)(-l));   // fp64 exp rounded once: agrees with glibc's expf, which the oracle calls (an fp32 expf measured +2 % on the frame, round 3, and is not bit-equal)
+  // fp64 exp rounded once: the correctly rounded expf (glibc's, which the oracle calls, is one ulp off on 118,468
+  // fp32 inputs in [-3.6, 2]; tests/test_gpu_grid_pass.py).  An fp32 expf measured +2 % on the frame, round 3.
+  const float e = (float)exp((double)(-l));
   return 1.0f / (1.0f + e);
 }
 

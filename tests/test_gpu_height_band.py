@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import grid_pass_ref
 import height_band_ref as ref
 import oracle_lib as ol
 from gvamd import synth
@@ -35,10 +36,9 @@ def _handle(gvamd, grid, tfs):
 
 
 def _check_grid(h, og):
-    assert np.array_equal(h.log_odds(), og.log_odds), "log-odds are adds + clamp: expected bit-equal"
-    assert np.max(np.abs(h.occupancy() - og.occupancy)) <= 1e-5
-    d = h.to_occupancy_grid()[0].astype(np.int16) - og.to_occupancy_grid()[0].astype(np.int16)
-    assert np.abs(d).max() <= 1 and np.count_nonzero(d) <= 1e-4 * d.size
+    """log-odds and int8 bit-equal; occupancy correctly rounded, and the oracle's where the host's expf is"""
+    grid_pass_ref.check_layers(h.log_odds(), h.occupancy(), h.to_occupancy_grid()[0], og.log_odds, og.occupancy,
+                               og.to_occupancy_grid()[0])
 
 
 def _ids(tfs, x, y, z, bboxes):
