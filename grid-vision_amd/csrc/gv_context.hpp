@@ -1,0 +1,344 @@
+// gv_context.hpp -- the host side's handle (one device + one resident grid + its HIP streams), the buffer sets it
+// is made of, and what the gv_api*.hip translation units share: the error macros and the internal functions
+// more than one of them calls.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "gv_host_math.hpp"
+#include "gv_test_hooks.h"
+#include "gv_kernels.hpp"
+#include "gv_resources.hpp"
+
+using namespace gv;
+
+struct ncclComm;   // rccl.h is gv_api_shard.hip's alone
+
+namespace gv_internal __attribute__((visibility("hidden"))) {
+
+// One of the three resident clouds: frames read the current one while the copy stream fills the next
+// (cloudCallback / timerCallback overlap, src/grid_vision_node.cpp:103-106,108-244).  Three, so that the
+// set being filled was last read two uploads ago: its readers have long finished in a streaming run.
+struct CloudSet {
+  DevBuf<float> base;           // one allocation of 3 * cap floats
+  float *x = nullptr, *y = nullptr, *z = nullptr;   // base, base + n, base + 2n of the cloud it holds (SoA, back to back)
+  size_t cap = 0;
+  DevBuf<uint8_t> raw;          // PointCloud2 bytes before the de-interleave
+  Event ready;                  // copy stream: upload complete
+  int release_slot = -1;        // ev_fin[release_slot]: the last frame that reads this set (-1: none since it was filled)
+  uint32_t seen = ~0u;          // bit k: stream k has waited for `ready` (or the upload is known complete)
+};
+
+// Per-frame detection inputs (bboxes, poses / network outputs) and what the device derives from them.
+// Sets 0/1 alternate between "read by the frames in flight" and "being uploaded"; set 2 belongs to the
+// standalone entry points of the reference surface, which therefore never disturb the frame's inputs.
+struct DetSet {
+  DevBuf<uint8_t> block;                     // ONE device allocation = one H2D copy per frame; the arrays below point into it
+  gv_bbox *bboxes = nullptr;
+  gv_lshape_pose *poses = nullptr;
+  float *orient = nullptr, *conf = nullptr, *dims = nullptr;
+  DevBuf<float4> bbox_f;                     // float thresholds of the bbox test
+  DevBuf<unsigned long long> tile_mask;      // candidate masks per 16x16-pixel tile
+  int32_t cap = 0;
+  int32_t mask_words = 1;
+  int32_t nb = 0, n_poses = 0;
+  uint32_t flags = 0;
+  bool valid = false;           // a gv_frame_set_detections* call has filled this set
+  PinnedBuf stage;              // pinned host copy of the caller's arrays (free to reuse on return)
+  Event ready;                  // the set's last upload is complete (and has left its staging block)
+  uint32_t seen = ~0u;          // bit k: stream k (0 public, 1 / 2 the lanes) is ordered after the upload
+  int release_slot = -1;        // last frame that reads this set: ev_fin[release_slot] (a finished grid pass => every earlier frame finished)
+  uint32_t readers = 0;         // bit k: a frame on stream k has read this set since its last upload
+};
+
+// Buffers of one frame in flight (gv_context::fs[p]: set 0 the serial frame and standalone calls, two sets per lane):
+// end bitmaps, free-cell bitmaps, rectangles, ray statistics
+struct FrameSet {
+  DevBuf<uint32_t> ends;        // one allocation: [hitN | clipN | hitT | clipT], ends_words in all
+  uint32_t *hitN = nullptr, *clipN = nullptr, *hitT = nullptr, *clipT = nullptr;
+  DevBuf<uint32_t> free_;       // [freeN | freeT]: free-cell bitmaps of the ray stage
+  uint32_t *freeN = nullptr, *freeT = nullptr;
+  DevBuf<Rect> rects;
+  DevBuf<unsigned long long> stats;
+  int fin_slot = -1;            // ev_fin slot of the last frame that used the set
+};
+
+// What each stream owns (gv_context::sb[k]: 0 public, 1.. the lanes): two frames in flight write their count grid,
+// per-point outputs and binning scratch side by side -- partition(f+1) of one lane runs beside tiles(f) of the other
+struct StreamBufs {
+  DevBuf<int32_t> hits;         // tile path: every cell written by every BIN frame
+  DevBuf<int32_t> cell_idx;     // per-point outputs
+  DevBuf<int16_t> bbox_id;
+  DevBuf<VisionOut> vout;
+  DevBuf<uint16_t> bin_keys, bin_tab;   // tile-path binning (gv_binning.hip)
+  DevBuf<uint32_t> bin_total[2];
+  DevBuf<uint32_t> bin_done, bin_scratch;
+  int bin_parity = 0;
+  // A lane's partition pass does not depend on the sector kernel queued in front of it (the previous frame of that
+  // lane: other buffers), only the in-order queue says so.  When nothing else was put on the lane since that
+  // sector kernel -- no wait, no upload, no table kernel -- the partition pass is launched without the barrier
+  // bit (hipExtAnyOrderLaunch) and starts while the sector kernel's last workgroups still run.  lane_clean:
+  // the last packet on this lane is a sector kernel.  GV_ANYORDER=0 switches it off.
+  bool lane_clean = false;
+  int sh_counts_slot = -1;      // ev_fin slot of the lane's last sharded KEEP_COUNTS frame (its x3 reduces hits in place)
+};
+
+}  // namespace gv_internal
+
+using namespace gv_internal;
+
+struct __attribute__((visibility("hidden"))) gv_context {
+  // Frames in flight run on LANES (three; GV_LANES=2: two): frame f does partition, tile pass and sector stage back
+  // to back on the in-order stream of lane f % lanes, then its grid pass on the PUBLIC stream behind one event.
+  // No event sits between the stages on a lane (a barrier packet between two kernels costs ~6 us of queue time,
+  // back to back kernels of one queue follow each other with a gap of a few us that the other lanes fill), the
+  // grid passes are one in-order sequence by construction (the log-odds grid is one sequence of updates), and
+  // everything a frame produced is visible on the public stream right behind it.  Buffer sets 1..2*lanes rotate
+  // with the frames (set 0: serial frames and standalone calls); a set is handed to frame f + 2*lanes once the
+  // HOST has seen frame f finish -- back-pressure on the caller instead of a barrier on a lane.
+  // Measured on config 3: one in-order stream 12.0 k frames/s; one stream per STAGE with three events per frame
+  // (round 1) 14.4 k; two lanes with the grid pass on the lane behind a cross-lane wait 16.5 k; two lanes as above
+  // 18.6 k in round 2, 23.5 k at the end of round 3; three lanes 24.7 k (the in-kernel timeline of the two-lane
+  // form shows the lanes in step, all of them between kernels at the same moments: profiles/r03/native_timeline.txt).
+  // Three lanes + public + copy are five streams on the four hardware queues a process gets by default; with
+  // GPU_MAX_HW_QUEUES=8 the same five streams run slower (57 us per frame against 40).  Independent HANDLES side by
+  // side (three or four grids, round 2: 15.4 / 14.3 k, tools/multi_handle.py) are a different thing: every grid
+  // pays its own grid pass.
+  static constexpr int kLanesMax = 3;              // three lanes by default, GV_LANES=2: two
+  static constexpr int kStreams = 1 + kLanesMax;   // public + lanes
+  static constexpr int kSets = 1 + 2 * kLanesMax;  // set 0: the serial frame; two sets per lane
+  static constexpr int kRing = 8;   // event rings: one slot per frame, reused every 8 frames
+  int n_lanes = 3;
+  int upload_stream_retries = 0;    // gv_create: upload streams replaced because they shared a hardware queue
+  double upload_probe_us = 0.0;     // the last probe's wait
+  // The third lane runs on the UPLOAD stream (public + two lanes + uploads are the four hardware queues a process
+  // gets; a fifth stream shares one of them with whatever the runtime picks, and when that is the upload stream the
+  // streamed frame drops to 0.8 of the copy rate).  It is used only while the upload stream is quiet: no cloud
+  // upload for kQuietFrames frames.  With a cloud per frame the library runs on two lanes, as in round 2.
+  static constexpr uint32_t kQuietFrames = 8;
+  uint32_t quiet_frames = 0;        // frames enqueued since the last cloud upload
+  int lanes_now() const { return (n_lanes == 3 && quiet_frames >= kQuietFrames) ? 3 : 2; }
+  int device = 0;
+  // (the streams come before every buffer and event: members go in reverse order, the streams last)
+  Stream stream, stream_copy, stream2, stream3, stream4;
+  Stream stream_x;                  // the exchanges of the sharded frame (created by gv_comm_init)
+  hipStream_t streams[kStreams]{};  // = {stream (public), stream2 (lane 0), stream3 (lane 1), stream4 (lane 2, GV_LANES=3)}
+  Event ev_sec[kRing];              // lane: partition, tile pass, sector stage of frame (slot) done
+  Event ev_fin[kRing];              // public stream: grid pass of frame (slot) done => that frame and every earlier one are done
+  Event ev_join;                    // copy stream -> public stream (gv_frame_fence)
+  uint64_t lane_frames = 0;         // lane frames enqueued so far: lane = n % lanes, buffer set = 1 + n % (2 * lanes)
+  int last_fin_slot = -1;           // ev_fin slot of the most recently enqueued frame (-1: idle)
+  FrameSet fs[kSets];             // per-set buffers of the frames in flight
+  StreamBufs sb[kStreams];        // per-stream buffers
+  size_t ends_words = 0, bmN_words = 0, bmT_words = 0;
+  DevBuf<uint8_t> miss8;          // generic path only: byte miss grid of the literal march
+  int last_set = 0;
+  uint64_t frame_no = 0;
+  bool pipe_busy = false;         // lane frames enqueued since the streams were last drained
+  bool no_pipeline = false;       // GV_PIPELINE=0
+  int32_t env_sector_rev = -1;    // GV_SECTOR_REV (sweeps)
+#ifdef GV_DIAG
+  std::vector<Event> *trace = nullptr;        // timing events around every pipelined kernel (gv_debug_pipeline_trace)
+  DevBuf<unsigned long long> d_dbg;           // GV_SECTOR_DBG=1: phase stamps of the sector kernel
+  DevBuf<unsigned long long> d_bin_dbg[2];    // GV_BIN_DBG=1: phase stamps of the partition / tile kernels
+  int32_t env_ablate = 0;                     // GV_ABLATE
+  DevBuf<unsigned long long> d_tl;            // GV_TIMELINE=1: {begin, end} of the four kernels of the last kTlFrames frames
+  static constexpr uint64_t kTlFrames = 4096;
+  unsigned long long *tl_slot(int kernel) const
+  {
+    return d_tl ? d_tl.get() + ((frame_no % kTlFrames) * 4 + (uint64_t)kernel) * 2 : nullptr;
+  }
+#endif
+  GridParams g{};
+  gv_cam_params cam{};
+  CamK camk{};
+  double K[9]{}, Kinv[9]{};
+
+  bool has_cl = false, has_bc = false, has_bl = false;
+  gv_transform tf_cl{}, tf_bc{}, tf_bl{};
+  Mat34f m_cam{}, m_base{};
+  Xform64 x_bc{};
+  RayOrigin org{};
+
+  // grid state (resident across frames)
+  DevBuf<float> log_odds, occupancy;
+  DevBuf<int8_t> occ_i8;
+  // [EXTENSION] X3 ego motion (gv_grid_move): the current base frame in the frame the layers are registered in, and
+  // the scratch copy of the three layers the resample gathers into (allocated by the first applied move)
+  host::Se2 move_residue{0.0, 0.0, 0.0};
+  DevBuf<uint8_t> move_scratch;
+  // [EXTENSION] X4 height band of the lidar map update (gv_set_height_band): handle configuration, copied into the
+  // kernel arguments of every binning launch at enqueue
+  HeightBand band{-INFINITY, INFINITY, 0};
+  // per-frame count grids
+  int32_t *hits = nullptr;                  // = sb[stream of the last frame].hits
+  DevBuf<uint8_t> clip_end;                 // generic path only
+  DevBuf<uint32_t> ray_list;
+  DevBuf<uint32_t> ray_count;               // [0] = number of list entries
+  DevBuf<int32_t> scratch_i32;              // G ints (miss read-back), also max(N) ints for id read-back
+  int32_t nxw = 0, nyw = 0, nx_pad = 0, ny_pad = 0;
+  bool tile_path = false;                   // nx % 4 == 0 and the grid fits the packed (a,b) fields
+  bool force_simple = false;                // GV_RAY_IMPL=simple
+  int env_reorder = 1;                      // GV_SECTOR_REORDER=0: workgroups in natural (octant, sector) order
+  int env_helpers = -1;                     // GV_SECTOR_HELPERS: -1 automatic, 0 off, 1 on
+  bool env_anyorder = true;                 // GV_ANYORDER=0: no any-order partition launches (StreamBufs::lane_clean)
+  size_t stat_slots = 1;                    // ray statistics slots written by the last frame
+  int32_t env_log2s_oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // GV_LOG2S_OCT="a,b,..." per octant index (sweeps)
+  uint32_t env_march_limit = 64u * 512u;     // GV_MARCH_LIMIT
+  uint32_t env_flat_direct = 2048;           // GV_FLAT_DIRECT
+  int32_t env_flat_k = 8;                   // GV_FLAT_K: exact-cell : marched-cell cost ratio (0 = always march)
+  int32_t env_log2s = 0, env_cap = 0, env_log2m = 0;     // GV_LOG2S / GV_CAP / GV_LOG2M (sweeps)
+
+  // tile-path binning (gv_binning.hip): what every stream's scratch holds
+  int32_t tiles_x = 0, tiles_y = 0, n_tiles = 0;
+  size_t bin_keys_cap = 0, bin_tab_cap = 0;
+  size_t bin_slots = 0;
+
+  // resident clouds
+  CloudSet cloud[3];
+  int cloud_cur = 0;
+  bool cloud_wait = false;                  // an asynchronous upload may still be in flight
+  float *cx = nullptr, *cy = nullptr, *cz = nullptr;   // = cloud[cloud_cur]
+  size_t n = 0;
+  DevBuf<float> tx, ty, tz;                 // transformed copy (A1 read-back)
+  int32_t *cell_idx = nullptr;              // = sb[stream of the last frame]
+  int16_t *bbox_id = nullptr;
+  size_t idx_cap = 0;
+
+  // detections
+  DetSet det[3];
+  int det_cur = 0;
+  int32_t bt_tiles_x = 1, bt_tiles_y = 1;   // 16x16-pixel tiles of the image
+  VisionOut *d_vout = nullptr;              // = sb[0].vout
+  int32_t vout_cap = 0;                     // rectangles, vision outputs (all sets) and centre points
+  DevBuf<double> d_pts;
+  // kNN depth / PCA pose scratch
+  DevBuf<Cand2> knn_partial;
+  DevBuf<CellNode> d_nodes; DevBuf<uint8_t> d_keep; size_t pc_cap = 0;   // selected points in bucket order; 1 = survives the radius filter
+  DevBuf<uint32_t> d_ticket_of;      // per cloud point: its slot inside its bucket (selected points only)
+  DevBuf<long long> d_pca_acc; DevBuf<unsigned> d_pca_ext; size_t pca_cap = 0;   // per bbox: integer sums / extent keys of the PCA rectangle (zero between calls)
+  DevBuf<unsigned> d_pca_ticket;
+  DevBuf<uint32_t> d_cellcnt, d_cellpre, d_celloff; size_t head_cap = 0;   // cell buckets: counts, prefix, block offsets (+ ticket)
+  DevBuf<float4> d_planes; DevBuf<unsigned> d_plane_counts; size_t planes_cap = 0;
+  DevBuf<uint8_t> d_ground;   // last ground mask (device resident)
+  size_t ground_n = 0;
+  DevBuf<double> d_rscratch;   // tree-sum partials of the plane refinement
+  DevBuf<RansacState> d_rstate;
+  // result block of the synchronous kNN / RANSAC / PCA calls: pinned and device-mapped, written by the call's last
+  // kernel; [0] = the sequence number of the last finished call (CallDone, gv_kernels.hpp), payload from byte 64
+  PinnedBuf res_host;
+  DevBuf<unsigned> d_res_ticket;
+  unsigned res_seq = 0;
+
+  // the node's tick (gv_tick_enqueue / gv_tick_wait): what the pending tick put where in the result block
+  struct Tick {
+    bool pending = false;
+    uint32_t flags = 0;
+    int32_t n_all = 0, n_static = 0, n_dynamic = 0;
+    bool pca_ran = false, vision_ran = false, knn_ran = false;
+    size_t off_depth = 0, off_pose = 0, off_vout = 0;
+    std::vector<gv_bbox> st_boxes;   // the static boxes (host copy: convertPixelsTo3D after the wait)
+    // the handle's state at enqueue that the wait reads: uploads and gv_set_transforms may come in between
+    size_t n = 0;                    // points of the cloud the tick reads ("empty segmented cloud" is m == n)
+    int cloud = -1;                  // its cloud set: an upload into it waits for `done` on the device
+    gv_transform tf_bc{};            // camera->base of the poses and base points
+    Xform64 x_bc{};
+    Event done;                      // public stream: everything the tick enqueued has finished
+    Event fork, join;                // the kNN depth on a lane beside the pose branch
+  } tick;
+  bool env_tick_knn_lane = true;   // GV_TICK_KNN_LANE=0: the static boxes' kNN in line on the public stream
+
+  bool counts_dirty = false;   // generic path: hits/miss/clip_end hold a kept frame
+  bool have_hits = false, have_miss = false, have_cell_idx = false, have_bbox_id = false;
+
+  // multi-GPU (one large frame sharded by points)
+  ncclComm *comm = nullptr;       // (ncclComm_t)
+  int32_t rank = 0, world = 1;
+  DevBuf<uint32_t> sh_xchg;       // exchange scratch: `world` received slices / packed bands
+  Event ev_sh[kRing][5];          // per frame slot: binning, exchange 1, sectors + packing, exchange 2, grid pass done
+  Event sh_t[7];                  // stage timing of the sharded frame (gv_time_frame_sharded_stages)
+
+  Event ev[kNumStages + 1];
+  // stage timing (gv_time_frame_stages): start / end of the partition, tile-pass, sector and grid-pass kernels,
+  // taken from their own dispatch packets; kt_used: the kernel was launched in the frame just timed
+  Event kt[4][2];
+  bool kt_used[4]{};
+  std::string err;
+};
+
+constexpr size_t kMaxStatSlots = 8u << 12;   // one (rays, visits) slot per sector workgroup
+
+#define GV_HIP(call)                                                                          \
+  do {                                                                                        \
+    hipError_t e_ = (call);                                                                   \
+    if (e_ != hipSuccess) {                                                                   \
+      char buf_[256];                                                                         \
+      std::snprintf(buf_, sizeof(buf_), "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
+      h->err = buf_;                                                                          \
+      return GV_ERR_HIP;                                                                      \
+    }                                                                                         \
+  } while (0)
+
+#define GV_TRY try {
+#define GV_CATCH                               \
+  }                                            \
+  catch (const std::bad_alloc &) {             \
+    if (h) h->err = "host allocation failed";  \
+    return GV_ERR_HIP;                         \
+  }                                            \
+  catch (...) {                                \
+    if (h) h->err = "unexpected exception";    \
+    return GV_ERR_HIP;                         \
+  }
+
+#define GV_NCCL(call)                                                                          \
+  do {                                                                                         \
+    ncclResult_t r_ = (call);                                                                  \
+    if (r_ != ncclSuccess) {                                                                   \
+      char buf_[256];                                                                          \
+      std::snprintf(buf_, sizeof(buf_), "%s:%d %s -> %s", __FILE__, __LINE__, #call, ncclGetErrorString(r_)); \
+      h->err = buf_;                                                                           \
+      return GV_ERR_RCCL;                                                                      \
+    }                                                                                          \
+  } while (0)
+
+// internal functions that more than one translation unit calls (hidden: they add nothing to the library's exports)
+namespace gv_internal __attribute__((visibility("hidden"))) {
+// gv_api.hip
+int drain(gv_context *h);
+bool sector_path(const gv_context *h);
+int set_device_only(gv_context *h);
+int use_device(gv_context *h);
+int enqueue_plain_update(gv_context *h, int32_t n_rects);
+int ensure_tbuf(gv_context *h, size_t n);
+int copy_out(gv_context *h, void *dst, const void *src, size_t bytes);
+void convert_pixels_host(const double Kinv[9], const Xform64 &x_bc, const gv_bbox *bboxes, const float *depths, int32_t nb,
+                         double *base_points_xyz);
+// gv_api_frame.hip
+int ensure_point_buffers(gv_context *h, size_t n, size_t n_slice = 0);
+int ensure_det(gv_context *h, DetSet &d, int32_t n);
+int ensure_det_shared(gv_context *h, int32_t n);
+BBoxTest bbox_test_of(const gv_context *h, const DetSet &d);
+int upload_det(gv_context *h, DetSet &d, const gv_bbox *bboxes, int32_t nb, const gv_lshape_pose *poses,
+               int32_t n_poses, const float *orient, const float *conf, const float *dims, hipStream_t s, bool masks = true,
+               int32_t n_net = -1, int32_t nb_test = -1, bool fused = false);
+int upload_scratch_bboxes(gv_context *h, const gv_bbox *b, int32_t nb, bool masks = true);
+int32_t enqueue_rects(gv_context *h, const DetSet &D, Rect *rects, VisionOut *vout, hipStream_t s);
+int check_frame_flags(const gv_context *h, uint32_t fl);
+int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, size_t n, bool keep_cell, bool do_ray,
+                    bool do_bbox, bool write_hits, hipEvent_t ev_points, Rect *fold_rects = nullptr, bool timed = false,
+                    bool any_order = false);
+int enqueue_sectors(gv_context *h, int p, int first, int stride, hipStream_t s, hipEvent_t done = nullptr,
+                    bool *done_attached = nullptr, hipEvent_t t0 = nullptr);
+int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, bool counts, int32_t y0, int32_t y1,
+                      hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr, bool *launched = nullptr);
+int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k);
+// gv_api_shard.hip
+void comm_destroy(gv_context *h);
+}  // namespace gv_internal

@@ -1,4 +1,4 @@
-// gv_types.hpp -- POD parameter blocks shared by the host side (gv_api.hip)
+// gv_types.hpp -- POD parameter blocks shared by the host side (gv_api*.hip)
 // and the gfx950 kernels (gv_kernels.hip).  Passed by value as kernel arguments.
 #pragma once
 

@@ -2052,6 +2052,69 @@ def test_handle_lifecycle_with_frames_in_flight(gvamd):
     assert before - after < (64 << 20), f"device memory not returned: {before - after} bytes"
 
 
+def test_handle_lifecycle_every_buffer_family(gvamd):
+    """Twenty handles at BASELINE configs[2] size (1 M points, 4 M cells), each touching every lazily allocated
+    buffer family before close(): PointCloud2 raw bytes, per-point buffers and a detection set that grow once, kNN
+    scratch and result block, ground mask + RANSAC scratch, per-box cloud / PCA scratch, a tick of each branch (the
+    lidar extension on one), the scratch layers of an applied gv_grid_move, the exchange scratch of the emulated
+    sharded frame (world 3).  Device memory comes back (hipMemGetInfo before / after; the first handle, which makes
+    the runtime allocate its pools and load its code objects, is not counted).
+    Bound: the largest `before - after` of three runs on the library as it was before the owning resource types
+    (0, 0 and 0 bytes; the library with them: 0) + 16 MB, which stays below twenty leaked copies of the smallest
+    family here, the 1 MB ground mask."""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+
+    def free_bytes():
+        fr, tot = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        assert hip.hipMemGetInfo(ctypes.byref(fr), ctypes.byref(tot)) == 0
+        return fr.value
+
+    config = 3
+    n, n_first = 1_000_000, 700_000
+    x, y, z, _ = synth.cloud_lidar_like(config, n)
+    raw = np.zeros((n_first, 16), np.uint8)
+    for arr, o in zip((x, y, z), (0, 4, 8)):
+        raw[:, o:o + 4] = arr[:n_first].view(np.uint8).reshape(n_first, 4)
+    raw = raw.reshape(-1)
+    flags = gvamd.FRAME_BIN | gvamd.FRAME_RAYMARCH | gvamd.FRAME_BBOX_TEST
+    few, many = synth.detections(3, 20), synth.detections(3, 200)   # 200 > the 64 a handle starts with
+    poses = synth.lshape_poses(config, 12)
+    st, dy = gvamd.filter_bboxes(many)
+    assert len(st) and len(dy)
+    net = synth.network_outputs(len(dy))
+    move = [0.0, 0.0, 0.0, 1.0, 1.37, -0.62, 0.0]
+
+    def one_handle(it):
+        h, _ = make_handle(gvamd, config, perturbed=True)
+        h.upload_pointcloud2(raw, n_first, 16, 0, 4, 8)
+        h.set_detections(flags, bboxes=few, poses=poses)
+        h.enqueue_frame()
+        h.enqueue_frame()
+        h.upload_xyz(x, y, z)                                    # the cloud grows
+        h.set_detections(flags, bboxes=many, poses=poses)        # the detection count grows
+        h.enqueue_frame()
+        h.compute_depth_for_bboxes(st, 4)
+        m, mask, _ = h.segment_ground_plane()
+        assert 0 < m < n and len(mask) == n
+        h.compute_bbox_pose_ground_removed(many)
+        h.tick(many, k_near=4, lidar_bin=bool(it % 2), lidar_raymarch=bool(it % 2))   # PCA branch
+        h.tick(many, k_near=4, vision=True, net=net)                                  # orientation-network branch
+        assert h.grid_move(move)["applied"]
+        h.frame_sharded_emulated(3, flags, bboxes=many, poses=poses)
+        for _ in range(1 + it % 3):
+            h.enqueue_frame()
+        h.close()   # frames in flight
+
+    one_handle(0)
+    before = free_bytes()
+    for it in range(20):
+        one_handle(it)
+    after = free_bytes()
+    print(f"lifecycle, every family: before - after = {before - after} bytes")
+    assert before - after < (16 << 20), f"device memory not returned: {before - after} bytes"
+
+
 def test_streaming_growth_reallocates_under_load(gvamd):
     """Clouds and detection sets that GROW while frames are in flight: every per-point buffer, binning scratch,
     detection block and rectangle list is reallocated mid-stream (the growth paths drain the lanes first).

@@ -1,6 +1,6 @@
 """Multi-rank semantics of the sharded frame on CPU: world_size 2 and 3, gloo.
 
-This replays the algorithm the product runs (gv_api.hip: enqueue_frame_sharded, gv_shard.hip), step by step, with
+This replays the algorithm the product runs (gv_api_shard.hip: enqueue_frame_sharded, gv_shard.hip), step by step, with
 the oracle's pieces and torch.distributed in place of the HIP kernels and RCCL:
   1. every rank turns ITS slice of the points into ray-END BITMAPS (hit ends, clipped ends) and partial hit counts;
   2. exchange 1: the bitmaps are cut into `world` equal slices (the product's gv_shard_slice_words), slice q goes to
