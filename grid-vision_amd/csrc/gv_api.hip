@@ -86,9 +86,10 @@ int enqueue_plain_update(gv_context *h, int32_t n_rects)
     t.nx_pad = h->nx_pad;
     t.ny_pad = h->ny_pad;
     t.counts = false;
+    t.dense = h->grid_pass_dense();
     t.y_begin = 0;
     t.y_end = h->g.ny;
-    launch_finalize_tiles(t, h->stream);
+    if (launch_finalize_tiles(t, h->stream) && t.dense) h->layers_in_step = true;
     GV_HIP(hipGetLastError());
     return GV_OK;
   }
@@ -284,6 +285,7 @@ int gv_create(gv_handle *out, uint8_t grid_x, uint8_t grid_y, double resolution,
     if (const char *e = std::getenv("GV_SECTOR_REORDER")) h->env_reorder = std::atoi(e) != 0;
     if (const char *e = std::getenv("GV_SECTOR_HELPERS")) h->env_helpers = std::atoi(e) != 0;
     if (const char *e = std::getenv("GV_ANYORDER")) h->env_anyorder = std::atoi(e) != 0;
+    if (const char *e = std::getenv("GV_GRID_SKIP")) h->env_grid_skip = std::atoi(e) != 0;
     if (const char *e = std::getenv("GV_CAP")) h->env_cap = std::atoi(e);
     if (const char *e = std::getenv("GV_FLAT_K")) h->env_flat_k = std::max(0, std::atoi(e));
     if (const char *e = std::getenv("GV_FLAT_DIRECT")) h->env_flat_direct = (uint32_t)std::max(0, std::atoi(e));
@@ -409,6 +411,7 @@ int gv_reset(gv_handle h)
   GV_HIP(hipGetLastError());
   GV_HIP(hipStreamSynchronize(h->stream));
   h->move_residue = host::Se2{0.0, 0.0, 0.0};
+  h->layers_in_step = true;   // 0.0 / 0.5 / 50: what the grid pass derives from the prior
   return GV_OK;
   GV_CATCH
 }
@@ -710,6 +713,7 @@ int gv_set_log_odds(gv_handle h, const float *in)
   if (!h || !in) return GV_ERR_BAD_ARG;
   int rc = use_device(h);
   if (rc) return rc;
+  h->layers_in_step = false;   // one layer replaced: the next grid pass writes every row
   GV_HIP(hipMemcpyAsync(h->log_odds, in, (size_t)h->g.G * sizeof(float), hipMemcpyHostToDevice, h->stream));
   GV_HIP(hipStreamSynchronize(h->stream));
   h->move_residue = host::Se2{0.0, 0.0, 0.0};

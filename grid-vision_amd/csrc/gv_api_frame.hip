@@ -460,8 +460,10 @@ int enqueue_sectors(gv_context *h, int p, int first, int stride, hipStream_t s, 
 }
 
 int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, bool counts, int32_t y0, int32_t y1,
-                      hipStream_t s, hipEvent_t done, hipEvent_t t0, bool *launched)
+                      hipStream_t s, hipEvent_t done, hipEvent_t t0, bool *launched, bool sharded)
 {
+  // a sharded pass writes this rank's band whole and leaves the layers out of step (gv_context::layers_in_step)
+  const bool dense = sharded || h->grid_pass_dense();
   FinalizeTileArgs t{};
   t.g = h->g;
   t.log_odds = h->log_odds;
@@ -475,12 +477,15 @@ int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, 
   t.nx_pad = h->nx_pad;
   t.ny_pad = h->ny_pad;
   t.counts = counts;
+  t.dense = dense;
   t.y_begin = y0;
   t.y_end = y1;
 #ifdef GV_DIAG
   t.tl = h->tl_slot(3);
 #endif
   const bool ran = launch_finalize_tiles(t, s, done, t0);
+  if (sharded) h->layers_in_step = false;
+  else if (ran && dense && y0 <= 0 && y1 >= h->g.ny) h->layers_in_step = true;
   if (launched) *launched = ran;
   if (!ran && done) GV_HIP(hipEventRecord(done, s));
   GV_HIP(hipGetLastError());

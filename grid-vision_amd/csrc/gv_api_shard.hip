@@ -162,7 +162,7 @@ int enqueue_frame_sharded(gv_context *h, const Event *te)
   int32_t y0, y1;
   shard_band_rows(h->rank, h->world, h->g.ny, h->ny_pad, y0, y1);
   GV_HIP(hipStreamWaitEvent(h->stream, ev[3], 0));
-  if ((rc = enqueue_grid_pass(h, p, rects, n_rects, true, y0, y1, h->stream))) return rc;
+  if ((rc = enqueue_grid_pass(h, p, rects, n_rects, true, y0, y1, h->stream, nullptr, nullptr, nullptr, true))) return rc;
   if (te) GV_HIP(hipEventRecord(te[5], h->stream));
   GV_HIP(hipEventRecord(ev[4], h->stream));
   // --- X: packed bands to everyone (band r sits at data[G - e_r, G - b_r)); band totals of the hit counts
@@ -271,6 +271,7 @@ int gv_comm_init(gv_handle h, const uint8_t id[128], int32_t rank, int32_t world
   GV_NCCL(ncclCommInitRank(&h->comm, world, uid, rank));
   h->rank = rank;
   h->world = world;
+  h->layers_in_step = false;   // the bands change hands: the next grid pass writes every row it owns
   // the exchange stream of the sharded frame and the events that chain its steps (ordering only)
   if (!h->stream_x) GV_HIP(h->stream_x.create());
   for (auto &row : h->ev_sh)
@@ -305,6 +306,7 @@ int gv_comm_destroy(gv_handle h)
   comm_destroy(h);
   h->rank = 0;
   h->world = 1;
+  h->layers_in_step = false;
   return GV_OK;
 }
 
@@ -405,7 +407,7 @@ static int emulate_ranks(gv_context *h, DetSet &D, int32_t world, DevBuf<uint32_
     if ((rc2 = shard_or_free_band(L, 0, nullptr, s))) return rc2;
     int32_t y0, y1;
     shard_band_rows(q, world, h->g.ny, h->ny_pad, y0, y1);
-    if ((rc2 = enqueue_grid_pass(h, 0, rects, n_rects, true, y0, y1, s))) return rc2;
+    if ((rc2 = enqueue_grid_pass(h, 0, rects, n_rects, true, y0, y1, s, nullptr, nullptr, nullptr, true))) return rc2;
   }
   GV_HIP(hipStreamSynchronize(s));
   return GV_OK;

@@ -169,6 +169,18 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // grid state (resident across frames)
   DevBuf<float> log_odds, occupancy;
   DevBuf<int8_t> occ_i8;
+  // The tile grid pass leaves a tile row alone whose log-odds it did not change by a bit (cells at a clamp: most of
+  // a map in steady state).  That is right only while occupancy and occ_i8 hold what the grid pass derives from the
+  // current log-odds: layers_in_step.  False after gv_set_log_odds (one layer replaced), after a sharded frame (a
+  // rank writes its own band only, and bands can change) and after any change of communicator; true after gv_reset
+  // (0.0 / 0.5 / 50 is such a triple) and once a dense pass over all rows has been enqueued.  gv_grid_move moves the
+  // three layers together.  The flag is read when a grid pass is ENQUEUED: grid passes are one in-order sequence on
+  // the public stream, so the pass that reads `true` runs behind the dense pass or the fill that made it true, and
+  // gv_set_log_odds drains every stream before it copies.  A caller that writes through gv_device_layers' pointers
+  // puts the layers out of step without the handle knowing.
+  bool layers_in_step = false;
+  bool env_grid_skip = true;      // GV_GRID_SKIP=0: every grid pass dense (A/B runs, tests)
+  bool grid_pass_dense() const { return !env_grid_skip || !layers_in_step; }
   // [EXTENSION] X3 ego motion (gv_grid_move): the current base frame in the frame the layers are registered in, and
   // the scratch copy of the three layers the resample gathers into (allocated by the first applied move)
   host::Se2 move_residue{0.0, 0.0, 0.0};
@@ -337,7 +349,8 @@ int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, siz
 int enqueue_sectors(gv_context *h, int p, int first, int stride, hipStream_t s, hipEvent_t done = nullptr,
                     bool *done_attached = nullptr, hipEvent_t t0 = nullptr);
 int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, bool counts, int32_t y0, int32_t y1,
-                      hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr, bool *launched = nullptr);
+                      hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr, bool *launched = nullptr,
+                      bool sharded = false);
 int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k);
 // gv_api_shard.hip
 void comm_destroy(gv_context *h);

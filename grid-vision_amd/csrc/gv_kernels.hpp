@@ -208,6 +208,8 @@ struct FinalizeTileArgs {
   const uint32_t *freeN, *freeT;   // free-cell bitmaps of the ray stage (N | T)
   int32_t nx_pad, ny_pad;
   bool counts;            // apply the hit/miss rule
+  bool dense;             // write every row; false: a tile row whose log-odds did not change by a bit is not written,
+                          // right only while occupancy and the packed grid derive from the current log-odds
   int32_t y_begin, y_end; // rows to finalise ([0, ny) on one GPU)
   unsigned long long *tl; // diagnostic build: launch begin / end (GV_TIMELINE)
 };

@@ -1163,8 +1163,8 @@ __device__ __forceinline__ float cell_update_t(float l, int k, bool counts, bool
   return l;
 }
 
-// One 64x64 tile per workgroup.  Requires nx % 4 == 0.  Per cell: 4 B log-odds in, 4 + 4 + 1 B out;
-// hit and free-space flags come from the bitmaps (N: one word per 32 cells of a row; T: bits run
+// One 64x64 tile per workgroup.  Requires nx % 4 == 0.  Per cell: 4 B log-odds in, 4 + 4 + 1 B out (nothing out
+// for a tile row that did not change, unless a.dense); hit and free-space flags come from the bitmaps (N: one word per 32 cells of a row; T: bits run
 // along y, a thread's four cells are four consecutive words = one 16-byte load).  Nothing is cleared
 // here: the binning tile pass rewrites / zeroes every bitmap word of the set it is about to use.
 #ifndef GV_FIN_ROWS
@@ -1233,10 +1233,21 @@ __global__ void __launch_bounds__(256) k_finalize_tiles(FinalizeTileArgs a)
         }
       }
     }
+    const unsigned o0 = __float_as_uint(l4.x), o1 = __float_as_uint(l4.y), o2 = __float_as_uint(l4.z), o3 = __float_as_uint(l4.w);
     l4.x = cell_update_t(l4.x, k0, COUNTS, hb & 1u, fb & 1u);
     l4.y = cell_update_t(l4.y, k1, COUNTS, hb & 2u, fb & 2u);
     l4.z = cell_update_t(l4.z, k2, COUNTS, hb & 4u, fb & 4u);
     l4.w = cell_update_t(l4.w, k3, COUNTS, hb & 8u, fb & 8u);
+    // A tile row (16 lanes, 64 cells: 256 B of each float layer, 64 B of the packed one) whose log-odds all came
+    // back with the bits they had is left alone: with the layers in step (gv_context::layers_in_step) occupancy and
+    // the packed grid already hold what would be stored.  Bits, not ==: a NaN equals itself, -0.0 is not 0.0.
+    // A row with any changed cell is written whole, so every store stays a full 64-byte piece or more.
+    if (!a.dense) {
+      const bool changed = ((__float_as_uint(l4.x) ^ o0) | (__float_as_uint(l4.y) ^ o1) | (__float_as_uint(l4.z) ^ o2) |
+                            (__float_as_uint(l4.w) ^ o3)) != 0u;
+      const unsigned long long rows = __ballot(changed);   // lanes outside the grid are inactive here: no bit
+      if (((rows >> (tid & 48)) & 0xFFFFull) == 0ull) continue;
+    }
     float4 p4;
     p4.x = sigmoid_ref_t(l4.x); p4.y = sigmoid_ref_t(l4.y); p4.z = sigmoid_ref_t(l4.z); p4.w = sigmoid_ref_t(l4.w);
     *reinterpret_cast<float4 *>(a.log_odds + c) = l4;   // read again by the next frame

@@ -417,7 +417,9 @@ int gv_tick(gv_handle h, const gv_tick_desc *d, gv_tick_result *r);   /* = enque
 void *gv_stream(gv_handle h);
 /* Device pointers of the resident grid for consumers on the device (stream-ordered behind a frame on gv_stream):
  * the packed OccupancyGrid.data bytes (G int8, `OccupancyGrid.data` order) and the two float layers (G floats,
- * grid_map order).  Any of the three may be null.  Read-only for the caller. */
+ * grid_map order).  Any of the three may be null.  Read-only for the caller: the grid pass leaves cells alone whose
+ * log-odds it does not change, so writing through these pointers puts the three layers out of step with each other
+ * until gv_reset or gv_set_log_odds. */
 int gv_device_layers(gv_handle h, int8_t **occ_i8, float **log_odds, float **occupancy);
 /* Time `frames` back-to-back gv_frame_enqueue calls with HIP events on the
  * handle's stream; *ms_total is the elapsed device time. */
