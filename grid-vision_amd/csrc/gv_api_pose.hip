@@ -32,7 +32,7 @@ int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, 
   DetSet &d = h->det[2];
   if ((rc = upload_det(h, d, bboxes, nb, nullptr, 0, orient, conf, dims, h->stream, false))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
-  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->d_vout, d.poses, h->stream);
+  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->d_vout, d.poses, nullptr, h->stream);
   GV_HIP(hipGetLastError());
   std::vector<VisionOut> vo((size_t)nb);
   GV_HIP(hipMemcpyAsync(vo.data(), h->d_vout, (size_t)nb * sizeof(VisionOut), hipMemcpyDeviceToHost, h->stream));
@@ -43,6 +43,29 @@ int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, 
     poses_out[m++] = pose_of_vision_out(vo[i]);
   }
   *n_out = m;
+  return GV_OK;
+  GV_CATCH
+}
+
+// test hook (gv_test_hooks.h): gv_vision_post_process's upload and launch with the kernel's `sets` output switched on
+int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, const float *dims, const gv_bbox *bboxes,
+                        int32_t nb, float *sets, int32_t *winner)
+{
+  if (!h || nb < 0 || (nb && (!orient || !conf || !dims || !bboxes || !sets || !winner))) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (nb == 0) return GV_OK;
+  int rc = use_device(h);
+  if (rc) return rc;
+  DetSet &d = h->det[2];
+  if ((rc = upload_det(h, d, bboxes, nb, nullptr, 0, orient, conf, dims, h->stream, false))) return rc;
+  GV_HIP(hipEventRecord(d.ready, h->stream));
+  DevBuf<float> dsets;   // nb * 64 * (loc0, loc1, loc2, err), then nb winners
+  if ((rc = dsets.reserve(h, (size_t)nb * 257))) return rc;
+  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->d_vout, d.poses, dsets, h->stream);
+  GV_HIP(hipGetLastError());
+  GV_HIP(hipMemcpyAsync(sets, dsets, (size_t)nb * 256 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipMemcpyAsync(winner, dsets + (size_t)nb * 256, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipStreamSynchronize(h->stream));
   return GV_OK;
   GV_CATCH
 }
@@ -417,7 +440,7 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   T.pca_ran = T.vision_ran = false;
   if (net) {   // VisionOrientation::postProcessOutputs (:190-209)
     launch_vision(D.orient, D.conf, D.dims, D.bboxes + n_all + ns, nd, h->cam, reinterpret_cast<VisionOut *>(blk + T.off_vout),
-                  D.poses, s);
+                  D.poses, nullptr, s);
     launch_rects_from_poses(D.poses, nd, h->g, true, h->x_bc, rects, s);
     n_rects = nd;
     T.vision_ran = true;

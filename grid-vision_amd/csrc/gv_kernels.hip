@@ -492,7 +492,7 @@ __device__ void qr_solve_4x3(const float Ain[12], const float bin[4], float x[3]
 __global__ void __launch_bounds__(64) k_vision(const float *__restrict__ orient, const float *__restrict__ conf,
                                                const float *__restrict__ dims, const gv_bbox *__restrict__ bboxes,
                                                int32_t nb, gv_cam_params cam, VisionOut *__restrict__ out,
-                                               gv_lshape_pose *__restrict__ poses_cam)
+                                               gv_lshape_pose *__restrict__ poses_cam, float *__restrict__ sets)
 {
   const int bi = blockIdx.x;
   if (bi >= nb) return;
@@ -505,9 +505,12 @@ __global__ void __launch_bounds__(64) k_vision(const float *__restrict__ orient,
   const float interval = (float)(2.0f * 3.14159265358979323846 / 2);
   const float bin = (argmax ? interval : 0.0f) + interval / 2.0f;
   // computeAlpha :260-275
-  // The float trig of the device library differs from glibc's by ulps; each one is evaluated in fp64 and
-  // rounded once instead, which is the correctly rounded float result (what glibc returns except for its
-  // own rare last-bit misses), so alpha / theta_ray / R agree with the host and the 64 residuals with them.
+  // The device's contract: each of the six trig values is evaluated in fp64 and rounded once to fp32, everything
+  // else runs in the reference's fp32 operation order, and the lowest set index wins on equal residuals
+  // (tests/vision_ref.py restates it; tests/test_gpu_vision.py holds all 64 sets to it bit for bit).  That is
+  // NOT what the host's float libm returns: glibc 2.35's atan2f differs from the rounded fp64 value for about
+  // one argument in six, atanf for 7 %, tanf for 4 %, sinf and cosf for over 1 % (DESIGN, Tolerances), so alpha can
+  // sit one ulp from the oracle's, and next to a threshold that is another corner branch.
   float alpha = (float)atan2((double)os[argmax * 2 + 1], (double)os[argmax * 2 + 0]);
   alpha += bin;
   alpha -= (float)3.14159265358979323846;
@@ -588,6 +591,11 @@ __global__ void __launch_bounds__(64) k_vision(const float *__restrict__ orient,
     const int ow = __shfl_xor(who, off);
     if (ob < best || (ob == best && ow < who)) { best = ob; who = ow; }
   }
+  if (sets) {   // gv_test_vision_sets only: every lane's (loc, err), then the winner (64 = none) behind all nb * 64 sets
+    float *o = sets + ((size_t)bi * 64 + lane) * 4;
+    o[0] = loc[0]; o[1] = loc[1]; o[2] = loc[2]; o[3] = err;
+    if (lane == 0) reinterpret_cast<int32_t *>(sets + (size_t)nb * 256)[bi] = who;
+  }
   const int src = (who < 64) ? who : 0;
   const float l0 = __shfl(loc[0], src), l1 = __shfl(loc[1], src), l2 = __shfl(loc[2], src);
   if (lane == 0) {
@@ -611,10 +619,10 @@ __global__ void __launch_bounds__(64) k_vision(const float *__restrict__ orient,
 }
 
 void launch_vision(const float *orient, const float *conf, const float *dims, const gv_bbox *bboxes, int32_t nb,
-                   const gv_cam_params &cam, VisionOut *out, gv_lshape_pose *poses_cam, hipStream_t s)
+                   const gv_cam_params &cam, VisionOut *out, gv_lshape_pose *poses_cam, float *sets, hipStream_t s)
 {
   if (nb <= 0) return;
-  hipLaunchKernelGGL(k_vision, dim3(nb), dim3(64), 0, s, orient, conf, dims, bboxes, nb, cam, out, poses_cam);
+  hipLaunchKernelGGL(k_vision, dim3(nb), dim3(64), 0, s, orient, conf, dims, bboxes, nb, cam, out, poses_cam, sets);
 }
 
 // --------------------------------------------------------- ray march (X2) --

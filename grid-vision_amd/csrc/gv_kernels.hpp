@@ -68,9 +68,10 @@ void launch_rects_from_points(const double *pts_xyz, const gv_bbox *bboxes, int3
                               const GridParams &g, Rect *rects, hipStream_t s);
 
 // vision-orientation geometry, one wavefront per bbox; also emits camera-frame
-// gv_lshape_pose (position + dims only; the quaternion is filled by the host)
+// gv_lshape_pose (position + dims only; the quaternion is filled by the host).  sets: nullptr in the product; the
+// test hook gv_test_vision_sets passes nb * 64 * 4 floats (loc0, loc1, loc2, err of every lane) + nb int32 (winner)
 void launch_vision(const float *orient, const float *conf, const float *dims, const gv_bbox *bboxes,
-                   int32_t nb, const gv_cam_params &cam, VisionOut *out, gv_lshape_pose *poses_cam,
+                   int32_t nb, const gv_cam_params &cam, VisionOut *out, gv_lshape_pose *poses_cam, float *sets,
                    hipStream_t s);
 
 void launch_ray_compact(const int32_t *hits, const uint8_t *clip_end, const GridParams &g,

@@ -12,6 +12,12 @@ extern "C" {
  * [n*r/world, n*(r+1)/world) -- with the exchanges done by device copies; the result must equal gv_process_frame's
  * (tests/test_gpu_parity.py::test_sharded_frame_every_rank_emulated). */
 int gv_test_frame_sharded_emulated(gv_handle h, const gv_frame_desc *desc, int32_t world);
+/* gv_vision_post_process's kernel (k_vision, through the same launch_vision) with its one test-only output switched on:
+ * sets[(i * 64 + lane) * 4 ..] = loc0, loc1, loc2, err of constraint set `lane` = ((l*4+t)*2+r)*4+b of box i, and
+ * winner[i] = the set the arg-min chose, 64 when no residual is below FLT_MAX.  The product's call sites pass a null
+ * pointer there and store nothing (tests/test_gpu_vision.py). */
+int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, const float *dims, const gv_bbox *bboxes,
+                        int32_t nb, float *sets /* nb*64*4 */, int32_t *winner /* nb */);
 #ifdef __cplusplus
 }
 #endif

@@ -372,6 +372,17 @@ class GridVisionHIP:
                                                   _ptr(poses), C.byref(m)), "vision_post_process")
         return poses[:m.value].copy()
 
+    def vision_sets(self, orient, conf, dims, bboxes):
+        """test hook (csrc/gv_test_hooks.h): (nb, 64, 4) loc0, loc1, loc2, err of every constraint set of k_vision, and
+        the (nb,) winner, 64 = none"""
+        o, c, d = _f32(orient), _f32(conf), _f32(dims)
+        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
+        sets = np.zeros((len(b), 64, 4), np.float32)
+        winner = np.zeros(len(b), np.int32)
+        self._ck(self._lib.gv_test_vision_sets(self._h, _ptr(o), _ptr(c), _ptr(d), _ptr(b), C.c_int32(len(b)),
+                                               _ptr(sets), _ptr(winner)), "gv_test_vision_sets")
+        return sets, winner
+
     def transform_lshape_objects(self, poses):
         p = np.ascontiguousarray(poses, dtype=LSHAPE_DTYPE).copy()
         self._ck(self._lib.gv_transform_lshape_objects(self._h, _ptr(p), C.c_int32(len(p))), "transform_lshape")

@@ -273,9 +273,13 @@ def test_pointcloud2_ingest(gvamd):
 def test_vision_post_process_tolerance(gvamd):
     """A13/A14: 64-combination least squares per bbox, one wavefront each.  SURVEY 8(a) A14: location
     within 1e-4 (absolute + relative).  The device evaluates the float trig in fp64 rounded once and runs
-    the oracle's QR operation order, so normally every box agrees to the last bits.  A box may pick another
-    of the 64 constraint sets only if that was a proven near-tie: the oracle's own residual of the set the
-    device chose must be within 1e-6 (relative) of the oracle's minimum."""
+    the oracle's QR operation order; the oracle calls the host's float libm, which is not the rounded fp64
+    value (glibc 2.35: atan2f for 16 % of the arguments, atanf 7 %, tanf 4 %, sinf and cosf over 1 %).  Of the 16
+    boxes emitted here alpha differs by an ulp for one and theta_ray for one, and one location is 4.8e-7 away; the
+    other 15 agree to the last bit (tests/test_vision_host.py, DESIGN Tolerances).  The bit-for-bit check of this path
+    is tests/test_gpu_vision.py against tests/vision_ref.py.  A box may pick another of the 64 constraint sets
+    only if that was a proven near-tie: the oracle's own residual of the set the device chose must be within
+    1e-6 (relative) of the oracle's minimum."""
     h, tfs = make_handle(gvamd, 2)
     nb = 50
     bboxes = synth.detections(3, nb)
