@@ -358,6 +358,33 @@ int gv_compute_bbox_pose_ground_removed(gv_handle h, const gv_bbox *bboxes, int3
   return GV_OK;
 }
 
+// test hook (gv_test_hooks.h): the public call, then the selected points and their keep flags as it left them
+int gv_test_bbox_pose_nodes(gv_handle h, const gv_bbox *bboxes, int32_t nb, int32_t with_ground, gv_lshape_pose *poses_out,
+                            uint8_t *valid, int32_t *n_poses_or_fail, float *nodes, uint8_t *keep, int64_t *n_sel)
+{
+  if (!h || !n_sel || !nodes || !keep) return GV_ERR_BAD_ARG;
+  *n_sel = 0;
+  int rc = with_ground ? gv_compute_bbox_pose_ground_removed(h, bboxes, nb, poses_out, valid, n_poses_or_fail)
+                       : gv_compute_bbox_pose(h, bboxes, nb, poses_out, valid);
+  if (rc) return rc;
+  GV_TRY
+  if (nb == 0 || h->n == 0 || (with_ground && h->n < 3)) return GV_OK;   // nothing was launched
+  if ((rc = set_device_only(h))) return rc;
+  // the number of selected points sits behind the block offsets of the bucket table (enqueue_bbox_pose)
+  uint32_t m = 0;
+  GV_HIP(hipMemcpyAsync(&m, h->d_celloff + h->head_cap / 4096, sizeof(m), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipStreamSynchronize(h->stream));
+  if ((size_t)m > h->n) { h->err = "more selected points than points"; return GV_ERR_STATE; }
+  if (m) {
+    GV_HIP(hipMemcpyAsync(nodes, h->d_nodes, (size_t)m * sizeof(CellNode), hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipMemcpyAsync(keep, h->d_keep, (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipStreamSynchronize(h->stream));
+  }
+  *n_sel = (int64_t)m;
+  return GV_OK;
+  GV_CATCH
+}
+
 /* ------------------------------------------------------------ the node's tick -- */
 // GridVision::timerCallback from filterBBoxes on (grid_vision_node.cpp:153-244) as ONE batch of device work: the
 // static boxes' kNN depth (:168-184), the dynamic boxes' poses -- orientation-network geometry (:190-209) or ground

@@ -18,6 +18,15 @@ int gv_test_frame_sharded_emulated(gv_handle h, const gv_frame_desc *desc, int32
  * pointer there and store nothing (tests/test_gpu_vision.py). */
 int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, const float *dims, const gv_bbox *bboxes,
                         int32_t nb, float *sets /* nb*64*4 */, int32_t *winner /* nb */);
+/* gv_compute_bbox_pose (with_ground == 0) or gv_compute_bbox_pose_ground_removed (with_ground != 0), the product's own
+ * call unchanged, and then what that call left resident on the device: *n_sel = the number of selected points (the
+ * bucket scan's total), nodes[4 * t ..] = the 16 bytes of CellNode t (camera x, y, z as floats, the box id as an int32)
+ * in bucket order, keep[t] = 1 where point t survived the radius filter.  nodes and keep have room for the resident
+ * cloud's n points.  A call that launches nothing (no boxes, no points) reports *n_sel = 0.  No kernel of its own
+ * (tests/test_gpu_pose.py). */
+int gv_test_bbox_pose_nodes(gv_handle h, const gv_bbox *bboxes, int32_t nb, int32_t with_ground, gv_lshape_pose *poses_out,
+                            uint8_t *valid, int32_t *n_poses_or_fail, float *nodes /* n*4 */, uint8_t *keep /* n */,
+                            int64_t *n_sel);
 #ifdef __cplusplus
 }
 #endif

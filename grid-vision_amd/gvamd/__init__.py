@@ -15,6 +15,7 @@ from . import build as _build
 from .synth import BBOX_DTYPE, LSHAPE_DTYPE
 
 GV_OK = 0
+NODE_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("id", np.int32)])   # CellNode
 STATUS = {0: "GV_OK", 1: "GV_ERR_BAD_ARG", 2: "GV_ERR_HIP", 3: "GV_ERR_RCCL", 4: "GV_ERR_NO_DEVICE",
           5: "GV_ERR_STATE", 6: "GV_ERR_TF"}
 
@@ -382,6 +383,21 @@ class GridVisionHIP:
         self._ck(self._lib.gv_test_vision_sets(self._h, _ptr(o), _ptr(c), _ptr(d), _ptr(b), C.c_int32(len(b)),
                                                _ptr(sets), _ptr(winner)), "gv_test_vision_sets")
         return sets, winner
+
+    def bbox_pose_nodes(self, bboxes, ground_removed=False):
+        """test hook (csrc/gv_test_hooks.h): compute_bbox_pose (or compute_bbox_pose_ground_removed) and what it left on
+        the device: (poses, valid, nodes, keep) -- nodes: the selected points in bucket order as a structured array
+        (x, y, z float32 in the camera frame, id int32), keep: their radius-filter flags"""
+        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
+        poses = np.zeros(max(len(b), 1), dtype=LSHAPE_DTYPE)
+        valid = np.zeros(max(len(b), 1), np.uint8)
+        nodes = np.zeros(max(self.n, 1), dtype=NODE_DTYPE)
+        keep = np.zeros(max(self.n, 1), np.uint8)
+        npz, m = C.c_int32(0), C.c_int64(0)
+        self._ck(self._lib.gv_test_bbox_pose_nodes(self._h, _ptr(b), C.c_int32(len(b)), C.c_int32(1 if ground_removed else 0),
+                                                   _ptr(poses), _ptr(valid), C.byref(npz), _ptr(nodes), _ptr(keep),
+                                                   C.byref(m)), "gv_test_bbox_pose_nodes")
+        return poses[:len(b)], valid[:len(b)], nodes[:m.value].copy(), keep[:m.value].copy()
 
     def transform_lshape_objects(self, poses):
         p = np.ascontiguousarray(poses, dtype=LSHAPE_DTYPE).copy()
