@@ -1,5 +1,5 @@
 // gv_api.hip -- C ABI (include/gridvision_hip.h) over the gfx950 kernels: the handle's life, transforms, getters,
-// plain map updates, grid publishing, ego motion, and the host-only helpers.  The frame pipeline is
+// plain map updates, grid publishing, ego motion, the inflated costmap layer, and the host-only helpers.  The frame pipeline is
 // gv_api_frame.hip, the sharded frame gv_api_shard.hip, the kNN / RANSAC / PCA path and the tick gv_api_pose.hip.
 // One gv_context = one device + one resident grid + its HIP streams.  No exception
 // leaves these files; every entry point returns a gv_status.
@@ -412,6 +412,7 @@ int gv_reset(gv_handle h)
   GV_HIP(hipStreamSynchronize(h->stream));
   h->move_residue = host::Se2{0.0, 0.0, 0.0};
   h->layers_in_step = true;   // 0.0 / 0.5 / 50: what the grid pass derives from the prior
+  h->infl.have_cost = h->infl.have_dist2 = false;   // the costmap was a snapshot of the grid that is gone
   return GV_OK;
   GV_CATCH
 }
@@ -666,7 +667,8 @@ int gv_to_occupancy_grid_async(gv_handle h, int8_t *data)
 // download in six took 300 us instead of 85); the download ordered on the upload stream between two uploads 381 us
 // (steady, but every copy command costs ~25 us of engine turn-around); this kernel 262 us, within 0.3 % frame after
 // frame -- the copy engines stay with the uploads, PCIe carries both directions at once.
-static int publish_by_kernel(gv_context *h, int8_t *data, hipStream_t s, bool *done)
+// `src`: G bytes of a device layer in OccupancyGrid.data order (the packed grid, the costmap).
+static int publish_by_kernel(gv_context *h, const int8_t *src, int8_t *data, hipStream_t s, bool *done)
 {
   *done = false;
   hipPointerAttribute_t at{};
@@ -676,10 +678,21 @@ static int publish_by_kernel(gv_context *h, int8_t *data, hipStream_t s, bool *d
     return GV_OK;
   }
   const size_t G = (size_t)h->g.G, body = G & ~(size_t)15;
-  launch_publish_grid(h->occ_i8, static_cast<int8_t *>(at.devicePointer), body, 32, s);
+  launch_publish_grid(src, static_cast<int8_t *>(at.devicePointer), body, 32, s);
   GV_HIP(hipGetLastError());
-  if (G > body) GV_HIP(hipMemcpyAsync(data + body, h->occ_i8 + body, G - body, hipMemcpyDeviceToHost, s));
+  if (G > body) GV_HIP(hipMemcpyAsync(data + body, src + body, G - body, hipMemcpyDeviceToHost, s));
   *done = true;
+  return GV_OK;
+}
+
+// one layer of G bytes to the caller's memory on the public stream: by the kernel where that works, else by a copy command
+static int publish_layer_async(gv_context *h, const int8_t *src, int8_t *data)
+{
+  int rc = set_device_only(h);
+  if (rc) return rc;
+  bool done = false;
+  if ((rc = publish_by_kernel(h, src, data, h->stream, &done))) return rc;
+  if (!done) GV_HIP(hipMemcpyAsync(data, src, (size_t)h->g.G, hipMemcpyDeviceToHost, h->stream));
   return GV_OK;
 }
 
@@ -687,12 +700,7 @@ int gv_publish_grid_async(gv_handle h, int8_t *data)
 {
   if (!h || !data) return GV_ERR_BAD_ARG;
   GV_TRY
-  int rc = set_device_only(h);
-  if (rc) return rc;
-  bool done = false;
-  if ((rc = publish_by_kernel(h, data, h->stream, &done))) return rc;
-  if (!done) GV_HIP(hipMemcpyAsync(data, h->occ_i8, (size_t)h->g.G, hipMemcpyDeviceToHost, h->stream));
-  return GV_OK;
+  return publish_layer_async(h, h->occ_i8, data);
   GV_CATCH
 }
 
@@ -775,6 +783,114 @@ int gv_set_height_band(gv_handle h, const gv_height_band *band)
     return GV_ERR_BAD_ARG;
   h->band = HeightBand{band->z_ground, band->z_max, band->ground_clears};
   return GV_OK;
+}
+
+// [EXTENSION] X6: handle configuration, the table is built here on the host and reaches the device with the next
+// gv_inflate (gv_context::Inflation).  A rejected configuration leaves the one in force alone.
+int gv_inflation_cost_table(const gv_inflation *cfg, double resolution, uint8_t *table, int32_t cap, int32_t *n)
+{
+  gv_context *h = nullptr;
+  if (!cfg) return GV_ERR_BAD_ARG;
+  GV_TRY
+  host::InflationTable t;
+  if (!host::inflation_table(*cfg, resolution, t)) return GV_ERR_BAD_ARG;
+  if (n) *n = t.d2max + 1;
+  if (!table || cap < t.d2max + 1) return GV_ERR_BAD_ARG;
+  std::memcpy(table, t.cost.data(), t.cost.size());
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_set_inflation(gv_handle h, const gv_inflation *cfg)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!cfg) {
+    h->infl.set = false;
+    return GV_OK;
+  }
+  host::InflationTable t;
+  if (!host::inflation_table(*cfg, h->g.res, t)) return GV_ERR_BAD_ARG;
+  h->infl.tab = std::move(t);
+  h->infl.thr = cfg->lethal_threshold;
+  h->infl.flags = cfg->flags;
+  h->infl.dirty = true;
+  h->infl.set = true;
+  return GV_OK;
+  GV_CATCH
+}
+
+// Two kernels on the public stream, between the grid passes of the frames around them (set_device_only: the streams
+// are not drained).  No host wait once the buffers exist.
+int gv_inflate(gv_handle h)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  gv_context::Inflation &f = h->infl;
+  if (!f.set) { h->err = "gv_inflate: no inflation set (gv_set_inflation)"; return GV_ERR_STATE; }
+  if (h->world > 1) { h->err = "gv_inflate: ranks own row bands of the grid, the stencil crosses them"; return GV_ERR_STATE; }
+  int rc = set_device_only(h);
+  if (rc) return rc;
+  const size_t G = (size_t)h->g.G;
+  const bool keep = (f.flags & GV_INFLATE_KEEP_DIST2) != 0;
+  const int32_t row_words = inflate_row_words(h->g.nx);
+  if ((rc = f.bits.reserve_zeroed(h, (size_t)h->g.ny * (size_t)row_words, h->stream))) return rc;
+  if ((rc = f.cost.reserve(h, G + 16))) return rc;
+  if (keep && (rc = f.dist2.reserve(h, G))) return rc;
+  constexpr size_t kTableBytes = (size_t)(host::kInflateMaxRc + 1) * (host::kInflateMaxRc + 1);
+  if (f.dirty) {
+    const int k = f.slot ^ 1;
+    if ((rc = f.d_table[k].reserve(h, kTableBytes))) return rc;
+    if ((rc = f.stage[k].reserve(h, kTableBytes, hipHostMallocDefault))) return rc;
+    if (!f.staged[k]) GV_HIP(f.staged[k].create(hipEventDisableTiming));
+    if (f.staged_used[k]) GV_HIP(hipEventSynchronize(f.staged[k]));
+    std::memcpy(f.stage[k].get(), f.tab.cost.data(), f.tab.cost.size());
+    GV_HIP(hipMemcpyAsync(f.d_table[k], f.stage[k].get(), f.tab.cost.size(), hipMemcpyHostToDevice, h->stream));
+    GV_HIP(hipEventRecord(f.staged[k], h->stream));
+    f.staged_used[k] = true;
+    f.slot = k;
+    f.dirty = false;
+  }
+  InflateArgs a{};
+  a.nx = h->g.nx; a.ny = h->g.ny;
+  a.row_words = row_words;
+  a.thr = f.thr;
+  a.rc = f.tab.rc; a.d2max = f.tab.d2max;
+  a.i8 = h->occ_i8;
+  a.bits = f.bits;
+  a.table = f.d_table[f.slot];
+  a.cost = f.cost;
+  a.dist2 = keep ? f.dist2.get() : nullptr;
+  launch_lethal_bits(a, h->stream);
+  launch_inflate_tiles(a, h->stream);
+  GV_HIP(hipGetLastError());
+  f.have_cost = true;
+  f.have_dist2 = keep;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_get_costmap(gv_handle h, uint8_t *out)
+{
+  if (!h || !out) return GV_ERR_BAD_ARG;
+  if (!h->infl.have_cost) return GV_ERR_STATE;
+  return copy_out(h, out, h->infl.cost, (size_t)h->g.G);
+}
+
+int gv_get_obstacle_dist2(gv_handle h, uint16_t *out)
+{
+  if (!h || !out) return GV_ERR_BAD_ARG;
+  if (!h->infl.have_cost || !h->infl.have_dist2) return GV_ERR_STATE;
+  return copy_out(h, out, h->infl.dist2, (size_t)h->g.G * sizeof(uint16_t));
+}
+
+int gv_publish_costmap_async(gv_handle h, uint8_t *data)
+{
+  if (!h || !data) return GV_ERR_BAD_ARG;
+  if (!h->infl.have_cost) return GV_ERR_STATE;
+  GV_TRY
+  return publish_layer_async(h, reinterpret_cast<const int8_t *>(h->infl.cost.get()), reinterpret_cast<int8_t *>(data));
+  GV_CATCH
 }
 
 int gv_get_hits(gv_handle h, int32_t *out)

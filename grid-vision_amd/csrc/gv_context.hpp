@@ -188,6 +188,27 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // [EXTENSION] X4 height band of the lidar map update (gv_set_height_band): handle configuration, copied into the
   // kernel arguments of every binning launch at enqueue
   HeightBand band{-INFINITY, INFINITY, 0};
+  // [EXTENSION] X6 inflated costmap (gv_set_inflation / gv_inflate).  The configuration and its host-built table are
+  // handle state; the buffers are made by the first gv_inflate (dist2 by the first one that keeps it).  A changed
+  // table reaches the device with the next gv_inflate: pinned staging slot k -> device slot k by a copy command on
+  // the public stream, k alternating, so a pass already enqueued keeps reading the slot it was given (the copy into a
+  // slot runs behind every earlier pass on that stream; the staging slot is rewritten only once its last copy has left
+  // it -- two reconfigurations ago, the one host wait that can occur here).
+  struct Inflation {
+    bool set = false;
+    int32_t thr = 0, flags = 0;
+    host::InflationTable tab;
+    bool dirty = false;               // `tab` is newer than the device slot
+    int slot = 0;                     // device slot of the current table
+    DevBuf<uint8_t> d_table[2];
+    PinnedBuf stage[2];
+    Event staged[2];
+    bool staged_used[2] = {false, false};
+    DevBuf<unsigned long long> bits;  // lethal bitmap (guard words zero since allocation)
+    DevBuf<uint8_t> cost;
+    DevBuf<uint16_t> dist2;
+    bool have_cost = false, have_dist2 = false;   // a gv_inflate since gv_create / gv_reset; the last one kept dist2
+  } infl;
   // per-frame count grids
   int32_t *hits = nullptr;                  // = sb[stream of the last frame].hits
   DevBuf<uint8_t> clip_end;                 // generic path only

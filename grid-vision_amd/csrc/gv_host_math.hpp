@@ -304,5 +304,47 @@ inline GridMoveStep plan_grid_move(const Se2 &residue, const Se2 &motion, const 
   return st;
 }
 
+// [EXTENSION] X6 inflated costmap (gv_inflate): the cost table of include/gridvision_hip.h, built once per
+// configuration in fp64.  cost[q], q = 0 .. d2max, from dist = sqrt((double)q) * res; d2max is the largest q whose dist
+// is within the inflation radius, rc = isqrt(d2max) is how far the kernels search along a row and across rows.
+constexpr int32_t kInflateMaxRc = 63;
+constexpr int32_t kInflateFlags = GV_INFLATE_KEEP_DIST2 | GV_INFLATE_OCCUPANCY_SCALE;
+
+struct InflationTable {
+  int32_t d2max = -1, rc = 0;
+  std::vector<uint8_t> cost;   // d2max + 1 entries
+};
+
+// false (out untouched) for anything gv_set_inflation rejects
+inline bool inflation_table(const gv_inflation &c, double res, InflationTable &out)
+{
+  if (!std::isfinite(c.inscribed_radius) || !std::isfinite(c.inflation_radius) || !std::isfinite(c.cost_scaling_factor) ||
+      !std::isfinite(res) || !(res > 0.0))
+    return false;
+  if (c.inscribed_radius < 0.0 || c.inflation_radius < c.inscribed_radius || c.cost_scaling_factor < 0.0) return false;
+  if (c.lethal_threshold < 1 || c.lethal_threshold > 100 || (c.flags & ~kInflateFlags) != 0) return false;
+  const int32_t q_end = (kInflateMaxRc + 1) * (kInflateMaxRc + 1);   // the first q with isqrt(q) > 63
+  int32_t d2max = 0;
+  while (d2max + 1 <= q_end && std::sqrt((double)(d2max + 1)) * res <= c.inflation_radius) ++d2max;
+  if (d2max >= q_end) return false;
+  InflationTable t;
+  t.d2max = d2max;
+  while ((t.rc + 1) * (t.rc + 1) <= d2max) ++t.rc;
+  t.cost.resize((size_t)d2max + 1);
+  for (int32_t q = 0; q <= d2max; ++q) {
+    const double dist = std::sqrt((double)q) * res;
+    uint8_t v;
+    if (q == 0) v = 254;
+    else if (dist <= c.inscribed_radius) v = 253;
+    else if (dist > c.inflation_radius) v = 0;
+    else v = (uint8_t)(252.0 * std::exp(-c.cost_scaling_factor * (dist - c.inscribed_radius)));
+    if (c.flags & GV_INFLATE_OCCUPANCY_SCALE)
+      v = v == 0 ? 0 : v == 253 ? 99 : v == 254 ? 100 : (uint8_t)(1 + (97 * ((int)v - 1)) / 251);
+    t.cost[(size_t)q] = v;
+  }
+  out = std::move(t);
+  return true;
+}
+
 }  // namespace host
 }  // namespace gv

@@ -107,6 +107,24 @@ struct GridMoveArgs {
 };
 void launch_grid_move(const GridMoveArgs &a, hipStream_t s);             // resident -> scratch
 void launch_grid_move_copy_back(const GridMoveArgs &a, hipStream_t s);   // scratch -> resident
+// [EXTENSION] X6 inflated costmap (gv_inflate.hip).  Everything is in OccupancyGrid.data order: "row" y, "column" x of
+// byte y * nx + x of the packed layer (the cell order turned by 180 degrees; distances do not care).
+// The lethal bitmap: one bit per cell along x, rows_words() 64-bit words per row = one zero guard word, the row's
+// whole words (bits past nx zero), one zero guard word.  The guard words are zeroed once, when the buffer is made.
+struct InflateArgs {
+  int32_t nx, ny;
+  int32_t row_words;            // words per bitmap row, guards included
+  int32_t thr;                  // lethal iff (int8) v >= thr
+  int32_t rc, d2max;            // search radius in cells, largest squared distance with a cost
+  const int8_t *i8;             // the packed layer
+  unsigned long long *bits;     // ny * row_words words
+  const uint8_t *table;         // d2max + 1 costs (device)
+  uint8_t *cost;                // G
+  uint16_t *dist2;              // G or null
+};
+inline int32_t inflate_row_words(int32_t nx) { return (nx + 63) / 64 + 2; }
+void launch_lethal_bits(const InflateArgs &a, hipStream_t s);
+void launch_inflate_tiles(const InflateArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

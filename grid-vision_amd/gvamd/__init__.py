@@ -30,6 +30,9 @@ TICK_VISION_ORIENT = 1 << 0
 TICK_LIDAR_BIN = 1 << 1
 TICK_LIDAR_RAYMARCH = 1 << 2
 
+INFLATE_KEEP_DIST2 = 1 << 0
+INFLATE_OCCUPANCY_SCALE = 1 << 1
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -51,6 +54,8 @@ ABI_SYMBOLS = [
     "gv_to_occupancy_grid_async", "gv_frame_enqueue_sharded", "gv_time_frame_sharded_stages", "gv_shard_band_rows",
     "gv_shard_slice_words", "gv_device_layers", "gv_tick_enqueue", "gv_tick_wait", "gv_tick",
     "gv_comm_info", "gv_publish_grid_async", "gv_grid_move", "gv_set_height_band",
+    "gv_inflation_cost_table", "gv_set_inflation", "gv_inflate", "gv_get_costmap", "gv_get_obstacle_dist2",
+    "gv_publish_costmap_async",
 ]
 
 
@@ -78,6 +83,12 @@ class GridMoveInfo(C.Structure):
 class HeightBand(C.Structure):
     """gv_height_band: obstacle height band of the lidar map update"""
     _fields_ = [("z_ground", C.c_float), ("z_max", C.c_float), ("ground_clears", C.c_int32)]
+
+
+class Inflation(C.Structure):
+    """gv_inflation: radii in metres, the scaling factor in 1/m, lethal iff int8 >= lethal_threshold, INFLATE_* flags"""
+    _fields_ = [("inscribed_radius", C.c_double), ("inflation_radius", C.c_double), ("cost_scaling_factor", C.c_double),
+                ("lethal_threshold", C.c_int32), ("flags", C.c_int32)]
 
 
 class FrameDesc(C.Structure):
@@ -194,6 +205,16 @@ def shard_band_rows(rank, world, ny):
     if rc:
         raise GVError(rc, "gv_shard_band_rows")
     return y0.value, y1.value
+
+
+def inflation_cost_table(cfg, resolution):
+    """the uint8 cost table (d2max + 1 entries) an Inflation gives at `resolution` (host only; needs no GPU)"""
+    table = np.zeros(4096, np.uint8)
+    n = C.c_int32(0)
+    rc = load().gv_inflation_cost_table(C.byref(cfg), C.c_double(resolution), _ptr(table), C.c_int32(table.size), C.byref(n))
+    if rc:
+        raise GVError(rc, "gv_inflation_cost_table")
+    return table[:n.value].copy()
 
 
 def shard_slice_words(words, world):
@@ -474,6 +495,40 @@ class GridVisionHIP:
         clears = int(ground_clears) if not isinstance(ground_clears, bool) else (1 if ground_clears else 0)
         b = HeightBand(float(z_ground), float(z_max), clears)
         self._ck(self._lib.gv_set_height_band(self._h, C.byref(b)), "gv_set_height_band")
+
+    # ---- [EXTENSION] inflated costmap layer
+    def set_inflation(self, inscribed_radius, inflation_radius=None, cost_scaling_factor=10.0, lethal_threshold=65,
+                      keep_dist2=False, occupancy_scale=False):
+        """the configuration of the inflate() calls that follow; set_inflation(None) turns it off.  The first argument
+        may also be an Inflation."""
+        if inscribed_radius is None:
+            self._ck(self._lib.gv_set_inflation(self._h, None), "gv_set_inflation")
+            return
+        cfg = inscribed_radius
+        if not isinstance(cfg, Inflation):
+            flags = (INFLATE_KEEP_DIST2 if keep_dist2 else 0) | (INFLATE_OCCUPANCY_SCALE if occupancy_scale else 0)
+            cfg = Inflation(float(inscribed_radius), float(inflation_radius), float(cost_scaling_factor),
+                            int(lethal_threshold), flags)
+        self._ck(self._lib.gv_set_inflation(self._h, C.byref(cfg)), "gv_set_inflation")
+
+    def inflate(self):
+        """obstacle distance and cost of the grid as it stands, asynchronous on stream()"""
+        self._ck(self._lib.gv_inflate(self._h), "gv_inflate")
+
+    def costmap(self):
+        out = np.empty(self.G, np.uint8)
+        self._ck(self._lib.gv_get_costmap(self._h, _ptr(out)), "gv_get_costmap")
+        return out
+
+    def obstacle_dist2(self):
+        out = np.empty(self.G, np.uint16)
+        self._ck(self._lib.gv_get_obstacle_dist2(self._h, _ptr(out)), "gv_get_obstacle_dist2")
+        return out
+
+    def publish_costmap_async(self, pinned_u8):
+        """the costmap to PINNED host memory (G bytes, int8 or uint8 view), like publish_grid_async"""
+        assert pinned_u8.dtype in (np.int8, np.uint8) and pinned_u8.size == self.G
+        self._ck(self._lib.gv_publish_costmap_async(self._h, _ptr(pinned_u8)), "gv_publish_costmap_async")
 
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):

@@ -211,6 +211,17 @@ public:
     gv::check(gv_set_height_band(ctx_.handle(), &b), ctx_.handle(), "gv_set_height_band");
   }
   void clearHeightBand() { gv::check(gv_set_height_band(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_height_band"); }
+  // [EXTENSION] X6 inflated costmap layer (nav2's InflationLayer with an exact distance transform): configure once,
+  // inflate() after a map update (asynchronous on the context's stream), getCostmap() in OccupancyGrid.data order.
+  void setInflation(const gv_inflation &cfg) { gv::check(gv_set_inflation(ctx_.handle(), &cfg), ctx_.handle(), "gv_set_inflation"); }
+  void clearInflation() { gv::check(gv_set_inflation(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_inflation"); }
+  void inflate() { gv::check(gv_inflate(ctx_.handle()), ctx_.handle(), "gv_inflate"); }
+  std::vector<uint8_t> getCostmap() const
+  {
+    std::vector<uint8_t> data(cells_);
+    gv::check(gv_get_costmap(ctx_.handle(), data.data()), ctx_.handle(), "gv_get_costmap");
+    return data;
+  }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {

@@ -303,6 +303,68 @@ typedef struct {
 /* NULL turns the band off (the state after gv_create). */
 int gv_set_height_band(gv_handle h, const gv_height_band *band);
 
+/* --------------------------------------- [EXTENSION] inflated costmap layer -- */
+/* X6.  What a planner reads is not the grid but the costmap made from it: every cell's distance to the nearest
+ * obstacle and the inflation cost derived from that distance (nav2's InflationLayer).  gv_inflate computes both on
+ * the device from the packed int8 layer.  The reference has no such step; this text is its definition.
+ *
+ * Lethal cells.  A cell is lethal iff its packed int8 value v (what gv_to_occupancy_grid returns) satisfies
+ *   v >= lethal_threshold, compared signed: the -1 of a NaN occupancy is never lethal.  There is no "unknown"
+ *   class; the never-observed prior, 50, is lethal or not by the threshold alone.
+ * Distance.  d2(c) is the smallest dx^2 + dy^2, in whole cells and as an exact integer, from cell c to a lethal cell
+ *   of the same map: the exact Euclidean distance transform, not nav2's wavefront approximation.  Cells off the map
+ *   are not obstacles, nothing wraps from the end of one row into the next, and the search is bounded by d2max
+ *   (below): a cell with no lethal cell within d2max has no distance and reads 65535 in the uint16 layer.
+ * Cost table.  cost[q] for q = 0 .. d2max is built once on the host in fp64 with
+ *   dist = sqrt((double)q) * resolution (one correctly rounded sqrt, one multiply):
+ *     q == 0                     254 (lethal)
+ *     dist <= inscribed_radius   253
+ *     dist >  inflation_radius   0
+ *     otherwise                  (uint8_t)(252.0 * exp(-cost_scaling_factor * (dist - inscribed_radius))), truncated
+ *   (nav2_costmap_2d::InflationLayer::computeCost).  d2max is the largest q with
+ *   sqrt((double)q) * resolution <= inflation_radius, and Rc = isqrt(d2max) <= 63 is required (d2 then fits 16 bits
+ *   and a row's search window three 64-bit words).  A cell without a distance costs 0.
+ *   With GV_INFLATE_OCCUPANCY_SCALE every table entry c goes through the translation Costmap2DPublisher applies
+ *   before it publishes a costmap as an OccupancyGrid: 0 -> 0, 253 -> 99, 254 -> 100, otherwise
+ *   1 + (97 * (c - 1)) / 251 in integer arithmetic.  The same kernel runs with that table.
+ * Output layers.  cost[G] uint8 and, with GV_INFLATE_KEEP_DIST2, dist2[G] uint16, both in OccupancyGrid.data order
+ *   (the order of gv_to_occupancy_grid), so the costmap publishes beside the grid with the same gv_grid_info.
+ *
+ * gv_set_inflation is handle configuration like the height band: no device work, kept through gv_reset,
+ * gv_set_log_odds and gv_grid_move, applied to the gv_inflate calls after it (one already enqueued keeps the table it
+ * was enqueued with); NULL turns it off (the state after gv_create).  GV_ERR_BAD_ARG, configuration unchanged, for a
+ * null handle, a NaN or infinite field, a negative radius or factor, inflation_radius < inscribed_radius, a threshold
+ * outside 1..100, unknown flag bits, or Rc > 63.
+ * gv_inflate enqueues the pass on gv_stream(h) without a host wait (the allocations of the first call aside): it reads
+ * the packed layer as the grid pass of the last enqueued frame or tick left it and is ordered ahead of the next one,
+ * like gv_publish_grid_async and gv_grid_move; allowed between gv_tick_enqueue and gv_tick_wait, where it inflates the
+ * tick's grid.  GV_ERR_STATE when no inflation is set and with a communicator of more than one rank (ranks own row
+ * bands, the stencil crosses them).  The costmap is a snapshot of the grid at the call: a later frame, move or
+ * gv_set_log_odds does not change it, gv_reset invalidates it.
+ * gv_get_costmap (G bytes) and gv_get_obstacle_dist2 (G values) are synchronous read-backs like gv_get_log_odds;
+ * GV_ERR_STATE before the first gv_inflate since gv_create or gv_reset, gv_get_obstacle_dist2 also when the last
+ * gv_inflate ran without GV_INFLATE_KEEP_DIST2.  gv_publish_costmap_async follows gv_publish_grid_async's rules.
+ * gv_inflation_cost_table is host only and takes no handle: the table a configuration gives at a resolution
+ * (positive, finite), *n = d2max + 1 entries; GV_ERR_BAD_ARG for an invalid configuration, a null table or cap < *n
+ * (*n is set whenever the configuration is valid). */
+enum {
+  GV_INFLATE_KEEP_DIST2      = 1 << 0,   /* keep the uint16 squared-distance layer         */
+  GV_INFLATE_OCCUPANCY_SCALE = 1 << 1    /* costs translated to the 0..100 OccupancyGrid scale */
+};
+typedef struct {
+  double inscribed_radius;      /* m, finite, >= 0                                   */
+  double inflation_radius;      /* m, finite, >= inscribed_radius, Rc <= 63          */
+  double cost_scaling_factor;   /* 1/m, finite, >= 0                                 */
+  int32_t lethal_threshold;     /* 1..100                                            */
+  int32_t flags;                /* GV_INFLATE_KEEP_DIST2 | GV_INFLATE_OCCUPANCY_SCALE */
+} gv_inflation;
+int gv_inflation_cost_table(const gv_inflation *cfg, double resolution, uint8_t *table, int32_t cap, int32_t *n);
+int gv_set_inflation(gv_handle h, const gv_inflation *cfg);
+int gv_inflate(gv_handle h);
+int gv_get_costmap(gv_handle h, uint8_t *out);
+int gv_get_obstacle_dist2(gv_handle h, uint16_t *out);
+int gv_publish_costmap_async(gv_handle h, uint8_t *data);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
@@ -402,7 +464,8 @@ typedef struct {
  * GV_ERR_STATE, and so do, between the two, the synchronous calls that would reuse the tick's result block or its
  * detection set (gv_compute_depth_for_bboxes, gv_compute_bbox_pose*, gv_segment_ground_plane, gv_extract_cloud_per_bbox,
  * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map*,
- * gv_grid_move, gv_set_transforms and gv_set_height_band may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
+ * gv_grid_move, gv_set_transforms, gv_set_height_band, gv_set_inflation, gv_inflate and the costmap getters may be
+ * called; their device work is ordered behind the tick on gv_stream(h), and an upload never
  * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
  * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform or height
  * band set in between applies from the next tick on.  (tests/test_gpu_tick.py) */
