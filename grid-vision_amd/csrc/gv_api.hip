@@ -169,19 +169,7 @@ int gv_create(gv_handle *out, uint8_t grid_x, uint8_t grid_y, double resolution,
   h->device = device_id;
   // grid_map::GridMap::setGeometry + setPosition  (src/occupancy_grid.cpp:10-11)
   GridParams &g = h->g;
-  g.res = resolution;
-  g.inv_res = 1.0 / resolution;
-  const double sx = std::round((double)grid_x / resolution), sy = std::round((double)grid_y / resolution);
-  if (!(sx >= 1.0 && sy >= 1.0) || sx * sy > (double)(1 << 30)) { delete h; return GV_ERR_BAD_ARG; }
-  g.nx = (int32_t)sx;
-  g.ny = (int32_t)sy;
-  g.G = g.nx * g.ny;
-  g.len_x = (double)g.nx * resolution;
-  g.len_y = (double)g.ny * resolution;
-  g.pos_x = (double)(grid_x / 3);   // uint8_t / int: integer division (:11)
-  g.pos_y = 0.0;
-  g.off_x = 0.5 * g.len_x;
-  g.off_y = 0.5 * g.len_y;
+  if (!host::grid_params(grid_x, grid_y, resolution, g)) { delete h; return GV_ERR_BAD_ARG; }
   h->cam = *cam;
   host::intrinsics((double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, h->K, h->Kinv);
   for (int i = 0; i < 9; ++i) h->camk.k[i] = h->K[i];
@@ -890,6 +878,117 @@ int gv_publish_costmap_async(gv_handle h, uint8_t *data)
   if (!h->infl.have_cost) return GV_ERR_STATE;
   GV_TRY
   return publish_layer_async(h, reinterpret_cast<const int8_t *>(h->infl.cost.get()), reinterpret_cast<int8_t *>(data));
+  GV_CATCH
+}
+
+// [EXTENSION] X7: handle configuration only; every scoring call copies h->traj.fp into its kernel arguments.
+int gv_set_footprint(gv_handle h, const gv_footprint *fp)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  if (!fp) {
+    h->traj.set = false;
+    return GV_OK;
+  }
+  if (!host::footprint_valid(*fp)) return GV_ERR_BAD_ARG;
+  h->traj.fp = *fp;
+  for (int32_t i = fp->n_vertices; i < host::kFootprintMaxVertices; ++i) h->traj.fp.vx[i] = h->traj.fp.vy[i] = 0.0;
+  h->traj.set = true;
+  return GV_OK;
+}
+
+// the device's view of `p` when it is pinned host memory aligned to `align` bytes, else null (the copy command then)
+static void *pinned_device_view(void *p, size_t align)
+{
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer ||
+      (reinterpret_cast<uintptr_t>(at.devicePointer) & (align - 1)) != 0) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return at.devicePointer;
+}
+
+// A copy of the poses (host poses only), one kernel, and a copy per result the kernel cannot write in place, all on
+// the public stream: between the grid passes of the frames around them, behind the last gv_inflate.
+int gv_score_trajectories_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags,
+                                gv_traj_score *scores, uint8_t *pose_cost)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  const bool keep = (flags & GV_TRAJ_KEEP_POSE_COST) != 0;
+  if (!poses || !scores || P < 1 || P > 4096 || K < 0 || K > (1 << 20) || (flags & ~host::kTrajFlags) != 0 ||
+      (keep && !pose_cost))
+    return GV_ERR_BAD_ARG;
+  gv_context::TrajScore &t = h->traj;
+  if (!t.set) { h->err = "gv_score_trajectories: no footprint set (gv_set_footprint)"; return GV_ERR_STATE; }
+  if (!h->infl.have_cost) { h->err = "gv_score_trajectories: no costmap (gv_inflate)"; return GV_ERR_STATE; }
+  if (h->world > 1) { h->err = "gv_score_trajectories: ranks own row bands of the grid, there is no whole costmap"; return GV_ERR_STATE; }
+  if (K == 0) return GV_OK;
+  int rc = set_device_only(h);
+  if (rc) return rc;
+  const size_t n_poses = (size_t)K * (size_t)P;
+  TrajArgs a{};
+  a.g = h->g;
+  a.fp = t.fp;
+  a.K = K; a.P = P;
+  a.cost = h->infl.cost;
+  if (flags & GV_TRAJ_DEVICE_POSES) {
+    a.poses = poses;
+  } else {
+    if ((rc = t.d_poses.reserve(h, n_poses * 3))) return rc;
+    GV_HIP(hipMemcpyAsync(t.d_poses, poses, n_poses * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    a.poses = t.d_poses;
+  }
+  a.scores = static_cast<gv_traj_score *>(pinned_device_view(scores, 16));
+  const bool copy_scores = a.scores == nullptr;
+  if (copy_scores) {
+    if ((rc = t.d_scores.reserve(h, (size_t)K))) return rc;
+    a.scores = t.d_scores;
+  }
+  bool copy_pose_cost = false;
+  if (keep) {
+    a.pose_cost = static_cast<uint8_t *>(pinned_device_view(pose_cost, 1));
+    copy_pose_cost = a.pose_cost == nullptr;
+    if (copy_pose_cost) {
+      if ((rc = t.d_pose_cost.reserve(h, n_poses))) return rc;
+      a.pose_cost = t.d_pose_cost;
+    }
+  }
+  launch_score_trajectories(a, h->stream);
+  GV_HIP(hipGetLastError());
+  if (copy_scores) GV_HIP(hipMemcpyAsync(scores, a.scores, (size_t)K * sizeof(gv_traj_score), hipMemcpyDeviceToHost, h->stream));
+  if (copy_pose_cost) GV_HIP(hipMemcpyAsync(pose_cost, a.pose_cost, n_poses, hipMemcpyDeviceToHost, h->stream));
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_score_trajectories(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_traj_score *scores,
+                          uint8_t *pose_cost)
+{
+  const int rc = gv_score_trajectories_async(h, poses, K, P, flags, scores, pose_cost);
+  if (rc || K == 0) return rc;
+  GV_HIP(hipStreamSynchronize(h->stream));
+  return GV_OK;
+}
+
+// host only: the twin of the kernel's geometry (host::footprint_cells), on the geometry gv_create gives
+int gv_footprint_cells(uint8_t grid_x, uint8_t grid_y, double resolution, const gv_footprint *fp, float x, float y, float yaw,
+                       int32_t *cells, int32_t cap, int32_t *n)
+{
+  gv_context *h = nullptr;
+  if (!fp || !n) return GV_ERR_BAD_ARG;
+  GV_TRY
+  GridParams g{};
+  if (!host::footprint_valid(*fp) || !host::grid_params(grid_x, grid_y, resolution, g)) return GV_ERR_BAD_ARG;
+  std::vector<int32_t> out;
+  if (!host::footprint_cells(g, *fp, x, y, yaw, out)) {
+    *n = -1;
+    return GV_OK;
+  }
+  *n = (int32_t)out.size();
+  if (!cells || cap < *n) return GV_ERR_BAD_ARG;
+  std::memcpy(cells, out.data(), out.size() * sizeof(int32_t));
+  return GV_OK;
   GV_CATCH
 }
 

@@ -209,6 +209,18 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<uint16_t> dist2;
     bool have_cost = false, have_dist2 = false;   // a gv_inflate since gv_create / gv_reset; the last one kept dist2
   } infl;
+  // [EXTENSION] X7 trajectory scoring (gv_set_footprint / gv_score_trajectories*).  The footprint is handle
+  // configuration, copied into the kernel arguments of every call at enqueue.  The buffers are made by the first call
+  // that needs them and grow with K * P: the device copy of host poses, and the landing places of results whose
+  // destination the kernel cannot write itself (pageable memory).  All three are used on the public stream only, so a
+  // call's copies and kernel run behind those of the call before it.
+  struct TrajScore {
+    bool set = false;
+    gv_footprint fp{};
+    DevBuf<float> d_poses;
+    DevBuf<gv_traj_score> d_scores;
+    DevBuf<uint8_t> d_pose_cost;
+  } traj;
   // per-frame count grids
   int32_t *hits = nullptr;                  // = sb[stream of the last frame].hits
   DevBuf<uint8_t> clip_end;                 // generic path only

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "gv_line.hpp"
 #include "gv_types.hpp"
 
 namespace gv {
@@ -224,6 +225,72 @@ inline bool get_index(const GridParams &g, double x, double y, int &ix, int &iy)
   if (jx < 0 || jy < 0 || jx >= g.nx || jy >= g.ny) return false;
   ix = jx;
   iy = jy;
+  return true;
+}
+
+// grid_map::GridMap::setGeometry + setPosition as the constructor calls them (src/occupancy_grid.cpp:10-11): the
+// geometry gv_create gives a handle.  false for what gv_create rejects.
+inline bool grid_params(uint8_t grid_x, uint8_t grid_y, double resolution, GridParams &g)
+{
+  if (grid_x == 0 || grid_y == 0 || !(resolution > 0.0)) return false;
+  g.res = resolution;
+  g.inv_res = 1.0 / resolution;
+  const double sx = std::round((double)grid_x / resolution), sy = std::round((double)grid_y / resolution);
+  if (!(sx >= 1.0 && sy >= 1.0) || sx * sy > (double)(1 << 30)) return false;
+  g.nx = (int32_t)sx;
+  g.ny = (int32_t)sy;
+  g.G = g.nx * g.ny;
+  g.len_x = (double)g.nx * resolution;
+  g.len_y = (double)g.ny * resolution;
+  g.pos_x = (double)(grid_x / 3);   // uint8_t / int: integer division (:11)
+  g.pos_y = 0.0;
+  g.off_x = 0.5 * g.len_x;
+  g.off_y = 0.5 * g.len_y;
+  return true;
+}
+
+// ---- [EXTENSION] X7 trajectory scoring (gv_score_trajectories): the footprint's rules and the host twin of the
+// kernel's geometry (include/gridvision_hip.h has the definition) ----
+constexpr int32_t kFootprintMaxVertices = 16;
+constexpr uint32_t kTrajFlags = GV_TRAJ_KEEP_POSE_COST | GV_TRAJ_DEVICE_POSES;
+
+// what gv_set_footprint accepts
+inline bool footprint_valid(const gv_footprint &f)
+{
+  if (f.n_vertices != 0 && (f.n_vertices < 3 || f.n_vertices > kFootprintMaxVertices)) return false;
+  for (int32_t i = 0; i < f.n_vertices; ++i)
+    if (!std::isfinite(f.vx[i]) || !std::isfinite(f.vy[i])) return false;
+  return f.collision_cost >= 1 && f.collision_cost <= 255 && f.off_map_cost >= 0 && f.off_map_cost <= 255 && f.flags == 0;
+}
+
+// The cells one pose tests, as iy * nx + ix: the centre, then every edge's line (gv_line.hpp, the closed form the
+// kernel evaluates a lane per cell) from vertex i to vertex (i + 1) % n.  false: the pose is off the map (out untouched).
+inline bool footprint_cells(const GridParams &g, const gv_footprint &f, float x, float y, float yaw, std::vector<int32_t> &out)
+{
+  int cx[kFootprintMaxVertices + 1], cy[kFootprintMaxVertices + 1];
+  const double px = (double)x, py = (double)y;
+  if (!get_index(g, px, py, cx[0], cy[0])) return false;
+  const int32_t n = f.n_vertices;
+  if (n > 0) {
+    const double c = std::cos((double)yaw), s = std::sin((double)yaw);
+    for (int32_t i = 0; i < n; ++i) {
+      const double wx = px + (c * f.vx[i] - s * f.vy[i]);
+      const double wy = py + (s * f.vx[i] + c * f.vy[i]);
+      if (!get_index(g, wx, wy, cx[i + 1], cy[i + 1])) return false;
+    }
+  }
+  std::vector<int32_t> cells;
+  cells.push_back(cy[0] * g.nx + cx[0]);
+  for (int32_t e = 0; e < n; ++e) {
+    const int32_t a = 1 + e, b = 1 + (e + 1 == n ? 0 : e + 1);
+    const int32_t m = line_cells(cx[a], cy[a], cx[b], cy[b]);
+    for (int32_t i = 0; i < m; ++i) {
+      int32_t lx, ly;
+      line_cell(cx[a], cy[a], cx[b], cy[b], (uint32_t)i, lx, ly);
+      cells.push_back(ly * g.nx + lx);
+    }
+  }
+  out = std::move(cells);
   return true;
 }
 

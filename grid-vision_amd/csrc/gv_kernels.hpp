@@ -125,6 +125,18 @@ struct InflateArgs {
 inline int32_t inflate_row_words(int32_t nx) { return (nx + 63) / 64 + 2; }
 void launch_lethal_bits(const InflateArgs &a, hipStream_t s);
 void launch_inflate_tiles(const InflateArgs &a, hipStream_t s);
+// [EXTENSION] X7 trajectory scoring (gv_trajscore.hip): K trajectories of P poses against the costmap of gv_inflate.
+// The footprint travels by value: a call already enqueued keeps the one it was enqueued with.
+struct TrajArgs {
+  GridParams g;
+  gv_footprint fp;
+  const float *poses;           // K * P * 3 (device)
+  int32_t K, P;
+  const uint8_t *cost;          // G, OccupancyGrid.data order: cell (ix, iy) is byte G - 1 - (iy * nx + ix)
+  gv_traj_score *scores;        // K records (device memory, or the device view of pinned host memory; 16-byte aligned)
+  uint8_t *pose_cost;           // K * P, or null
+};
+void launch_score_trajectories(const TrajArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

@@ -33,6 +33,11 @@ TICK_LIDAR_RAYMARCH = 1 << 2
 INFLATE_KEEP_DIST2 = 1 << 0
 INFLATE_OCCUPANCY_SCALE = 1 << 1
 
+TRAJ_KEEP_POSE_COST = 1 << 0
+TRAJ_DEVICE_POSES = 1 << 1
+TRAJ_SCORE_DTYPE = np.dtype([("max_cost", np.int32), ("first_collision", np.int32), ("cost_sum", np.uint32),
+                             ("n_off_map", np.int32)])   # gv_traj_score
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -56,6 +61,7 @@ ABI_SYMBOLS = [
     "gv_comm_info", "gv_publish_grid_async", "gv_grid_move", "gv_set_height_band",
     "gv_inflation_cost_table", "gv_set_inflation", "gv_inflate", "gv_get_costmap", "gv_get_obstacle_dist2",
     "gv_publish_costmap_async",
+    "gv_set_footprint", "gv_score_trajectories_async", "gv_score_trajectories", "gv_footprint_cells",
 ]
 
 
@@ -89,6 +95,23 @@ class Inflation(C.Structure):
     """gv_inflation: radii in metres, the scaling factor in 1/m, lethal iff int8 >= lethal_threshold, INFLATE_* flags"""
     _fields_ = [("inscribed_radius", C.c_double), ("inflation_radius", C.c_double), ("cost_scaling_factor", C.c_double),
                 ("lethal_threshold", C.c_int32), ("flags", C.c_int32)]
+
+
+class Footprint(C.Structure):
+    """gv_footprint: n_vertices 0 (centre cell only) or 3..16, vertices in metres in the robot frame (x forward), a pose
+    collides at cost >= collision_cost, a pose that leaves the map costs off_map_cost"""
+    _fields_ = [("n_vertices", C.c_int32), ("vx", C.c_double * 16), ("vy", C.c_double * 16),
+                ("collision_cost", C.c_int32), ("off_map_cost", C.c_int32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, vertices, collision_cost=253, off_map_cost=255, flags=0):
+        """vertices: a sequence of (x, y), empty for the circular robot"""
+        f = cls()
+        f.n_vertices = len(vertices)
+        for i, (x, y) in enumerate(list(vertices)[:16]):
+            f.vx[i], f.vy[i] = float(x), float(y)
+        f.collision_cost, f.off_map_cost, f.flags = int(collision_cost), int(off_map_cost), int(flags)
+        return f
 
 
 class FrameDesc(C.Structure):
@@ -215,6 +238,23 @@ def inflation_cost_table(cfg, resolution):
     if rc:
         raise GVError(rc, "gv_inflation_cost_table")
     return table[:n.value].copy()
+
+
+def footprint_cells(grid_x, grid_y, resolution, footprint, x, y, yaw):
+    """the cells one pose tests on the grid GridVisionHIP(grid_x, grid_y, resolution) holds: int32 array, the centre cell
+    first, then the outline edge by edge, each iy * nx + ix; None for an off-map pose (host only; needs no GPU)"""
+    lib = load()
+    n = C.c_int32(0)
+    cells = np.zeros(256, np.int32)
+    for _ in range(2):
+        rc = lib.gv_footprint_cells(C.c_uint8(grid_x), C.c_uint8(grid_y), C.c_double(resolution), C.byref(footprint),
+                                    C.c_float(x), C.c_float(y), C.c_float(yaw), _ptr(cells), C.c_int32(cells.size), C.byref(n))
+        if rc == 0:
+            return None if n.value < 0 else cells[:n.value].copy()
+        if n.value <= cells.size:
+            break
+        cells = np.zeros(n.value, np.int32)
+    raise GVError(rc, "gv_footprint_cells")
 
 
 def shard_slice_words(words, world):
@@ -529,6 +569,41 @@ class GridVisionHIP:
         """the costmap to PINNED host memory (G bytes, int8 or uint8 view), like publish_grid_async"""
         assert pinned_u8.dtype in (np.int8, np.uint8) and pinned_u8.size == self.G
         self._ck(self._lib.gv_publish_costmap_async(self._h, _ptr(pinned_u8)), "gv_publish_costmap_async")
+
+    # ---- [EXTENSION] trajectory scoring against the resident costmap
+    def set_footprint(self, footprint, collision_cost=253, off_map_cost=255):
+        """the footprint of the score_trajectories() calls that follow: a Footprint, or a sequence of (x, y) vertices
+        (empty: the circular robot); set_footprint(None) turns it off"""
+        if footprint is None:
+            self._ck(self._lib.gv_set_footprint(self._h, None), "gv_set_footprint")
+            return
+        f = footprint if isinstance(footprint, Footprint) else Footprint.of(footprint, collision_cost, off_map_cost)
+        self._ck(self._lib.gv_set_footprint(self._h, C.byref(f)), "gv_set_footprint")
+
+    def score_trajectories_async(self, poses, K, P, scores, pose_cost=None, device_ptr=None):
+        """enqueue on stream(): poses float32 (K, P, 3) host array that stays unchanged until completion (or
+        device_ptr: the address of K * P * 3 floats in device memory), scores a TRAJ_SCORE_DTYPE array of K, pose_cost
+        None or a uint8 array of K * P; both complete after synchronize()"""
+        flags = (TRAJ_KEEP_POSE_COST if pose_cost is not None else 0) | (TRAJ_DEVICE_POSES if device_ptr is not None else 0)
+        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(poses)
+        self._ck(self._lib.gv_score_trajectories_async(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags),
+                                                       _ptr(scores), _ptr(pose_cost)), "gv_score_trajectories_async")
+
+    def score_trajectories(self, poses, keep_pose_cost=False, device_ptr=None):
+        """poses: float32 (K, P, 3) of (x, y, yaw) in the grid's frame (with device_ptr only its shape is used: the
+        floats are read from that device address).  Returns the TRAJ_SCORE_DTYPE array of K, and with keep_pose_cost
+        also the uint8 (K, P) pose costs."""
+        shape = np.shape(poses)
+        assert len(shape) == 3 and shape[2] == 3, "poses is (K, P, 3)"
+        K, P = int(shape[0]), int(shape[1])
+        p = _f32(poses) if device_ptr is None else None
+        scores = np.zeros(K, TRAJ_SCORE_DTYPE)
+        pc = np.zeros(K * P, np.uint8) if keep_pose_cost else None
+        flags = (TRAJ_KEEP_POSE_COST if keep_pose_cost else 0) | (TRAJ_DEVICE_POSES if device_ptr is not None else 0)
+        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(p)
+        self._ck(self._lib.gv_score_trajectories(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores),
+                                                 _ptr(pc)), "gv_score_trajectories")
+        return (scores, pc.reshape(K, P)) if keep_pose_cost else scores
 
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):

@@ -38,6 +38,12 @@ struct FlowParams {
   double lidar_ground_z = 0.3;
   double lidar_max_obstacle_z = 2.5;
   bool lidar_ground_clears = true;
+  // [EXTENSION] X6 / X7: every tick that updates the map also refreshes the inflated costmap behind the update
+  // (gv_inflate, asynchronous on the context's stream), so that a planner can score trajectories against it
+  // (OccupancyGridMap::scoreTrajectories) without asking for it.  The configuration is set once by the constructor.
+  // false (default): no costmap is made, every output of the flow is what it was.
+  bool inflate_costmap = false;
+  gv_inflation inflation{0.35, 0.55, 10.0, 65, 0};
 };
 
 // what one tick of the 50 ms timer (grid_vision_node.cpp:49-50) has to work with
@@ -83,6 +89,7 @@ public:
   FrameFlow(GridVisionContext &ctx, OccupancyGridMap &grid, const FlowParams &p) : ctx_(ctx), grid_(grid), vision_(ctx), p_(p)
   {
     if (p_.lidar_height_band) grid_.setHeightBand(p_.lidar_ground_z, p_.lidar_max_obstacle_z, p_.lidar_ground_clears);
+    if (p_.inflate_costmap) grid_.setInflation(p_.inflation);
   }
 
   // base <- camera and camera <- lidar known (transformLidarToCamera's lookup, :280-307)
@@ -174,6 +181,7 @@ private:
     if (p_.lidar_binning && ctx_.cloudSize() > 0) flags |= GV_TICK_LIDAR_BIN | (p_.lidar_raymarch ? GV_TICK_LIDAR_RAYMARCH : 0u);
     ctx_.tickEnqueue(r.bboxes, flags, p_.k_near, n_net ? orient.data() : nullptr, n_net ? conf.data() : nullptr,
                      n_net ? dims.data() : nullptr, n_net, grid_out_);
+    if (p_.inflate_costmap) grid_.inflate();   // between enqueue and wait: it inflates the tick's grid
     GridVisionContext::TickOutput t = ctx_.tickWait();
     r.depth_vec = std::move(t.depths);
     r.cam_points = std::move(t.base_points);
@@ -198,6 +206,7 @@ private:
     } else {
       grid_.updateMap();
     }
+    if (p_.inflate_costmap) grid_.inflate();
   }
 
   GridVisionContext &ctx_;

@@ -222,6 +222,23 @@ public:
     gv::check(gv_get_costmap(ctx_.handle(), data.data()), ctx_.handle(), "gv_get_costmap");
     return data;
   }
+  // [EXTENSION] X7 trajectory scoring against the costmap of the last inflate(): configure the footprint once, then
+  // score K trajectories of P poses (poses[K * P * 3]: x, y, yaw in the grid's frame).  One record per trajectory;
+  // pose_cost, when given, receives the K * P pose costs.  Synchronous; a controller that must not wait calls
+  // gv_score_trajectories_async with pinned buffers on the context's stream.
+  void setFootprint(const gv_footprint &fp) { gv::check(gv_set_footprint(ctx_.handle(), &fp), ctx_.handle(), "gv_set_footprint"); }
+  void clearFootprint() { gv::check(gv_set_footprint(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_footprint"); }
+  std::vector<gv_traj_score> scoreTrajectories(const std::vector<float> &poses, int32_t K, int32_t P,
+                                               std::vector<uint8_t> *pose_cost = nullptr)
+  {
+    if (K < 0 || P < 1 || poses.size() < (size_t)K * (size_t)P * 3) throw gv::Error(GV_ERR_BAD_ARG, "scoreTrajectories: poses is K * P * 3");
+    std::vector<gv_traj_score> scores((size_t)K);
+    if (pose_cost) pose_cost->resize((size_t)K * (size_t)P);
+    if (K == 0) return scores;
+    gv::check(gv_score_trajectories(ctx_.handle(), poses.data(), K, P, pose_cost ? GV_TRAJ_KEEP_POSE_COST : 0u, scores.data(),
+                                    pose_cost ? pose_cost->data() : nullptr), ctx_.handle(), "gv_score_trajectories");
+    return scores;
+  }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {

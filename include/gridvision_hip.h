@@ -365,6 +365,93 @@ int gv_get_costmap(gv_handle h, uint8_t *out);
 int gv_get_obstacle_dist2(gv_handle h, uint16_t *out);
 int gv_publish_costmap_async(gv_handle h, uint8_t *data);
 
+/* ------------------------------------ [EXTENSION] trajectory scoring (planner) -- */
+/* X7.  A sampling controller (MPPI, DWB) tests thousands of candidate trajectories of some tens of poses per control
+ * cycle against the costmap.  gv_score_trajectories does that on the device against the resident costmap of the last
+ * gv_inflate: K trajectories of P poses go in, K records of 16 bytes come out, the costmap never leaves the device.
+ * The reference has no such step; this text is its definition, modelled on nav2's
+ * FootprintCollisionChecker::footprintCost / lineCost.
+ *
+ * Footprint.  n_vertices == 0 is the circular robot: a pose costs what its centre cell costs (nav2 with
+ *   consider_footprint: false), and its yaw is never read.  Otherwise 3..16 vertices (vx[i], vy[i]) in metres in the
+ *   robot frame, x forward, all finite; the polygon is closed from the last vertex to the first.
+ * Pose.  Three float32 (x, y, yaw) in the grid's frame (base_link at the last map update); poses[K][P][3],
+ *   trajectory-major.
+ * Vertices in the world.  c = cos((double)yaw), s = sin((double)yaw) in fp64 and, every operation one fp64 operation in
+ *   this order, never contracted:
+ *     wx = (double)x + (c * vx[i] - s * vy[i])
+ *     wy = (double)y + (s * vx[i] + c * vy[i])
+ * Cells.  getIndex -- the grid's own (position - 0.5 * length convention, exact division at cell borders, the one every
+ *   map update uses) -- is applied to the centre ((double)x, (double)y) and to every vertex and gives grid_map cells
+ *   (ix, iy).  The cost of cell (ix, iy) is cost[G - 1 - (iy * nx + ix)]: the costmap is in OccupancyGrid.data order.
+ * Outline.  Edge i runs from the cell of vertex i to the cell of vertex (i + 1) % n.  Its cells are those of
+ *   grid_map::LineIterator(cell_i, cell_i+1), both ends included: with ddx = |dx|, ddy = |dy| the major axis is x when
+ *   ddx >= ddy and steps every cell, major + 1 cells in all; num = major / 2 at the start, num += minor after every
+ *   cell, and the minor axis steps (num -= major) when num >= major.  Because of the truncated major / 2 and the tie
+ *   at ddx == ddy THE DIRECTION OF AN EDGE MATTERS: the cells from a to b are not always those from b to a, so the
+ *   order of the vertices is part of the footprint.  Only the outline is tested, as nav2 does; a lethal cell strictly
+ *   inside the polygon does not count.
+ * Pose cost.  If the centre or any vertex is off the map (getIndex's own test; a NaN or infinite coordinate fails it,
+ *   and so does every vertex of a pose with a NaN or infinite yaw) the pose cost is off_map_cost.  Otherwise it is the
+ *   maximum of the centre cell's cost and the cost of every outline cell.
+ * Per trajectory (gv_traj_score):
+ *   max_cost         the maximum pose cost;
+ *   first_collision  the smallest pose index whose cost is >= collision_cost, -1 when none is;
+ *   cost_sum         the sum over the poses of the centre cell's cost, off_map_cost for an off-map pose (what DWB's
+ *                    BaseObstacle and MPPI's cost critic add up);
+ *   n_off_map        the number of off-map poses.
+ *   All four are maxima, minima and integer sums: the result does not depend on how the work is scheduled.
+ * With GV_TRAJ_KEEP_POSE_COST, pose_cost[K * P] (uint8) also receives every pose cost.
+ *
+ * gv_set_footprint is handle configuration like gv_set_inflation: no device work, kept through gv_reset,
+ * gv_set_log_odds and gv_grid_move; NULL turns it off (the state after gv_create).  Every scoring call carries the
+ * footprint in force when it is enqueued; a later gv_set_footprint does not reach it.  GV_ERR_BAD_ARG, configuration
+ * unchanged, for a null handle, n_vertices of 1, 2 or more than 16 (or negative), a non-finite vertex among the first
+ * n_vertices, collision_cost outside 1..255, off_map_cost outside 0..255, or flags other than 0.
+ * gv_score_trajectories_async enqueues the scoring on gv_stream(h) without a host wait (the allocations of a first or
+ * larger call aside); it reads the costmap as the last enqueued gv_inflate left it and is ordered like gv_inflate
+ * itself: behind everything enqueued before it, ahead of what follows; allowed between gv_tick_enqueue and
+ * gv_tick_wait.  poses is host memory, copied on the public stream (it must stay unchanged until completion; pinned
+ * memory, gv_host_alloc, makes the copy truly asynchronous); with GV_TRAJ_DEVICE_POSES it is device memory that the
+ * kernel reads in place, and the caller orders its producer before gv_stream(h).  scores -- and pose_cost, required
+ * with GV_TRAJ_KEEP_POSE_COST and ignored without -- follow gv_publish_grid_async's rules: pinned memory (scores
+ * 16-byte aligned) is written by the kernel without a copy command, anything else through a copy command; either is
+ * complete once an event recorded on gv_stream(h) after the call has passed, or after gv_synchronize.
+ * K == 0 is a successful no-op (once the arguments and the state below have passed).  GV_ERR_BAD_ARG for a null
+ * handle, null poses or scores, P outside 1..4096, K < 0 or K > 2^20, unknown flags, or GV_TRAJ_KEEP_POSE_COST with a
+ * null pose_cost.  GV_ERR_STATE when no footprint is set,
+ * when no gv_inflate has run since gv_create / gv_reset, and with a communicator of more than one rank.
+ * gv_score_trajectories is the same call followed by the wait for it.
+ * gv_footprint_cells is host only and takes no handle: the cells one pose tests on the grid gv_create(grid_x, grid_y,
+ * resolution) makes, with the library's own geometry code -- cells[0] the centre, then the outline edge by edge (an
+ * edge's cells in line order, shared vertex cells repeated), each as iy * nx + ix; *n receives their number, also
+ * when that exceeds cap (then GV_ERR_BAD_ARG, nothing written), and -1 for an off-map pose (GV_OK).  GV_ERR_BAD_ARG
+ * for an invalid footprint or geometry or a null n. */
+enum {
+  GV_TRAJ_KEEP_POSE_COST = 1 << 0,   /* write pose_cost[K * P]                    */
+  GV_TRAJ_DEVICE_POSES   = 1 << 1    /* poses is device memory, read in place     */
+};
+typedef struct {
+  int32_t n_vertices;         /* 0 (centre cell only) or 3..16                              */
+  double vx[16], vy[16];      /* m, robot frame, x forward; the first n_vertices are read    */
+  int32_t collision_cost;     /* 1..255: a pose collides when its cost is >= this            */
+  int32_t off_map_cost;       /* 0..255: the cost of a pose that leaves the map              */
+  uint32_t flags;             /* 0                                                           */
+} gv_footprint;
+typedef struct {
+  int32_t max_cost;
+  int32_t first_collision;
+  uint32_t cost_sum;
+  int32_t n_off_map;
+} gv_traj_score;
+int gv_set_footprint(gv_handle h, const gv_footprint *fp);
+int gv_score_trajectories_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags,
+                                gv_traj_score *scores, uint8_t *pose_cost);
+int gv_score_trajectories(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags,
+                          gv_traj_score *scores, uint8_t *pose_cost);
+int gv_footprint_cells(uint8_t grid_x, uint8_t grid_y, double resolution, const gv_footprint *fp, float x, float y,
+                       float yaw, int32_t *cells, int32_t cap, int32_t *n);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
@@ -464,7 +551,8 @@ typedef struct {
  * GV_ERR_STATE, and so do, between the two, the synchronous calls that would reuse the tick's result block or its
  * detection set (gv_compute_depth_for_bboxes, gv_compute_bbox_pose*, gv_segment_ground_plane, gv_extract_cloud_per_bbox,
  * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map*,
- * gv_grid_move, gv_set_transforms, gv_set_height_band, gv_set_inflation, gv_inflate and the costmap getters may be
+ * gv_grid_move, gv_set_transforms, gv_set_height_band, gv_set_inflation, gv_inflate, the costmap getters,
+ * gv_set_footprint and gv_score_trajectories* may be
  * called; their device work is ordered behind the tick on gv_stream(h), and an upload never
  * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
  * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform or height
