@@ -36,12 +36,8 @@ namespace gv_internal __attribute__((visibility("hidden"))) {
 
 int drain(gv_context *h)
 {
-  GV_HIP(hipStreamSynchronize(h->stream_copy));
-  GV_HIP(hipStreamSynchronize(h->stream));
-  GV_HIP(hipStreamSynchronize(h->stream2));
-  GV_HIP(hipStreamSynchronize(h->stream3));
-  if (h->stream4) GV_HIP(hipStreamSynchronize(h->stream4));
-  if (h->stream_x) GV_HIP(hipStreamSynchronize(h->stream_x));
+  for (hipStream_t s : h->own_streams())
+    if (s) GV_HIP(hipStreamSynchronize(s));
   h->pipe_busy = false;
   h->last_fin_slot = -1;
   for (auto &f : h->fs) f.fin_slot = -1;
@@ -52,7 +48,7 @@ int drain(gv_context *h)
   return GV_OK;
 }
 
-bool sector_path(const gv_context *h) { return h->tile_path && !h->force_simple; }
+bool sector_path(const gv_context *h) { return h->tile_path && !h->tune.force_simple; }
 
 int set_device_only(gv_context *h)
 {
@@ -72,27 +68,17 @@ int use_device(gv_context *h)
 // plain grid update (A7 / A8 / A10): rectangles already in fs[0].rects
 int enqueue_plain_update(gv_context *h, int32_t n_rects)
 {
-  if (sector_path(h)) {
-    FinalizeTileArgs t{};
-    t.g = h->g;
-    t.log_odds = h->log_odds;
-    t.occupancy = h->occupancy;
-    t.occ_i8 = h->occ_i8;
-    t.rects = h->fs[0].rects;
-    t.n_rects = n_rects;
-    t.hitN = h->fs[0].hitN;
-    t.freeN = h->fs[0].freeN;
-    t.freeT = h->fs[0].freeT;
-    t.nx_pad = h->nx_pad;
-    t.ny_pad = h->ny_pad;
-    t.counts = false;
-    t.dense = h->grid_pass_dense();
-    t.y_begin = 0;
-    t.y_end = h->g.ny;
-    if (launch_finalize_tiles(t, h->stream) && t.dense) h->layers_in_step = true;
-    GV_HIP(hipGetLastError());
-    return GV_OK;
-  }
+  if (sector_path(h))   // the frame's grid pass without the hit/miss rule, over every row
+    return enqueue_grid_pass(h, 0, h->fs[0].rects, n_rects, false, 0, h->g.ny, h->stream, nullptr, nullptr, nullptr, false, false);
+  launch_finalize(finalize_args(h, n_rects), h->stream);
+  GV_HIP(hipGetLastError());
+  return GV_OK;
+}
+
+// the generic grid pass over every cell with the rectangles in fs[0].rects and no hit/miss rule (a plain update); the
+// generic frame adds its count grids
+FinalizeArgs finalize_args(const gv_context *h, int32_t n_rects)
+{
   FinalizeArgs f{};
   f.g = h->g;
   f.log_odds = h->log_odds;
@@ -100,15 +86,9 @@ int enqueue_plain_update(gv_context *h, int32_t n_rects)
   f.occ_i8 = h->occ_i8;
   f.rects = h->fs[0].rects;
   f.n_rects = n_rects;
-  f.hits = nullptr;
-  f.miss = nullptr;
-  f.clip_end = nullptr;
-  f.zero_counts = false;
   f.cell_begin = 0;
   f.cell_end = h->g.G;
-  launch_finalize(f, h->stream);
-  GV_HIP(hipGetLastError());
-  return GV_OK;
+  return f;
 }
 
 int ensure_tbuf(gv_context *h, size_t n)
@@ -147,6 +127,225 @@ void convert_pixels_host(const double Kinv[9], const Xform64 &x_bc, const gv_bbo
 
 }  // namespace gv_internal
 
+// ---- gv_create, step by step.  The steps run in this order and make their HIP calls in the order written: the order
+// in which streams are created and first used decides which hardware queue each lands on (profiles/r03/h2d_notes.md).
+namespace {
+
+#define GV_C(call)                                           \
+  do {                                                       \
+    if ((call) != 0) return GV_ERR_HIP;                      \
+  } while (0)
+
+// every knob of the handle, from the environment
+void read_tuning(Tuning &t)
+{
+  auto num = [](const char *name, int &v) {
+    const char *e = std::getenv(name);
+    if (e) v = std::atoi(e);
+    return e != nullptr;
+  };
+  int v = 0;
+  if (num("GV_LANES", v)) t.n_lanes = (v == 2) ? 2 : 3;
+  t.lane3_own_stream = std::getenv("GV_LANE3_OWN_STREAM") != nullptr;
+  if (num("GV_QUEUE_PROBE", v)) t.queue_probe = v != 0;
+  t.verbose = std::getenv("GV_VERBOSE") != nullptr;
+  if (num("GV_TICK_KNN_LANE", v)) t.tick_knn_lane = v != 0;
+  const char *impl = std::getenv("GV_RAY_IMPL");
+  t.force_simple = impl && std::strcmp(impl, "simple") == 0;
+  if (num("GV_PIPELINE", v)) t.no_pipeline = v == 0;
+  num("GV_LOG2S", t.log2s);
+  if (const char *e = std::getenv("GV_LOG2S_OCT")) {
+    int k = 0;
+    for (const char *q = e; *q && k < 8; ++k) {
+      t.log2s_oct[k] = std::atoi(q);
+      while (*q && *q != ',') ++q;
+      if (*q == ',') ++q;
+    }
+  }
+  if (num("GV_SECTOR_REORDER", v)) t.reorder = v != 0;
+  if (num("GV_SECTOR_HELPERS", v)) t.helpers = v != 0;
+  if (num("GV_ANYORDER", v)) t.anyorder = v != 0;
+  if (num("GV_GRID_SKIP", v)) t.grid_skip = v != 0;
+  num("GV_CAP", t.cap);
+  if (num("GV_FLAT_K", v)) t.flat_k = std::max(0, v);
+  if (num("GV_FLAT_DIRECT", v)) t.flat_direct = (uint32_t)std::max(0, v);
+  if (num("GV_MARCH_LIMIT", v)) t.march_limit = (uint32_t)std::max(0, v);
+  if (num("GV_LOG2M", v)) t.log2m = std::min(9, std::max(4, v));
+  num("GV_SECTOR_REV", t.sector_rev);
+#ifdef GV_DIAG
+  num("GV_ABLATE", t.ablate);
+  if (num("GV_BIN_DBG", v)) t.bin_dbg = v > 0;
+  if (num("GV_TIMELINE", v)) t.timeline = v > 0;
+  if (num("GV_SECTOR_DBG", v)) t.sector_dbg = v > 0;
+#endif
+}
+
+// grid_map::GridMap::setGeometry + setPosition (src/occupancy_grid.cpp:10-11), the camera, the padded grid of the
+// tile path.  Host only.
+bool set_geometry(gv_context *h, uint8_t grid_x, uint8_t grid_y, double resolution, const gv_cam_params *cam)
+{
+  GridParams &g = h->g;
+  if (!host::grid_params(grid_x, grid_y, resolution, g)) return false;
+  h->cam = *cam;
+  host::intrinsics((double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, h->K, h->Kinv);
+  for (int i = 0; i < 9; ++i) h->camk.k[i] = h->K[i];
+  h->camk.W = cam->orig_w;
+  h->camk.H = cam->orig_h;
+  h->bt_tiles_x = std::max(1, (cam->orig_w + 15) / 16);
+  h->bt_tiles_y = std::max(1, (cam->orig_h + 15) / 16);
+  // packed (a,b) fields hold 13 bits each; vector stores need nx % 4 == 0
+  h->tile_path = (g.nx % 4 == 0) && g.nx <= 8000 && g.ny <= 8000;
+  // bitmaps: padded to whole binning tiles, so that every word belongs to exactly one tile
+  h->nx_pad = kBinTile * ((g.nx + kBinTile - 1) / kBinTile);
+  h->ny_pad = kBinTile * ((g.ny + kBinTile - 1) / kBinTile);
+  h->nxw = h->nx_pad / 32;
+  h->nyw = h->ny_pad / 32;
+  h->tiles_x = h->nx_pad / kBinTile;
+  h->tiles_y = h->ny_pad / kBinTile;
+  h->n_tiles = h->tiles_x * h->tiles_y;
+  return true;
+}
+
+int create_streams(gv_context *h)
+{
+  GV_C(h->stream.create());
+  GV_C(h->lane[0].create());
+  GV_C(h->lane[1].create());
+  GV_C(h->stream_copy.create());
+  if (h->tune.n_lanes == 3 && h->tune.lane3_own_stream) GV_C(h->lane[2].create());
+  return GV_OK;
+}
+
+// The upload stream must not share a hardware queue with the public stream or a lane (a process gets four
+// queues; a stream created when four exist joins the one with the fewest streams, ties by address -- e.g. a host
+// application or framework that owns a stream already pushes one of ours onto a shared queue, and when that is
+// the upload stream every cloud waits behind kernels: the 0.55-0.8-of-copy-rate regime of profiles/r03/h2d_notes.md).
+// Probe: hold the three compute streams busy for 150 us each, time a 4-byte memset on the upload stream; if it had
+// to wait, make another upload stream (before letting go of this one, so that it lands elsewhere) and try again.
+int probe_upload_queue(gv_context *h)
+{
+  DevBuf<unsigned> probe;
+  GV_C(probe.reserve(h, 64));
+  std::vector<Stream> rejected;   // let go after the loop: a replacement made while they exist lands elsewhere
+  launch_hold(1ull, h->stream);   // (the kernel's code object is loaded before anything is timed)
+  // Only the handle's own streams are synchronised (a device-wide wait would stall on, and be perturbed by, every
+  // other handle or application stream of the process); a stream's hardware queue is created on its first use, so
+  // one untimed memset goes first.  Costs 0.3-1 ms per gv_create; GV_QUEUE_PROBE=0 skips it.
+  auto sync_own = [&]() -> hipError_t {
+    for (hipStream_t q : h->own_streams()) {
+      const hipError_t e = q ? hipStreamSynchronize(q) : hipSuccess;
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  };
+  for (int attempt = 0; attempt < 6; ++attempt) {
+    GV_C(hipMemsetAsync(probe, 0, 4, h->stream_copy));   // untimed: the queue exists afterwards
+    GV_C(sync_own());
+    for (hipStream_t q : {(hipStream_t)h->stream, (hipStream_t)h->lane[0], (hipStream_t)h->lane[1]})
+      launch_hold(15000ull, q);   // 150 us at 100 MHz
+    const auto t0 = std::chrono::steady_clock::now();
+    GV_C(hipMemsetAsync(probe, 0, 4, h->stream_copy));
+    GV_C(hipStreamSynchronize(h->stream_copy));
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    GV_C(sync_own());
+    h->upload_probe_us = us;
+    if (us < 90.0) break;
+    h->upload_stream_retries++;
+    Stream nw;
+    GV_C(nw.create());
+    rejected.push_back(std::move(h->stream_copy));
+    h->stream_copy = std::move(nw);
+  }
+  if (h->tune.verbose)
+    std::fprintf(stderr, "gridvision_hip: upload stream probe %.0f us, %d replacement(s)\n", h->upload_probe_us, h->upload_stream_retries);
+  return GV_OK;
+}
+
+// the view the frame code indexes, and the ordering events
+int create_events(gv_context *h)
+{
+  h->streams[0] = h->stream;
+  for (int l = 0; l < gv_context::kLanesMax; ++l) h->streams[1 + l] = h->lane[l];
+  if (!h->lane[2]) h->streams[3] = h->stream_copy;   // the third lane runs on the upload stream (gv_context::lanes_now)
+  // Ordering-only events between queues of this device (and a completion flag the host polls): nobody reads
+  // memory on the strength of them -- results are read in stream order on the public stream or after a
+  // stream synchronise -- so the kernels that carry them need no system-scope release at their end.
+  for (auto &e : h->ev_fin) GV_C(e.create(hipEventDisableTiming | hipEventDisableSystemFence));
+  for (auto &e : h->ev_sec) GV_C(e.create(hipEventDisableTiming | hipEventDisableSystemFence));
+  GV_C(h->ev_join.create(hipEventDisableTiming));
+  GV_C(h->tick.done.create(hipEventDisableTiming));
+  GV_C(h->tick.fork.create(hipEventDisableTiming));
+  GV_C(h->tick.join.create(hipEventDisableTiming));
+  for (auto &c : h->cloud) GV_C(c.ready.create(hipEventDisableTiming));
+  for (auto &d : h->det) GV_C(d.ready.create(hipEventDisableTiming));
+  return GV_OK;
+}
+
+// the resident layers, the count grids and bitmaps of every stream and buffer set (zeroed on the public stream), the
+// timing events
+int alloc_grid(gv_context *h)
+{
+  const size_t G = (size_t)h->g.G;
+  GV_C(h->log_odds.reserve(h, G));
+  GV_C(h->occupancy.reserve(h, G));
+  GV_C(h->occ_i8.reserve(h, G));
+  GV_C(h->ray_count.reserve_zeroed(h, 4, h->stream));
+  GV_C(h->scratch_i32.reserve(h, G));
+#ifdef GV_DIAG
+  if (h->tune.bin_dbg)
+    for (auto &q : h->d_bin_dbg) GV_C(q.reserve_zeroed(h, 8192 * 16, h->stream));
+  if (h->tune.timeline) {
+    const size_t nt = gv_context::kTlFrames * 8;
+    GV_C(h->d_tl.reserve(h, nt));
+    std::vector<unsigned long long> init(nt);
+    for (size_t i = 0; i < nt; i += 2) { init[i] = ~0ull; init[i + 1] = 0ull; }
+    GV_C(hipMemcpy(h->d_tl, init.data(), nt * sizeof(unsigned long long), hipMemcpyHostToDevice));
+  }
+  if (h->tune.sector_dbg) GV_C(h->d_dbg.reserve_zeroed(h, kMaxStatSlots * 16, h->stream));
+#endif
+  const bool sectors = sector_path(h);
+  const int n_streams = sectors ? 1 + h->tune.n_lanes : 1;
+  for (int k = 0; k < n_streams; ++k) GV_C(h->sb[k].hits.reserve_zeroed(h, G, h->stream));
+  for (int k = 0; k < (sectors ? gv_context::kSets : 1); ++k)
+    GV_C(h->fs[k].stats.reserve_zeroed(h, kMaxStatSlots * 2, h->stream));
+  if (sectors) {
+    h->bmN_words = (size_t)h->ny_pad * h->nxw;   // multiples of 4 words (pads are multiples of 128)
+    h->bmT_words = (size_t)h->nx_pad * h->nyw;
+    h->ends_words = 2 * (h->bmN_words + h->bmT_words);
+    for (FrameSet &f : h->fs) {
+      // + slack: the sharded exchange pads the buffer to `world` equal slices
+      GV_C(f.ends.reserve_zeroed(h, h->ends_words + 1024, h->stream));
+      f.hitN = f.ends;
+      f.clipN = f.hitN + h->bmN_words;
+      f.hitT = f.clipN + h->bmN_words;
+      f.clipT = f.hitT + h->bmT_words;
+      GV_C(f.free_.reserve_zeroed(h, h->bmN_words + h->bmT_words + 16, h->stream));
+      f.freeN = f.free_;
+      f.freeT = f.free_ + h->bmN_words;
+    }
+    for (int q = 0; q < n_streams; ++q) {
+      for (auto &tot : h->sb[q].bin_total) GV_C(tot.reserve_zeroed(h, (size_t)h->n_tiles, h->stream));
+      GV_C(h->sb[q].bin_done.reserve_zeroed(h, (size_t)h->n_tiles, h->stream));
+    }
+  } else {
+    // generic path: byte flags of clipped ray ends and of free cells + the compacted ray list
+    GV_C(h->clip_end.reserve_zeroed(h, G + 16, h->stream));
+    GV_C(h->miss8.reserve_zeroed(h, G + 16, h->stream));
+    GV_C(h->ray_list.reserve(h, G));
+  }
+  for (auto &e : h->ev) GV_C(e.create(hipEventDefault));   // timing events
+  for (auto &pr : h->kt)
+    for (auto &e : pr) GV_C(e.create(hipEventDefault));
+  // what follows the detection count and the cloud, at its starting size
+  GV_C(ensure_det_shared(h, 64));
+  for (auto &d : h->det) GV_C(ensure_det(h, d, 64));
+  GV_C(ensure_point_buffers(h, 0));
+  return GV_OK;
+}
+#undef GV_C
+
+}  // namespace
+
 extern "C" {
 
 int gv_abi_version(void) { return 4; }
@@ -167,195 +366,17 @@ int gv_create(gv_handle *out, uint8_t grid_x, uint8_t grid_y, double resolution,
   }
   if (device_id >= ndev) { delete h; return GV_ERR_NO_DEVICE; }
   h->device = device_id;
-  // grid_map::GridMap::setGeometry + setPosition  (src/occupancy_grid.cpp:10-11)
-  GridParams &g = h->g;
-  if (!host::grid_params(grid_x, grid_y, resolution, g)) { delete h; return GV_ERR_BAD_ARG; }
-  h->cam = *cam;
-  host::intrinsics((double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, h->K, h->Kinv);
-  for (int i = 0; i < 9; ++i) h->camk.k[i] = h->K[i];
-  h->camk.W = cam->orig_w;
-  h->camk.H = cam->orig_h;
-  h->bt_tiles_x = std::max(1, (cam->orig_w + 15) / 16);
-  h->bt_tiles_y = std::max(1, (cam->orig_h + 15) / 16);
-
+  if (!set_geometry(h, grid_x, grid_y, resolution, cam)) { delete h; return GV_ERR_BAD_ARG; }
+  read_tuning(h->tune);
   auto fail = [&](int code) { gv_destroy(h); return code; };
-#define GV_C(call)                                           \
-  do {                                                       \
-    if ((call) != 0) return fail(GV_ERR_HIP);                \
-  } while (0)
-  GV_C(hipSetDevice(h->device));
-  GV_C(h->stream.create());
-  GV_C(h->stream2.create());
-  GV_C(h->stream3.create());
-  GV_C(h->stream_copy.create());
-  if (const char *e = std::getenv("GV_LANES")) h->n_lanes = (std::atoi(e) == 2) ? 2 : 3;
-  // (GV_LANE3_OWN_STREAM=1, experiment: the third lane on a fifth stream instead of the upload stream)
-  if (h->n_lanes == 3 && std::getenv("GV_LANE3_OWN_STREAM")) GV_C(h->stream4.create());
-  // The upload stream must not share a hardware queue with the public stream or a lane (a process gets four
-  // queues; a stream created when four exist joins the one with the fewest streams, ties by address -- e.g. a host
-  // application or framework that owns a stream already pushes one of ours onto a shared queue, and when that is
-  // the upload stream every cloud waits behind kernels: the 0.55-0.8-of-copy-rate regime of profiles/r03/h2d_notes.md).
-  // Probe: hold the three compute streams busy for 150 us each, time a 4-byte memset on the upload stream; if it had
-  // to wait, make another upload stream (before letting go of this one, so that it lands elsewhere) and try again.
-  if (!(std::getenv("GV_QUEUE_PROBE") && std::atoi(std::getenv("GV_QUEUE_PROBE")) == 0)) {
-    DevBuf<unsigned> probe;
-    GV_C(probe.reserve(h, 64));
-    std::vector<Stream> rejected;   // let go after the loop: a replacement made while they exist lands elsewhere
-    launch_hold(1ull, h->stream);   // (the kernel's code object is loaded before anything is timed)
-    // Only the handle's own streams are synchronised (a device-wide wait would stall on, and be perturbed by, every
-    // other handle or application stream of the process); a stream's hardware queue is created on its first use, so
-    // one untimed memset goes first.  Costs 0.3-1 ms per gv_create; GV_QUEUE_PROBE=0 skips it.
-    auto sync_own = [&]() -> hipError_t {
-      for (hipStream_t q : std::initializer_list<hipStream_t>{h->stream, h->stream2, h->stream3, h->stream_copy}) {
-        const hipError_t e = hipStreamSynchronize(q);
-        if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
-    };
-    for (int attempt = 0; attempt < 6; ++attempt) {
-      GV_C(hipMemsetAsync(probe, 0, 4, h->stream_copy));   // untimed: the queue exists afterwards
-      GV_C(sync_own());
-      for (hipStream_t q : std::initializer_list<hipStream_t>{h->stream, h->stream2, h->stream3})
-        launch_hold(15000ull, q);   // 150 us at 100 MHz
-      const auto t0 = std::chrono::steady_clock::now();
-      GV_C(hipMemsetAsync(probe, 0, 4, h->stream_copy));
-      GV_C(hipStreamSynchronize(h->stream_copy));
-      const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-      GV_C(sync_own());
-      h->upload_probe_us = us;
-      if (us < 90.0) break;
-      h->upload_stream_retries++;
-      Stream nw;
-      GV_C(nw.create());
-      rejected.push_back(std::move(h->stream_copy));
-      h->stream_copy = std::move(nw);
-    }
-    if (std::getenv("GV_VERBOSE"))
-      std::fprintf(stderr, "gridvision_hip: upload stream probe %.0f us, %d replacement(s)\n", h->upload_probe_us, h->upload_stream_retries);
-  }
-  h->streams[0] = h->stream;
-  h->streams[1] = h->stream2;
-  h->streams[2] = h->stream3;
-  h->streams[3] = h->stream4 ? h->stream4 : h->stream_copy;
-  // Ordering-only events between queues of this device (and a completion flag the host polls): nobody reads
-  // memory on the strength of them -- results are read in stream order on the public stream or after a
-  // stream synchronise -- so the kernels that carry them need no system-scope release at their end.
-  for (auto &e : h->ev_fin) GV_C(e.create(hipEventDisableTiming | hipEventDisableSystemFence));
-  for (auto &e : h->ev_sec) GV_C(e.create(hipEventDisableTiming | hipEventDisableSystemFence));
-  GV_C(h->ev_join.create(hipEventDisableTiming));
-  GV_C(h->tick.done.create(hipEventDisableTiming));
-  GV_C(h->tick.fork.create(hipEventDisableTiming));
-  GV_C(h->tick.join.create(hipEventDisableTiming));
-  if (const char *e = std::getenv("GV_TICK_KNN_LANE")) h->env_tick_knn_lane = std::atoi(e) != 0;
-  for (auto &c : h->cloud) GV_C(c.ready.create(hipEventDisableTiming));
-  for (auto &d : h->det) GV_C(d.ready.create(hipEventDisableTiming));
-  const size_t G = (size_t)g.G;
-  GV_C(h->log_odds.reserve(h, G));
-  GV_C(h->occupancy.reserve(h, G));
-  GV_C(h->occ_i8.reserve(h, G));
-  GV_C(h->ray_count.reserve_zeroed(h, 4, h->stream));
-  GV_C(h->scratch_i32.reserve(h, G));
-  // packed (a,b) fields hold 13 bits each; vector stores need nx % 4 == 0
-  h->tile_path = (g.nx % 4 == 0) && g.nx <= 8000 && g.ny <= 8000;
-  {
-    const char *impl = std::getenv("GV_RAY_IMPL");
-    h->force_simple = impl && std::strcmp(impl, "simple") == 0;
-    if (const char *e = std::getenv("GV_PIPELINE")) h->no_pipeline = std::atoi(e) == 0;
-    if (const char *e = std::getenv("GV_LOG2S")) h->env_log2s = std::atoi(e);
-    if (const char *e = std::getenv("GV_LOG2S_OCT")) {
-      int k = 0;
-      for (const char *q = e; *q && k < 8; ++k) {
-        h->env_log2s_oct[k] = std::atoi(q);
-        while (*q && *q != ',') ++q;
-        if (*q == ',') ++q;
-      }
-    }
-    if (const char *e = std::getenv("GV_SECTOR_REORDER")) h->env_reorder = std::atoi(e) != 0;
-    if (const char *e = std::getenv("GV_SECTOR_HELPERS")) h->env_helpers = std::atoi(e) != 0;
-    if (const char *e = std::getenv("GV_ANYORDER")) h->env_anyorder = std::atoi(e) != 0;
-    if (const char *e = std::getenv("GV_GRID_SKIP")) h->env_grid_skip = std::atoi(e) != 0;
-    if (const char *e = std::getenv("GV_CAP")) h->env_cap = std::atoi(e);
-    if (const char *e = std::getenv("GV_FLAT_K")) h->env_flat_k = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("GV_FLAT_DIRECT")) h->env_flat_direct = (uint32_t)std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("GV_MARCH_LIMIT")) h->env_march_limit = (uint32_t)std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("GV_LOG2M")) h->env_log2m = std::min(9, std::max(4, std::atoi(e)));
-    if (const char *e = std::getenv("GV_SECTOR_REV")) h->env_sector_rev = std::atoi(e);
-#ifdef GV_DIAG
-    if (const char *e = std::getenv("GV_ABLATE")) h->env_ablate = std::atoi(e);
-    if (const char *e = std::getenv("GV_BIN_DBG")) {
-      if (std::atoi(e) > 0)
-        for (auto &q : h->d_bin_dbg) {
-          GV_C(q.reserve_zeroed(h, 8192 * 16, h->stream));
-        }
-    }
-    if (const char *e = std::getenv("GV_TIMELINE")) {
-      if (std::atoi(e) > 0) {
-        const size_t nt = gv_context::kTlFrames * 8;
-        GV_C(h->d_tl.reserve(h, nt));
-        std::vector<unsigned long long> init(nt);
-        for (size_t i = 0; i < nt; i += 2) { init[i] = ~0ull; init[i + 1] = 0ull; }
-        GV_C(hipMemcpy(h->d_tl, init.data(), nt * sizeof(unsigned long long), hipMemcpyHostToDevice));
-      }
-    }
-    if (const char *e = std::getenv("GV_SECTOR_DBG")) {
-      if (std::atoi(e) > 0) {
-        GV_C(h->d_dbg.reserve_zeroed(h, kMaxStatSlots * 16, h->stream));
-      }
-    }
-#endif
-  }
-  const bool sectors = h->tile_path && !h->force_simple;
-  const int nsets_alloc = sectors ? gv_context::kSets : 1;
-  for (int k = 0; k < (sectors ? 1 + h->n_lanes : 1); ++k) {
-    GV_C(h->sb[k].hits.reserve_zeroed(h, G, h->stream));
-  }
-  h->hits = h->sb[0].hits;
-  for (int k = 0; k < nsets_alloc; ++k) {
-    GV_C(h->fs[k].stats.reserve_zeroed(h, kMaxStatSlots * 2, h->stream));
-  }
-  // bitmaps: padded to whole binning tiles, so that every word belongs to exactly one tile
-  h->nx_pad = kBinTile * ((g.nx + kBinTile - 1) / kBinTile);
-  h->ny_pad = kBinTile * ((g.ny + kBinTile - 1) / kBinTile);
-  h->nxw = h->nx_pad / 32;
-  h->nyw = h->ny_pad / 32;
-  h->tiles_x = h->nx_pad / kBinTile;
-  h->tiles_y = h->ny_pad / kBinTile;
-  h->n_tiles = h->tiles_x * h->tiles_y;
-  if (sectors) {
-    h->bmN_words = (size_t)h->ny_pad * h->nxw;   // multiples of 4 words (pads are multiples of 128)
-    h->bmT_words = (size_t)h->nx_pad * h->nyw;
-    h->ends_words = 2 * (h->bmN_words + h->bmT_words);
-    for (FrameSet &f : h->fs) {
-      // + slack: the sharded exchange pads the buffer to `world` equal slices
-      GV_C(f.ends.reserve_zeroed(h, h->ends_words + 1024, h->stream));
-      f.hitN = f.ends;
-      f.clipN = f.hitN + h->bmN_words;
-      f.hitT = f.clipN + h->bmN_words;
-      f.clipT = f.hitT + h->bmT_words;
-      GV_C(f.free_.reserve_zeroed(h, h->bmN_words + h->bmT_words + 16, h->stream));
-      f.freeN = f.free_;
-      f.freeT = f.free_ + h->bmN_words;
-    }
-    for (int q = 0; q < 1 + h->n_lanes; ++q) {
-      for (auto &tot : h->sb[q].bin_total) GV_C(tot.reserve_zeroed(h, (size_t)h->n_tiles, h->stream));
-      GV_C(h->sb[q].bin_done.reserve_zeroed(h, (size_t)h->n_tiles, h->stream));
-    }
-  } else {
-    // generic path: byte flags of clipped ray ends and of free cells + the compacted ray list
-    GV_C(h->clip_end.reserve_zeroed(h, G + 16, h->stream));
-    GV_C(h->miss8.reserve_zeroed(h, G + 16, h->stream));
-    GV_C(h->ray_list.reserve(h, G));
-  }
-  for (auto &e : h->ev) GV_C(e.create(hipEventDefault));   // timing events
-  for (auto &pr : h->kt)
-    for (auto &e : pr) GV_C(e.create(hipEventDefault));
-#undef GV_C
-  if (ensure_det_shared(h, 64) != GV_OK) return fail(GV_ERR_HIP);
-  for (auto &d : h->det)
-    if (ensure_det(h, d, 64) != GV_OK) return fail(GV_ERR_HIP);
-  if (ensure_point_buffers(h, 0) != GV_OK) return fail(GV_ERR_HIP);
+  if (hipSetDevice(h->device) != hipSuccess) return fail(GV_ERR_HIP);
+  int rc;
+  if ((rc = create_streams(h))) return fail(rc);
+  if (h->tune.queue_probe && (rc = probe_upload_queue(h))) return fail(rc);
+  if ((rc = create_events(h))) return fail(rc);
+  if ((rc = alloc_grid(h))) return fail(rc);
   *out = h;
-  int rc = gv_reset(h);
+  rc = gv_reset(h);
   if (rc != GV_OK) { *out = nullptr; return fail(rc); }
   return GV_OK;
   GV_CATCH
@@ -366,7 +387,7 @@ int gv_destroy(gv_handle h)
 {
   if (!h) return GV_ERR_BAD_ARG;
   (void)hipSetDevice(h->device);
-  for (hipStream_t s : std::initializer_list<hipStream_t>{h->stream_copy, h->stream, h->stream2, h->stream3, h->stream4, h->stream_x})
+  for (hipStream_t s : h->own_streams())
     if (s) (void)hipStreamSynchronize(s);
   comm_destroy(h);
   delete h;
@@ -451,25 +472,13 @@ int gv_transform_lidar_to_camera(gv_handle h, float *x_cam, float *y_cam, float 
   GV_CATCH
 }
 
-static void bbox_points_args(gv_context *h, PointsArgs &a)
-{
-  a.x = h->cx; a.y = h->cy; a.z = h->cz;
-  a.n = (uint32_t)h->n;
-  a.g = h->g;
-  a.m_cam = h->m_cam;
-  a.cam = h->camk;
-  a.bt = bbox_test_of(h, h->det[2]);
-  a.bbox_id = h->bbox_id;
-  a.do_bbox = true;
-}
-
 // device int16 ids -> caller's int32 array
 static int read_back_ids(gv_context *h, int32_t *out)
 {
   if (!h->n) return GV_OK;
   int rc = ensure_scratch_i32(h, h->n);
   if (rc) return rc;
-  launch_i16_to_i32(h->bbox_id, h->scratch_i32, h->n, h->stream);
+  launch_i16_to_i32(h->sb[h->last.points].bbox_id, h->scratch_i32, h->n, h->stream);
   GV_HIP(hipGetLastError());
   GV_HIP(hipMemcpyAsync(out, h->scratch_i32, h->n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   GV_HIP(hipStreamSynchronize(h->stream));
@@ -484,13 +493,11 @@ int gv_extract_cloud_per_bbox(gv_handle h, const gv_bbox *bboxes, int32_t nb, in
   int rc = use_device(h);
   if (rc) return rc;
   if ((rc = upload_scratch_bboxes(h, bboxes, nb))) return rc;
-  PointsArgs a{};
-  bbox_points_args(h, a);
-  launch_points(a, h->stream);
+  launch_points(bbox_points_args(h, h->det[2], 0, h->n, h->sb[h->last.points].bbox_id), h->stream);
   GV_HIP(hipGetLastError());
   if ((rc = read_back_ids(h, bbox_id))) return rc;
   GV_HIP(hipStreamSynchronize(h->stream));
-  h->have_bbox_id = true;
+  h->last.bbox_id = true;
   if (counts) {
     for (int32_t b = 0; b < nb; ++b) counts[b] = 0;
     for (size_t i = 0; i < h->n; ++i)
@@ -995,18 +1002,18 @@ int gv_footprint_cells(uint8_t grid_x, uint8_t grid_y, double resolution, const 
 int gv_get_hits(gv_handle h, int32_t *out)
 {
   if (!h || !out) return GV_ERR_BAD_ARG;
-  if (!h->have_hits) return GV_ERR_STATE;
-  return copy_out(h, out, h->hits, (size_t)h->g.G * sizeof(int32_t));
+  if (!h->last.hits) return GV_ERR_STATE;
+  return copy_out(h, out, h->sb[h->last.stream].hits, (size_t)h->g.G * sizeof(int32_t));
 }
 
 int gv_get_miss(gv_handle h, int32_t *out)
 {
   if (!h || !out) return GV_ERR_BAD_ARG;
-  if (!h->have_miss) return GV_ERR_STATE;
+  if (!h->last.miss) return GV_ERR_STATE;
   int rc = use_device(h);
   if (rc) return rc;
   if (sector_path(h))
-    launch_miss_to_i32(h->fs[h->last_set].freeN, h->fs[h->last_set].freeT, h->g.nx, h->g.ny, h->nx_pad, h->ny_pad,
+    launch_miss_to_i32(h->fs[h->last.set].freeN, h->fs[h->last.set].freeT, h->g.nx, h->g.ny, h->nx_pad, h->ny_pad,
                        h->scratch_i32, h->stream);
   else
     launch_u8_to_i32(h->miss8, h->scratch_i32, (size_t)h->g.G, h->stream);
@@ -1017,14 +1024,14 @@ int gv_get_miss(gv_handle h, int32_t *out)
 int gv_get_cell_idx(gv_handle h, int32_t *out)
 {
   if (!h || !out) return GV_ERR_BAD_ARG;
-  if (!h->have_cell_idx) return GV_ERR_STATE;
-  return copy_out(h, out, h->cell_idx, h->n * sizeof(int32_t));
+  if (!h->last.cell_idx) return GV_ERR_STATE;
+  return copy_out(h, out, h->sb[h->last.points].cell_idx, h->n * sizeof(int32_t));
 }
 
 int gv_get_bbox_id(gv_handle h, int32_t *out)
 {
   if (!h || !out) return GV_ERR_BAD_ARG;
-  if (!h->have_bbox_id) return GV_ERR_STATE;
+  if (!h->last.bbox_id) return GV_ERR_STATE;
   GV_TRY
   int rc = use_device(h);
   if (rc) return rc;
@@ -1036,11 +1043,12 @@ int gv_get_ray_stats(gv_handle h, uint64_t *n_rays, uint64_t *n_visits)
 {
   if (!h) return GV_ERR_BAD_ARG;
   GV_TRY
-  std::vector<unsigned long long> st(2 * h->stat_slots, 0ull);
-  int rc = copy_out(h, st.data(), h->fs[h->last_set].stats, st.size() * sizeof(unsigned long long));
+  const size_t slots = h->last.stat_slots;
+  std::vector<unsigned long long> st(2 * slots, 0ull);
+  int rc = copy_out(h, st.data(), h->fs[h->last.set].stats, st.size() * sizeof(unsigned long long));
   if (rc) return rc;
   unsigned long long rays = 0, visits = 0;
-  for (size_t i = 0; i < h->stat_slots; ++i) { rays += st[2 * i]; visits += st[2 * i + 1]; }
+  for (size_t i = 0; i < slots; ++i) { rays += st[2 * i]; visits += st[2 * i + 1]; }
   if (n_rays) *n_rays = rays;
   if (n_visits) *n_visits = visits;
   return GV_OK;

@@ -39,7 +39,7 @@ DetLayout det_layout(int32_t cap)
 int clear_counts(gv_context *h)
 {
   const size_t G = (size_t)h->g.G;
-  GV_HIP(hipMemsetAsync(h->hits, 0, G * sizeof(int32_t), h->stream));
+  GV_HIP(hipMemsetAsync(h->sb[0].hits, 0, G * sizeof(int32_t), h->stream));
   GV_HIP(hipMemsetAsync(h->miss8, 0, G, h->stream));
   GV_HIP(hipMemsetAsync(h->clip_end, 0, G, h->stream));
   h->counts_dirty = false;
@@ -78,8 +78,8 @@ int fill_sector_args(gv_context *h, SectorArgs &sa, int p)
       ++l2;
       est *= 0.5;
     }
-    if (h->env_log2s > 0) { l2 = h->env_log2s; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
-    if (h->env_log2s_oct[o] > 0) { l2 = h->env_log2s_oct[o]; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
+    if (h->tune.log2s > 0) { l2 = h->tune.log2s; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
+    if (h->tune.log2s_oct[o] > 0) { l2 = h->tune.log2s_oct[o]; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
     sa.log2s_oct[o] = (uint8_t)l2;
     est_max = std::max(est_max, est);
   }
@@ -100,29 +100,29 @@ int fill_sector_args(gv_context *h, SectorArgs &sa, int p)
       double up = 0.0, down = 0.0;
       for (int b = 0; b < 8; ++b) { up = std::max(up, load[b] + w[b]); down = std::max(down, load[b] + w[7 - b]); }
       bool rev = down < up;
-      if (h->env_sector_rev == 0) rev = false;
-      if (h->env_sector_rev == 1) rev = (r & 1) != 0;
+      if (h->tune.sector_rev == 0) rev = false;
+      if (h->tune.sector_rev == 1) rev = (r & 1) != 0;
       if (rev) mask |= (uint16_t)(1u << r);
       for (int b = 0; b < 8; ++b) load[b] += rev ? w[7 - b] : w[b];
     }
     sa.rev_oct[o] = mask;
   }
-  sa.cap = h->env_cap > 0 ? std::max(2048, h->env_cap) : ((est_max <= 1700.0 && h->env_log2s <= 0) ? 2048 : 4096);
+  sa.cap = h->tune.cap > 0 ? std::max(2048, h->tune.cap) : ((est_max <= 1700.0 && h->tune.log2s <= 0) ? 2048 : 4096);
   sa.ablate = 0;
   sa.dbg = nullptr;
 #ifdef GV_DIAG
-  sa.ablate = h->env_ablate;
+  sa.ablate = h->tune.ablate;
   sa.dbg = h->d_dbg;
   sa.tl = h->tl_slot(2);
 #endif
-  sa.flat_k = h->env_flat_k;
-  sa.march_limit = h->env_march_limit;
-  sa.flat_direct = h->env_flat_direct;
-  sa.log2m = h->env_log2m > 0 ? h->env_log2m : 9;
+  sa.flat_k = h->tune.flat_k;
+  sa.march_limit = h->tune.march_limit;
+  sa.flat_direct = h->tune.flat_direct;
+  sa.log2m = h->tune.log2m > 0 ? h->tune.log2m : 9;
   sa.marks_words = (imax + 3) & ~1;   // one word per wedge column, 0..imax
   std::stable_sort(ord, ord + 8, [&](int a, int b) { return len[a] > len[b]; });
   sa.oct_perm = 0;
-  sa.reorder = h->env_reorder;
+  sa.reorder = h->tune.reorder;
   uint32_t base = 0;
   for (int k = 0; k < 8; ++k) {
     sa.oct_perm |= (uint32_t)ord[k] << (3 * k);
@@ -131,7 +131,7 @@ int fill_sector_args(gv_context *h, SectorArgs &sa, int p)
   }
   // second workgroups for the axis / diagonal sectors of every octant once the wedges are long enough to have
   // heavy tails (GV_SECTOR_HELPERS=0 / 1 forces them off / on)
-  sa.n_helpers = (h->env_helpers >= 0) ? (h->env_helpers ? 16 : 0) : (imax >= 512 ? 16 : 0);
+  sa.n_helpers = (h->tune.helpers >= 0) ? (h->tune.helpers ? 16 : 0) : (imax >= 512 ? 16 : 0);
   if (base + 16 > kMaxStatSlots || base > 65535u) { h->err = "too many sector workgroups"; return GV_ERR_BAD_ARG; }
   sa.wg_base[8] = (uint16_t)base;
   sa.hitN = h->fs[p].hitN; sa.clipN = h->fs[p].clipN; sa.hitT = h->fs[p].hitT; sa.clipT = h->fs[p].clipT;
@@ -141,7 +141,7 @@ int fill_sector_args(gv_context *h, SectorArgs &sa, int p)
   sa.stats = h->fs[p].stats;
   sa.wg_first = 0;
   sa.wg_stride = 1;
-  h->stat_slots = (size_t)sa.wg_base[8] + (size_t)sa.n_helpers;
+  h->last.stat_slots = (size_t)sa.wg_base[8] + (size_t)sa.n_helpers;
   return GV_OK;
 }
 
@@ -155,8 +155,8 @@ namespace gv_internal __attribute__((visibility("hidden"))) {
 // the sharded frame): a slice may pick a smaller chunk than the whole cloud and then needs MORE table rows
 int ensure_point_buffers(gv_context *h, size_t n, size_t n_slice)
 {
-  const int nsets = sector_path(h) ? 1 + h->n_lanes : 1;   // per-stream copies
-  const bool need_idx = n > h->idx_cap || !h->cell_idx;
+  const int nsets = sector_path(h) ? 1 + h->tune.n_lanes : 1;   // per-stream copies
+  const bool need_idx = n > h->idx_cap || !h->idx_cap;
   size_t keys_need, tab_need;
   bin_needs(h, n, keys_need, tab_need);
   for (size_t m : {n_slice, n_slice ? n_slice - 1 : (size_t)0}) {   // slices are floor or ceil of n / world
@@ -174,13 +174,10 @@ int ensure_point_buffers(gv_context *h, size_t n, size_t n_slice)
   if (need_idx) {
     const size_t want = n + n / 8 + 1024;
     h->idx_cap = 0;
-    h->cell_idx = nullptr;
-    h->bbox_id = nullptr;
     for (int k = 0; k < nsets; ++k)
       if ((rc = h->sb[k].cell_idx.reserve(h, want)) || (rc = h->sb[k].bbox_id.reserve(h, want))) return rc;
-    h->cell_idx = h->sb[0].cell_idx;
-    h->bbox_id = h->sb[0].bbox_id;
-    h->have_cell_idx = h->have_bbox_id = false;
+    h->last.points = 0;   // new buffers: the standalone calls write stream 0's
+    h->last.cell_idx = h->last.bbox_id = false;
     h->idx_cap = want;
   }
   if (need_bin) {
@@ -239,7 +236,6 @@ int ensure_det_shared(gv_context *h, int32_t n)
     if ((rc = f.rects.reserve(h, (size_t)want))) return rc;
   for (StreamBufs &b : h->sb)
     if ((rc = b.vout.reserve(h, (size_t)want))) return rc;
-  h->d_vout = h->sb[0].vout;
   if ((rc = h->d_pts.reserve(h, (size_t)want * 3))) return rc;
   h->vout_cap = want;
   return GV_OK;
@@ -254,6 +250,46 @@ BBoxTest bbox_test_of(const gv_context *h, const DetSet &d)
   t.tiles_y = h->bt_tiles_y;
   t.mask_words = d.mask_words;
   return t;
+}
+
+// Arguments of the point kernel for the bbox test alone: points [lo, lo + n) of the resident cloud against detection
+// set D, ids to ids[0, n).  The generic frame fills in its binning and ray fields on top.
+PointsArgs bbox_points_args(const gv_context *h, const DetSet &D, size_t lo, size_t n, int16_t *ids)
+{
+  PointsArgs a{};
+  a.x = h->cx + lo; a.y = h->cy + lo; a.z = h->cz + lo;
+  a.n = (uint32_t)n;
+  a.g = h->g;
+  a.m_cam = h->m_cam;
+  a.cam = h->camk;
+  a.bt = bbox_test_of(h, D);
+  a.bbox_id = ids;
+  a.do_bbox = true;
+  return a;
+}
+
+// Every frame form ends here.  set / stream: whose free-cell bitmaps and statistics, whose count grid.  points: the
+// stream whose per-point outputs the flags cell_idx / bbox_id speak of.  The four flags: what the form produced.
+void set_last_frame(gv_context *h, int set, int stream, int points, bool hits, bool miss, bool cell_idx, bool bbox_id)
+{
+  h->last = LastFrame{set, stream, points, hits, miss, cell_idx, bbox_id, h->last.stat_slots};   // (the ray stage sets stat_slots)
+}
+
+// Who read what: the frame that completes ev_fin[slot] used buffer set p, cloud set CS and detection set D, the
+// latter on the streams in `readers`.  on_lane: it is in flight on a lane until the next drain; quiet: it counts
+// towards the frames without an upload that open the third lane (gv_context::lanes_now).
+void note_frame_readers(gv_context *h, int slot, int p, CloudSet &CS, DetSet &D, uint32_t readers, bool on_lane, bool quiet)
+{
+  h->last_fin_slot = slot;
+  h->fs[p].fin_slot = slot;
+  CS.release_slot = slot;
+  D.release_slot = slot;
+  D.readers |= readers;
+  h->frame_no++;
+  if (!on_lane) return;
+  h->lane_frames++;
+  h->pipe_busy = true;
+  if (quiet && h->quiet_frames < 0x7fffffffu) h->quiet_frames++;
 }
 
 // Upload the small per-frame arrays into detection set `d` on stream `s` and derive the bbox-test
@@ -400,18 +436,7 @@ int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, siz
   launch_bin_partition(a, s, timed ? h->kt[0][0] : nullptr, timed ? h->kt[0][1] : nullptr, any_order);
   h->sb[k].lane_clean = false;
   if (timed) h->kt_used[0] = n > 0 || fold_rects;
-  if (do_bbox && !bbox_fused) {
-    PointsArgs pa{};
-    pa.x = a.x; pa.y = a.y; pa.z = a.z;
-    pa.n = a.n;
-    pa.g = h->g;
-    pa.m_cam = h->m_cam;
-    pa.cam = h->camk;
-    pa.bt = a.bt;
-    pa.bbox_id = a.bbox_id;
-    pa.do_bbox = true;
-    launch_points(pa, s);
-  }
+  if (do_bbox && !bbox_fused) launch_points(bbox_points_args(h, D, lo, n, a.bbox_id), s);
   if (ev_points) GV_HIP(hipEventRecord(ev_points, s));
   BinTileArgs t{};
   t.nx = h->g.nx; t.ny = h->g.ny;
@@ -459,8 +484,10 @@ int enqueue_sectors(gv_context *h, int p, int first, int stride, hipStream_t s, 
   return GV_OK;
 }
 
+// The tile grid pass over rows [y0, y1) with the bitmaps of set p.  of_frame = false: a plain map update (diagnostic
+// build: the timeline stamps stay with the frames).
 int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, bool counts, int32_t y0, int32_t y1,
-                      hipStream_t s, hipEvent_t done, hipEvent_t t0, bool *launched, bool sharded)
+                      hipStream_t s, hipEvent_t done, hipEvent_t t0, bool *launched, bool sharded, bool of_frame)
 {
   // a sharded pass writes this rank's band whole and leaves the layers out of step (gv_context::layers_in_step)
   const bool dense = sharded || h->grid_pass_dense();
@@ -481,8 +508,9 @@ int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, 
   t.y_begin = y0;
   t.y_end = y1;
 #ifdef GV_DIAG
-  t.tl = h->tl_slot(3);
+  if (of_frame) t.tl = h->tl_slot(3);
 #endif
+  (void)of_frame;
   const bool ran = launch_finalize_tiles(t, s, done, t0);
   if (sharded) h->layers_in_step = false;
   else if (ran && dense && y0 <= 0 && y1 >= h->g.ny) h->layers_in_step = true;
@@ -516,7 +544,7 @@ namespace {
 
 // The tile-path frame: rectangles + partition, tile histogram + end bitmaps, sector ray stage back to
 // back on one in-order stream, then the grid pass on the public stream.  pipelined: the stream of lane
-// n % 2 and buffer set 1 + n % 4 (n = lane frames so far), the grid pass behind one event.  Serial
+// n % lanes and buffer set 1 + n % (2 * lanes) (n = lane frames so far), the grid pass behind one event.  Serial
 // (GV_PIPELINE=0, stage timing): everything on the public stream, buffer set 0.  The sharded frame has its own
 // enqueue (enqueue_frame_sharded).
 int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
@@ -527,7 +555,7 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
   const bool keep_cell = fl & GV_FRAME_KEEP_CELL_IDX;
   int rc = check_frame_flags(h, fl);
   if (rc) return rc;
-  const int p = pipelined ? 1 + (int)(h->lane_frames % (uint64_t)(2 * h->n_lanes)) : 0;
+  const int p = pipelined ? 1 + (int)(h->lane_frames % (uint64_t)(2 * h->tune.n_lanes)) : 0;
   const int k = pipelined ? 1 + (int)(h->lane_frames % (uint64_t)h->lanes_now()) : 0;
   hipStream_t s = h->streams[k];
   // back-pressure: the frame that last used this buffer set (four frames ago) has finished
@@ -559,7 +587,7 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
   const int32_t n_rects = fold_rects ? D.n_poses : enqueue_rects(h, D, rects, h->sb[k].vout, s);
   mark(s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageDetections + 1], s));
-  bool part_any_order = pipelined && !stage_events && h->env_anyorder && h->sb[k].lane_clean;
+  bool part_any_order = pipelined && !stage_events && h->tune.anyorder && h->sb[k].lane_clean;
 #ifdef GV_DIAG
   if (h->trace) part_any_order = false;   // the trace markers are packets on the lane
 #endif
@@ -573,29 +601,12 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
       return rc;
   } else {
     h->sb[k].lane_clean = false;
-    if (do_bbox) {
-      PointsArgs a{};
-      a.x = h->cx; a.y = h->cy; a.z = h->cz;
-      a.n = (uint32_t)h->n;
-      a.g = h->g;
-      a.m_cam = h->m_cam;
-      a.cam = h->camk;
-      a.bt = bbox_test_of(h, D);
-      a.bbox_id = h->sb[k].bbox_id;
-      a.do_bbox = true;
-      launch_points(a, s);
-    }
+    if (do_bbox) launch_points(bbox_points_args(h, D, 0, h->n, h->sb[k].bbox_id), s);
     if (stage_events) GV_HIP(hipEventRecord(h->ev[kStagePoints + 1], s));
   }
   mark(s);
   mark(s); mark(s);   // (trace slot of the former bitmap kernel: the tile pass is part of the binning pair)
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageRayCompact + 1], s));
-  h->last_set = p;
-  h->hits = h->sb[k].hits;
-  h->bbox_id = h->sb[k].bbox_id;
-  h->cell_idx = h->sb[k].cell_idx;
-  h->have_cell_idx = do_bin && keep_cell;
-  h->have_bbox_id = do_bbox;
 
   // --- free-space ray stage.  On a lane its completion event rides the kernel's own dispatch packet.
   const int slot = (int)(h->frame_no % (uint64_t)gv_context::kRing);
@@ -628,20 +639,11 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
   } else if ((rc = enqueue_grid_pass(h, p, rects, n_rects, do_bin, 0, h->g.ny, s, h->ev_fin[slot]))) return rc;
   mark(s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageFinalize + 1], s));
-  // cloud, detection set and buffer set remember their last user
-  h->last_fin_slot = slot;
-  h->fs[p].fin_slot = slot;
-  CS.release_slot = slot;
-  D.release_slot = slot;
-  D.readers |= 1u << k;
-  h->frame_no++;
-  if (pipelined) {
-    h->lane_frames++;
-    h->pipe_busy = true;
-    if (h->quiet_frames < 0x7fffffffu) h->quiet_frames++;
-  }
-  h->have_hits = do_bin;
-  h->have_miss = do_bin;   // the free-cell bitmaps of set p stay until the set's next frame
+  // cloud, detection set and buffer set remember their last user: this frame, which read D on its own stream only
+  note_frame_readers(h, slot, p, CS, D, 1u << k, pipelined, true);
+  // the tile pass writes every cell of hits[], and the free-cell bitmaps of set p stay until the set's next frame: a
+  // BIN frame has both whether or not it kept anything
+  set_last_frame(h, p, k, k, do_bin, do_bin, do_bin && keep_cell, do_bbox);
   return GV_OK;
 }
 
@@ -662,20 +664,14 @@ int enqueue_frame_generic(gv_context *h, bool stage_events)
   if (stage_events) GV_HIP(hipEventRecord(h->ev[0], s));
   const int32_t n_rects = enqueue_rects(h, D, h->fs[0].rects, h->sb[0].vout, s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageDetections + 1], s));
+  int32_t *const hits = h->sb[0].hits;
   if (do_bin || do_bbox) {
-    PointsArgs a{};
-    a.x = h->cx; a.y = h->cy; a.z = h->cz;
-    a.n = (uint32_t)h->n;
-    a.g = h->g;
+    PointsArgs a = bbox_points_args(h, D, 0, h->n, h->sb[0].bbox_id);
     a.m_base = h->m_base;
-    a.m_cam = h->m_cam;
-    a.cam = h->camk;
     a.org = h->org;
-    a.bt = bbox_test_of(h, D);
-    a.hits = h->hits;
+    a.hits = hits;
     a.clip_end = h->clip_end;
-    a.cell_idx = keep_cell ? h->cell_idx : nullptr;
-    a.bbox_id = h->bbox_id;
+    a.cell_idx = keep_cell ? h->sb[0].cell_idx.get() : nullptr;
     a.do_bin = do_bin; a.do_ray = do_ray; a.do_bbox = do_bbox;
     a.band = h->band;
     launch_points(a, s);
@@ -684,8 +680,8 @@ int enqueue_frame_generic(gv_context *h, bool stage_events)
   if (do_ray && h->org.valid) {
     GV_HIP(hipMemsetAsync(h->ray_count, 0, sizeof(uint32_t), s));
     GV_HIP(hipMemsetAsync(h->fs[0].stats, 0, 2 * sizeof(unsigned long long), s));
-    h->stat_slots = 1;
-    launch_ray_compact(h->hits, h->clip_end, h->g, h->ray_list, h->ray_count, s);
+    h->last.stat_slots = 1;
+    launch_ray_compact(hits, h->clip_end, h->g, h->ray_list, h->ray_count, s);
     if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageRayCompact + 1], s));
     launch_ray_march(h->ray_list, h->ray_count, h->g, h->org, h->miss8, h->fs[0].stats, s);
     if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageRayMarch + 1], s));
@@ -693,34 +689,20 @@ int enqueue_frame_generic(gv_context *h, bool stage_events)
     GV_HIP(hipEventRecord(h->ev[kStageRayCompact + 1], s));
     GV_HIP(hipEventRecord(h->ev[kStageRayMarch + 1], s));
   }
-  FinalizeArgs f{};
-  f.g = h->g;
-  f.log_odds = h->log_odds;
-  f.occupancy = h->occupancy;
-  f.occ_i8 = h->occ_i8;
-  f.rects = h->fs[0].rects;
-  f.n_rects = n_rects;
-  f.hits = do_bin ? h->hits : nullptr;
+  FinalizeArgs f = finalize_args(h, n_rects);
+  f.hits = do_bin ? hits : nullptr;
   f.miss = h->miss8;
   f.clip_end = h->clip_end;
   f.zero_counts = do_bin && !keep_counts;
-  f.cell_begin = 0;
-  f.cell_end = h->g.G;
   launch_finalize(f, s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageFinalize + 1], s));
   GV_HIP(hipGetLastError());
   const int slot = (int)(h->frame_no % (uint64_t)gv_context::kRing);
   GV_HIP(hipEventRecord(h->ev_fin[slot], s));   // cloud and detection set remember their last reader
-  h->last_fin_slot = slot;
-  CS.release_slot = slot;
-  D.release_slot = slot;
-  D.readers |= 1u;
-  h->frame_no++;
-  h->last_set = 0;
+  note_frame_readers(h, slot, 0, CS, D, 1u, false, false);   // everything on the public stream
   h->counts_dirty = do_bin && keep_counts;
-  h->have_hits = h->have_miss = do_bin && keep_counts;
-  h->have_cell_idx = do_bin && keep_cell;
-  h->have_bbox_id = do_bbox;
+  // the grid pass zeroes the count grids for the next frame unless the caller asked to keep them
+  set_last_frame(h, 0, 0, 0, do_bin && keep_counts, do_bin && keep_counts, do_bin && keep_cell, do_bbox);
   return GV_OK;
 }
 
@@ -769,12 +751,15 @@ int end_cloud_upload(gv_context *h, int target, size_t n)
   h->cx = c.x; h->cy = c.y; h->cz = c.z;
   h->n = n;
   h->cloud_wait = true;
-  h->have_cell_idx = h->have_bbox_id = false;
+  h->last.cell_idx = h->last.bbox_id = false;   // they spoke of the cloud before this one
   return GV_OK;
 }
 
+// the four upload entry points: argument checks, then the copies on the upload stream; wait: until they have landed
 int upload_xyz(gv_context *h, const float *x, const float *y, const float *z, size_t n, bool wait)
 {
+  if (!h || (n && (!x || !y || !z)) || n > 0x7fffffffu) return GV_ERR_BAD_ARG;
+  GV_TRY
   int target = 0;
   int rc = begin_cloud_upload(h, n, target);
   if (rc) return rc;
@@ -793,11 +778,16 @@ int upload_xyz(gv_context *h, const float *x, const float *y, const float *z, si
   if ((rc = end_cloud_upload(h, target, n))) return rc;
   if (wait) GV_HIP(hipEventSynchronize(c.ready));
   return GV_OK;
+  GV_CATCH
 }
 
 int upload_pc2(gv_context *h, const uint8_t *data, size_t n, uint32_t point_step, uint32_t off_x, uint32_t off_y,
                uint32_t off_z, bool wait)
 {
+  if (!h || (n && !data) || n > 0x7fffffffu) return GV_ERR_BAD_ARG;
+  if (point_step < 4 || off_x + 4 > point_step || off_y + 4 > point_step || off_z + 4 > point_step)
+    return GV_ERR_BAD_ARG;
+  GV_TRY
   int target = 0;
   int rc = begin_cloud_upload(h, n, target);
   if (rc) return rc;
@@ -815,11 +805,11 @@ int upload_pc2(gv_context *h, const uint8_t *data, size_t n, uint32_t point_step
   if ((rc = end_cloud_upload(h, target, n))) return rc;
   if (wait) GV_HIP(hipEventSynchronize(c.ready));
   return GV_OK;
+  GV_CATCH
 }
 
 int set_detections(gv_context *h, const gv_frame_desc *d)
 {
-  if (!h || !d) return GV_ERR_BAD_ARG;
   if (d->n_bboxes < 0 || d->n_poses < 0) return GV_ERR_BAD_ARG;
   if (d->n_bboxes && !d->bboxes) return GV_ERR_BAD_ARG;
   const bool vision = d->flags & GV_FRAME_VISION_ORIENT;
@@ -835,7 +825,7 @@ int set_detections(gv_context *h, const gv_frame_desc *d)
   // reader, which completes after every earlier frame.
   const int target = h->det_cur ^ 1;
   DetSet &D = h->det[target];
-  const int k = (sector_path(h) && !h->no_pipeline) ? 1 + (int)(h->lane_frames % (uint64_t)h->lanes_now()) : 0;
+  const int k = (sector_path(h) && !h->tune.no_pipeline) ? 1 + (int)(h->lane_frames % (uint64_t)h->lanes_now()) : 0;
   hipStream_t s = h->streams[k];
   h->sb[k].lane_clean = false;   // the upload and the table kernels go on this stream, in front of the frame's partition pass
   if (D.release_slot >= 0 && D.readers != (1u << k)) GV_HIP(hipStreamWaitEvent(s, h->ev_fin[D.release_slot], 0));
@@ -858,40 +848,24 @@ extern "C" {
 
 int gv_cloud_upload_xyz(gv_handle h, const float *x, const float *y, const float *z, size_t n)
 {
-  if (!h || (n && (!x || !y || !z)) || n > 0x7fffffffu) return GV_ERR_BAD_ARG;
-  GV_TRY
   return upload_xyz(h, x, y, z, n, true);
-  GV_CATCH
 }
 
 int gv_cloud_upload_xyz_async(gv_handle h, const float *x, const float *y, const float *z, size_t n)
 {
-  if (!h || (n && (!x || !y || !z)) || n > 0x7fffffffu) return GV_ERR_BAD_ARG;
-  GV_TRY
   return upload_xyz(h, x, y, z, n, false);
-  GV_CATCH
 }
 
 int gv_cloud_upload_pointcloud2(gv_handle h, const uint8_t *data, size_t n, uint32_t point_step, uint32_t off_x,
                                 uint32_t off_y, uint32_t off_z)
 {
-  if (!h || (n && !data) || n > 0x7fffffffu) return GV_ERR_BAD_ARG;
-  if (point_step < 4 || off_x + 4 > point_step || off_y + 4 > point_step || off_z + 4 > point_step)
-    return GV_ERR_BAD_ARG;
-  GV_TRY
   return upload_pc2(h, data, n, point_step, off_x, off_y, off_z, true);
-  GV_CATCH
 }
 
 int gv_cloud_upload_pointcloud2_async(gv_handle h, const uint8_t *data, size_t n, uint32_t point_step, uint32_t off_x,
                                       uint32_t off_y, uint32_t off_z)
 {
-  if (!h || (n && !data) || n > 0x7fffffffu) return GV_ERR_BAD_ARG;
-  if (point_step < 4 || off_x + 4 > point_step || off_y + 4 > point_step || off_z + 4 > point_step)
-    return GV_ERR_BAD_ARG;
-  GV_TRY
   return upload_pc2(h, data, n, point_step, off_x, off_y, off_z, false);
-  GV_CATCH
 }
 
 int gv_cloud_upload_wait(gv_handle h)
@@ -907,24 +881,21 @@ int gv_cloud_upload_wait(gv_handle h)
 
 int gv_frame_set_detections(gv_handle h, const gv_frame_desc *d)
 {
+  if (!h || !d) return GV_ERR_BAD_ARG;
   GV_TRY
   return set_detections(h, d);
   GV_CATCH
 }
 
-int gv_frame_set_detections_async(gv_handle h, const gv_frame_desc *d)
-{
-  GV_TRY
-  return set_detections(h, d);
-  GV_CATCH
-}
+// (the upload is asynchronous either way: the set's `ready` event orders the frames behind it)
+int gv_frame_set_detections_async(gv_handle h, const gv_frame_desc *d) { return gv_frame_set_detections(h, d); }
 
 int gv_frame_enqueue(gv_handle h)
 {
   if (!h) return GV_ERR_BAD_ARG;
   GV_TRY
   if (!h->det[h->det_cur].valid) return GV_ERR_STATE;   // no gv_frame_set_detections yet
-  if (sector_path(h) && !h->no_pipeline) {
+  if (sector_path(h) && !h->tune.no_pipeline) {
     int rc = set_device_only(h);
     if (rc) return rc;
     return enqueue_frame_tiles(h, true, false);

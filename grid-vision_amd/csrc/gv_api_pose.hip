@@ -32,10 +32,10 @@ int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, 
   DetSet &d = h->det[2];
   if ((rc = upload_det(h, d, bboxes, nb, nullptr, 0, orient, conf, dims, h->stream, false))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
-  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->d_vout, d.poses, nullptr, h->stream);
+  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, nullptr, h->stream);
   GV_HIP(hipGetLastError());
   std::vector<VisionOut> vo((size_t)nb);
-  GV_HIP(hipMemcpyAsync(vo.data(), h->d_vout, (size_t)nb * sizeof(VisionOut), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipMemcpyAsync(vo.data(), h->sb[0].vout, (size_t)nb * sizeof(VisionOut), hipMemcpyDeviceToHost, h->stream));
   GV_HIP(hipStreamSynchronize(h->stream));
   int32_t m = 0;
   for (int32_t i = 0; i < nb; ++i) {
@@ -61,7 +61,7 @@ int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, con
   GV_HIP(hipEventRecord(d.ready, h->stream));
   DevBuf<float> dsets;   // nb * 64 * (loc0, loc1, loc2, err), then nb winners
   if ((rc = dsets.reserve(h, (size_t)nb * 257))) return rc;
-  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->d_vout, d.poses, dsets, h->stream);
+  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, dsets, h->stream);
   GV_HIP(hipGetLastError());
   GV_HIP(hipMemcpyAsync(sets, dsets, (size_t)nb * 256 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   GV_HIP(hipMemcpyAsync(winner, dsets + (size_t)nb * 256, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -221,10 +221,10 @@ static int enqueue_bbox_pose(gv_context *h, int32_t nb, bool with_ground, float 
   // extractCloudPerBBox + RadiusOutlierRemoval(0.4, 10)  (cloud_detections.cpp:250-298, 150-154)
   const double radius = 0.4;
   launch_radius_filter(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, h->camk, bbox_test_of(h, h->det[2]), nb, with_ground, thr_f,
-                       h->d_rstate, h->bbox_id, h->d_cellcnt, h->d_cellpre, h->d_celloff,
+                       h->d_rstate, h->sb[h->last.points].bbox_id, h->d_cellcnt, h->d_cellpre, h->d_celloff,
                        h->d_celloff + n_buckets / 4096 + 2, h->d_nodes, h->d_keep, h->d_ticket_of, h->d_pca_acc, (uint32_t)n_buckets,
                        host::floor_to_float(radius * radius), 10, s);
-  h->have_bbox_id = true;
+  h->last.bbox_id = true;
   // centroid + PCA rectangle per bbox from order-independent integer sums over the kept points (:156-247)
   launch_pca_rect(h->d_nodes, h->d_celloff + n_buckets / 4096, (uint32_t)n, h->d_keep, h->d_pca_acc, h->d_pca_ext, h->d_pca_ticket, nb,
                   h->d_rstate, with_ground, reinterpret_cast<gv_lshape_pose *>(out), out + pose_block_valid_off(nb),
@@ -448,7 +448,7 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
     if ((rc = ensure_tbuf(h, std::max<size_t>(n, 1)))) return rc;
     if ((rc = h->knn_partial.reserve(h, knn_partial_entries(ns, k)))) return rc;
     hipStream_t sk = s;
-    if (h->env_tick_knn_lane && nd > 0) {
+    if (h->tune.tick_knn_lane && nd > 0) {
       sk = h->streams[1];
       GV_HIP(hipEventRecord(T.fork, s));
       GV_HIP(hipStreamWaitEvent(sk, T.fork, 0));
@@ -489,10 +489,8 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
     if ((rc = enqueue_binning(h, D, 0, 0, 0, n, false, lidar_ray, false, true, nullptr))) return rc;
     if (lidar_ray && (rc = enqueue_sectors(h, 0, 0, 1, s))) return rc;
     if ((rc = enqueue_grid_pass(h, 0, rects, n_rects, true, 0, h->g.ny, s))) return rc;
-    h->last_set = 0;
-    h->hits = h->sb[0].hits;
-    h->have_hits = true;
-    h->have_miss = true;
+    // a tick writes no per-point output: those of the call before it stay where they are
+    set_last_frame(h, 0, 0, h->last.points, true, true, h->last.cell_idx, h->last.bbox_id);
   } else if ((rc = enqueue_plain_update(h, n_rects)))
     return rc;
   // a copy command, not gv_publish_grid_async's kernel: no upload competes for the copy engines inside a tick, and the

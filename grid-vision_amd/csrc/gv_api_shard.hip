@@ -110,6 +110,9 @@ int enqueue_frame_sharded(gv_context *h, const Event *te)
   int rc = check_frame_flags(h, fl);
   if (rc) return rc;
   if (!do_bin || !h->comm || !h->stream_x) return GV_ERR_STATE;
+  // Its own rotation, not enqueue_frame_tiles': always lanes 0 / 1 and buffer sets 1..4, whatever GV_LANES says and
+  // however long the upload stream has been quiet.  The third lane is the upload stream (gv_context::lanes_now), which
+  // this form leaves to the uploads, and its back-pressure is four frames deep.
   const int p = 1 + (int)(h->lane_frames % 4u);
   const int k = 1 + (int)(h->lane_frames % 2u);
   hipStream_t s = h->streams[k], X = h->stream_x;
@@ -216,23 +219,13 @@ int enqueue_frame_sharded(gv_context *h, const Event *te)
   GV_HIP(hipEventRecord(h->ev_fin[slot], X));
   // what the frame produced (the gathered packed grid) is visible on the public stream right behind it
   GV_HIP(hipStreamWaitEvent(h->stream, h->ev_fin[slot], 0));
-  h->last_fin_slot = slot;
-  h->fs[p].fin_slot = slot;
-  CS.release_slot = slot;
-  D.release_slot = slot;
-  D.readers |= (1u << k) | 1u;
-  h->frame_no++;
-  h->lane_frames++;
-  h->pipe_busy = true;
-  h->last_set = p;
-  h->hits = h->sb[k].hits;
-  h->bbox_id = h->sb[k].bbox_id;
-  h->cell_idx = h->sb[k].cell_idx;
-  h->have_cell_idx = keep_cell;
-  h->have_bbox_id = do_bbox;
+  // D counts as read on the lane and on the public stream; a sharded frame never runs on the third lane and does not
+  // count towards the quiet frames that open it
+  note_frame_readers(h, slot, p, CS, D, (1u << k) | 1u, true, false);
   if (keep_counts) h->sb[k].sh_counts_slot = slot;
-  h->have_hits = keep_counts;   // band totals at this rank's band rows (gv_comm_band)
-  h->have_miss = false;         // free-cell bitmaps are complete for this rank's band only
+  // hits: band totals at this rank's band rows (gv_comm_band), only when kept (the tile pass writes hits[] only then);
+  // miss: never, the free-cell bitmaps are complete for this rank's band only
+  set_last_frame(h, p, k, k, keep_counts, false, keep_cell, do_bbox);
   return GV_OK;
 }
 
@@ -428,10 +421,9 @@ int gv_test_frame_sharded_emulated(gv_handle h, const gv_frame_desc *desc, int32
   if ((rc = use_device(h))) return rc;
   DetSet &D = h->det[h->det_cur];
   const uint32_t fl = D.flags;
-  const bool do_bin = fl & GV_FRAME_BIN, do_bbox = fl & GV_FRAME_BBOX_TEST;
-  const bool keep_cell = fl & GV_FRAME_KEEP_CELL_IDX;
+  const bool do_bbox = fl & GV_FRAME_BBOX_TEST, keep_cell = fl & GV_FRAME_KEEP_CELL_IDX;
   if ((rc = check_frame_flags(h, fl))) return rc;
-  if (!do_bin) return GV_ERR_STATE;
+  if (!(fl & GV_FRAME_BIN)) return GV_ERR_STATE;
   if ((rc = ensure_shard_scratch(h, world))) return rc;
   if ((rc = ensure_point_buffers(h, h->n, (h->n + (size_t)world - 1) / (size_t)world))) return rc;
   // every rank's end bitmaps and packed free bands, and the combined end bitmaps: gone with this call
@@ -439,14 +431,8 @@ int gv_test_frame_sharded_emulated(gv_handle h, const gv_frame_desc *desc, int32
   DevBuf<uint32_t> comb;
   rc = emulate_ranks(h, D, world, ends.data(), packs.data(), comb);
   (void)hipStreamSynchronize(h->stream);   // on every way out, before the temporaries go
-  h->last_set = 0;
-  h->hits = h->sb[0].hits;
-  h->bbox_id = h->sb[0].bbox_id;
-  h->cell_idx = h->sb[0].cell_idx;
-  h->have_hits = false;
-  h->have_miss = false;
-  h->have_cell_idx = do_bin && keep_cell;
-  h->have_bbox_id = do_bbox;
+  // no whole count grid (the slices are binned without hits[]) and, as on a rank of the sharded frame, no miss grid
+  set_last_frame(h, 0, 0, 0, false, false, keep_cell, do_bbox);
   return rc;
   GV_CATCH
 }

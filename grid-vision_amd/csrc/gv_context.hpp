@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <new>
@@ -89,6 +90,42 @@ struct StreamBufs {
   int sh_counts_slot = -1;      // ev_fin slot of the lane's last sharded KEEP_COUNTS frame (its x3 reduces hits in place)
 };
 
+// What the last frame left behind, for the getters and the standalone calls that go on from it.  Written in one place,
+// set_last_frame (gv_api_frame.hip), which every frame form calls at its end; ensure_point_buffers, end_cloud_upload,
+// gv_extract_cloud_per_bbox and enqueue_bbox_pose change single per-point flags.
+struct LastFrame {
+  int set = 0;                  // fs[set]: free-cell bitmaps (gv_get_miss) and ray statistics
+  int stream = 0;               // sb[stream].hits: the count grid
+  int points = 0;               // sb[points].cell_idx / .bbox_id: per-point outputs (a tick writes none: they stay where they were)
+  bool hits = false, miss = false, cell_idx = false, bbox_id = false;   // what the getters may read
+  size_t stat_slots = 1;        // ray statistics slots written by the last ray stage
+};
+
+// Experiment and sweep knobs: read from the environment by read_tuning (gv_api.hip), once, at gv_create.
+struct Tuning {
+  int n_lanes = 3;                  // GV_LANES=2: two lanes
+  bool lane3_own_stream = false;    // GV_LANE3_OWN_STREAM (experiment): the third lane on a fifth stream instead of the upload stream
+  bool queue_probe = true;          // GV_QUEUE_PROBE=0: no probe of the upload stream's hardware queue
+  bool verbose = false;             // GV_VERBOSE: the probe's result on stderr
+  bool no_pipeline = false;         // GV_PIPELINE=0
+  bool force_simple = false;        // GV_RAY_IMPL=simple
+  bool tick_knn_lane = true;        // GV_TICK_KNN_LANE=0: the static boxes' kNN in line on the public stream
+  bool grid_skip = true;            // GV_GRID_SKIP=0: every grid pass dense (A/B runs, tests)
+  bool anyorder = true;             // GV_ANYORDER=0: no any-order partition launches (StreamBufs::lane_clean)
+  int reorder = 1;                  // GV_SECTOR_REORDER=0: workgroups in natural (octant, sector) order
+  int helpers = -1;                 // GV_SECTOR_HELPERS: -1 automatic, 0 off, 1 on
+  int32_t sector_rev = -1;          // GV_SECTOR_REV (sweeps)
+  int32_t log2s_oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // GV_LOG2S_OCT="a,b,..." per octant index (sweeps)
+  uint32_t march_limit = 64u * 512u;   // GV_MARCH_LIMIT
+  uint32_t flat_direct = 2048;         // GV_FLAT_DIRECT
+  int32_t flat_k = 8;               // GV_FLAT_K: exact-cell : marched-cell cost ratio (0 = always march)
+  int32_t log2s = 0, cap = 0, log2m = 0;   // GV_LOG2S / GV_CAP / GV_LOG2M (sweeps)
+#ifdef GV_DIAG
+  int32_t ablate = 0;               // GV_ABLATE
+  bool bin_dbg = false, timeline = false, sector_dbg = false;   // GV_BIN_DBG / GV_TIMELINE / GV_SECTOR_DBG = 1: the stamp buffers exist
+#endif
+};
+
 }  // namespace gv_internal
 
 using namespace gv_internal;
@@ -114,7 +151,7 @@ struct __attribute__((visibility("hidden"))) gv_context {
   static constexpr int kStreams = 1 + kLanesMax;   // public + lanes
   static constexpr int kSets = 1 + 2 * kLanesMax;  // set 0: the serial frame; two sets per lane
   static constexpr int kRing = 8;   // event rings: one slot per frame, reused every 8 frames
-  int n_lanes = 3;
+  Tuning tune;
   int upload_stream_retries = 0;    // gv_create: upload streams replaced because they shared a hardware queue
   double upload_probe_us = 0.0;     // the last probe's wait
   // The third lane runs on the UPLOAD stream (public + two lanes + uploads are the four hardware queues a process
@@ -123,12 +160,15 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // upload for kQuietFrames frames.  With a cloud per frame the library runs on two lanes, as in round 2.
   static constexpr uint32_t kQuietFrames = 8;
   uint32_t quiet_frames = 0;        // frames enqueued since the last cloud upload
-  int lanes_now() const { return (n_lanes == 3 && quiet_frames >= kQuietFrames) ? 3 : 2; }
+  int lanes_now() const { return (tune.n_lanes == 3 && quiet_frames >= kQuietFrames) ? 3 : 2; }
   int device = 0;
   // (the streams come before every buffer and event: members go in reverse order, the streams last)
-  Stream stream, stream_copy, stream2, stream3, stream4;
+  Stream stream, stream_copy;       // public, uploads
+  Stream lane[kLanesMax];           // lane[2] exists only with GV_LANE3_OWN_STREAM
   Stream stream_x;                  // the exchanges of the sharded frame (created by gv_comm_init)
-  hipStream_t streams[kStreams]{};  // = {stream (public), stream2 (lane 0), stream3 (lane 1), stream4 (lane 2, GV_LANES=3)}
+  hipStream_t streams[kStreams]{};  // what the frame code indexes: {stream, lane[0], lane[1], lane[2] or else stream_copy}
+  // every stream the handle owns, in the order drain waits for them (null: not created)
+  std::array<hipStream_t, 3 + kLanesMax> own_streams() const { return {stream_copy, stream, lane[0], lane[1], lane[2], stream_x}; }
   Event ev_sec[kRing];              // lane: partition, tile pass, sector stage of frame (slot) done
   Event ev_fin[kRing];              // public stream: grid pass of frame (slot) done => that frame and every earlier one are done
   Event ev_join;                    // copy stream -> public stream (gv_frame_fence)
@@ -138,16 +178,13 @@ struct __attribute__((visibility("hidden"))) gv_context {
   StreamBufs sb[kStreams];        // per-stream buffers
   size_t ends_words = 0, bmN_words = 0, bmT_words = 0;
   DevBuf<uint8_t> miss8;          // generic path only: byte miss grid of the literal march
-  int last_set = 0;
+  LastFrame last;
   uint64_t frame_no = 0;
   bool pipe_busy = false;         // lane frames enqueued since the streams were last drained
-  bool no_pipeline = false;       // GV_PIPELINE=0
-  int32_t env_sector_rev = -1;    // GV_SECTOR_REV (sweeps)
 #ifdef GV_DIAG
   std::vector<Event> *trace = nullptr;        // timing events around every pipelined kernel (gv_debug_pipeline_trace)
   DevBuf<unsigned long long> d_dbg;           // GV_SECTOR_DBG=1: phase stamps of the sector kernel
   DevBuf<unsigned long long> d_bin_dbg[2];    // GV_BIN_DBG=1: phase stamps of the partition / tile kernels
-  int32_t env_ablate = 0;                     // GV_ABLATE
   DevBuf<unsigned long long> d_tl;            // GV_TIMELINE=1: {begin, end} of the four kernels of the last kTlFrames frames
   static constexpr uint64_t kTlFrames = 4096;
   unsigned long long *tl_slot(int kernel) const
@@ -179,8 +216,7 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // gv_set_log_odds drains every stream before it copies.  A caller that writes through gv_device_layers' pointers
   // puts the layers out of step without the handle knowing.
   bool layers_in_step = false;
-  bool env_grid_skip = true;      // GV_GRID_SKIP=0: every grid pass dense (A/B runs, tests)
-  bool grid_pass_dense() const { return !env_grid_skip || !layers_in_step; }
+  bool grid_pass_dense() const { return !tune.grid_skip || !layers_in_step; }
   // [EXTENSION] X3 ego motion (gv_grid_move): the current base frame in the frame the layers are registered in, and
   // the scratch copy of the three layers the resample gathers into (allocated by the first applied move)
   host::Se2 move_residue{0.0, 0.0, 0.0};
@@ -221,24 +257,13 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<gv_traj_score> d_scores;
     DevBuf<uint8_t> d_pose_cost;
   } traj;
-  // per-frame count grids
-  int32_t *hits = nullptr;                  // = sb[stream of the last frame].hits
+  // per-frame count grids (sb[k].hits; generic path: sb[0].hits)
   DevBuf<uint8_t> clip_end;                 // generic path only
   DevBuf<uint32_t> ray_list;
   DevBuf<uint32_t> ray_count;               // [0] = number of list entries
   DevBuf<int32_t> scratch_i32;              // G ints (miss read-back), also max(N) ints for id read-back
   int32_t nxw = 0, nyw = 0, nx_pad = 0, ny_pad = 0;
   bool tile_path = false;                   // nx % 4 == 0 and the grid fits the packed (a,b) fields
-  bool force_simple = false;                // GV_RAY_IMPL=simple
-  int env_reorder = 1;                      // GV_SECTOR_REORDER=0: workgroups in natural (octant, sector) order
-  int env_helpers = -1;                     // GV_SECTOR_HELPERS: -1 automatic, 0 off, 1 on
-  bool env_anyorder = true;                 // GV_ANYORDER=0: no any-order partition launches (StreamBufs::lane_clean)
-  size_t stat_slots = 1;                    // ray statistics slots written by the last frame
-  int32_t env_log2s_oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // GV_LOG2S_OCT="a,b,..." per octant index (sweeps)
-  uint32_t env_march_limit = 64u * 512u;     // GV_MARCH_LIMIT
-  uint32_t env_flat_direct = 2048;           // GV_FLAT_DIRECT
-  int32_t env_flat_k = 8;                   // GV_FLAT_K: exact-cell : marched-cell cost ratio (0 = always march)
-  int32_t env_log2s = 0, env_cap = 0, env_log2m = 0;     // GV_LOG2S / GV_CAP / GV_LOG2M (sweeps)
 
   // tile-path binning (gv_binning.hip): what every stream's scratch holds
   int32_t tiles_x = 0, tiles_y = 0, n_tiles = 0;
@@ -252,15 +277,12 @@ struct __attribute__((visibility("hidden"))) gv_context {
   float *cx = nullptr, *cy = nullptr, *cz = nullptr;   // = cloud[cloud_cur]
   size_t n = 0;
   DevBuf<float> tx, ty, tz;                 // transformed copy (A1 read-back)
-  int32_t *cell_idx = nullptr;              // = sb[stream of the last frame]
-  int16_t *bbox_id = nullptr;
-  size_t idx_cap = 0;
+  size_t idx_cap = 0;                       // per-point outputs (sb[k].cell_idx / .bbox_id) hold this many points
 
   // detections
   DetSet det[3];
   int det_cur = 0;
   int32_t bt_tiles_x = 1, bt_tiles_y = 1;   // 16x16-pixel tiles of the image
-  VisionOut *d_vout = nullptr;              // = sb[0].vout
   int32_t vout_cap = 0;                     // rectangles, vision outputs (all sets) and centre points
   DevBuf<double> d_pts;
   // kNN depth / PCA pose scratch
@@ -297,10 +319,8 @@ struct __attribute__((visibility("hidden"))) gv_context {
     Event done;                      // public stream: everything the tick enqueued has finished
     Event fork, join;                // the kNN depth on a lane beside the pose branch
   } tick;
-  bool env_tick_knn_lane = true;   // GV_TICK_KNN_LANE=0: the static boxes' kNN in line on the public stream
 
   bool counts_dirty = false;   // generic path: hits/miss/clip_end hold a kept frame
-  bool have_hits = false, have_miss = false, have_cell_idx = false, have_bbox_id = false;
 
   // multi-GPU (one large frame sharded by points)
   ncclComm *comm = nullptr;       // (ncclComm_t)
@@ -361,6 +381,7 @@ bool sector_path(const gv_context *h);
 int set_device_only(gv_context *h);
 int use_device(gv_context *h);
 int enqueue_plain_update(gv_context *h, int32_t n_rects);
+FinalizeArgs finalize_args(const gv_context *h, int32_t n_rects);
 int ensure_tbuf(gv_context *h, size_t n);
 int copy_out(gv_context *h, void *dst, const void *src, size_t bytes);
 void convert_pixels_host(const double Kinv[9], const Xform64 &x_bc, const gv_bbox *bboxes, const float *depths, int32_t nb,
@@ -370,6 +391,9 @@ int ensure_point_buffers(gv_context *h, size_t n, size_t n_slice = 0);
 int ensure_det(gv_context *h, DetSet &d, int32_t n);
 int ensure_det_shared(gv_context *h, int32_t n);
 BBoxTest bbox_test_of(const gv_context *h, const DetSet &d);
+PointsArgs bbox_points_args(const gv_context *h, const DetSet &D, size_t lo, size_t n, int16_t *ids);
+void set_last_frame(gv_context *h, int set, int stream, int points, bool hits, bool miss, bool cell_idx, bool bbox_id);
+void note_frame_readers(gv_context *h, int slot, int p, CloudSet &CS, DetSet &D, uint32_t readers, bool on_lane, bool quiet);
 int upload_det(gv_context *h, DetSet &d, const gv_bbox *bboxes, int32_t nb, const gv_lshape_pose *poses,
                int32_t n_poses, const float *orient, const float *conf, const float *dims, hipStream_t s, bool masks = true,
                int32_t n_net = -1, int32_t nb_test = -1, bool fused = false);
@@ -383,7 +407,7 @@ int enqueue_sectors(gv_context *h, int p, int first, int stride, hipStream_t s, 
                     bool *done_attached = nullptr, hipEvent_t t0 = nullptr);
 int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, bool counts, int32_t y0, int32_t y1,
                       hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr, bool *launched = nullptr,
-                      bool sharded = false);
+                      bool sharded = false, bool of_frame = true);
 int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k);
 // gv_api_shard.hip
 void comm_destroy(gv_context *h);
