@@ -75,38 +75,45 @@ template <bool RAY, bool BBOX, bool KEEPCELL>
 __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(BinArgs a)
 {
   extern __shared__ __align__(16) unsigned char smem[];
-  if (blockIdx.x >= a.n_wg) {
+  // Every field of the argument block is read where it is used (GV_KARG), the handful the whole kernel shares
+  // (chunk, n_tiles) once: a by-value field lives in scalar registers from the top of the kernel to its last use,
+  // and with the points loop in between those registers spill to vector lanes.
+  if (blockIdx.x >= GV_KARG(n_wg)) {
     // one extra workgroup: the frame's base-frame poses -> index rectangles for the grid pass (A8/A9,
     // src/occupancy_grid.cpp:79-90,147-172).  Rides this launch instead of costing one of its own.
-    for (int q = threadIdx.x; q < a.n_rect_poses; q += kPartThreads) a.rects_out[q] = rect_from_pose(a.g, a.rect_poses[q]);
+    const int nrp = GV_KARG(n_rect_poses);
+    const GridParams g = GV_KARG(g);
+    const gv_lshape_pose *poses = GV_KARG(rect_poses);
+    Rect *rects = GV_KARG(rects_out);
+    for (int q = threadIdx.x; q < nrp; q += kPartThreads) rects[q] = rect_from_pose(g, poses[q]);
     return;
   }
-  const int T = a.n_tiles;
+  const int T = GV_KARG(n_tiles);
+  const uint32_t chunk = GV_KARG(chunk);
   unsigned *staged = reinterpret_cast<unsigned *>(smem);                      // [chunk] tile << 16 | key
-  unsigned *hist = staged + a.chunk;                                          // [T] counts, then cursors
+  unsigned *hist = staged + chunk;                                            // [T] counts, then cursors
   unsigned short *sorted = reinterpret_cast<unsigned short *>(hist + T);      // [chunk] keys grouped by tile
   unsigned short *outl = sorted;                                              // outside-point list (dead before `sorted` is written)
   __shared__ unsigned s_wsum[kPartThreads / 64], s_nout;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t w = blockIdx.x;
-  const uint32_t base = w * a.chunk;
-  const uint32_t npts = min(a.chunk, a.n - base);
+  const uint32_t base = w * chunk;
+  const uint32_t npts = min(chunk, GV_KARG(n) - base);
   GV_STAMP(a.dbg, 0);
   GV_TL_BEGIN(a.tl);
   for (int t = tid; t < T; t += kPartThreads) hist[t] = 0;
   if (tid == 0) s_nout = 0;
   // bbox test: thresholds and tile candidate masks staged in LDS -- per point they are a chain of dependent
   // look-ups (mask word -> one threshold quadruple per candidate), an LDS latency each instead of a global one
-  BBoxTest lbt = a.bt;
+  const size_t bt_off = ((size_t)chunk * 4 + (size_t)T * 4 + (size_t)chunk * 2 + 15) & ~(size_t)15;
   if (BBOX) {
-    const size_t off = ((size_t)a.chunk * 4 + (size_t)T * 4 + (size_t)a.chunk * 2 + 15) & ~(size_t)15;
-    float4 *l_bbox = reinterpret_cast<float4 *>(smem + off);
-    unsigned long long *l_mask = reinterpret_cast<unsigned long long *>(smem + off + (size_t)a.nb_pad * 16);
-    const int nmask = a.bt.tiles_x * a.bt.tiles_y * a.bt.mask_words;
-    for (int q = tid; q < a.nb; q += kPartThreads) l_bbox[q] = a.bt.bbox_f[q];
-    for (int q = tid; q < nmask; q += kPartThreads) l_mask[q] = a.bt.tile_mask[q];
-    lbt.bbox_f = l_bbox;
-    lbt.tile_mask = l_mask;
+    const BBoxTest bt = GV_KARG(bt);
+    const int nb = GV_KARG(nb);
+    float4 *l_bbox = reinterpret_cast<float4 *>(smem + bt_off);
+    unsigned long long *l_mask = reinterpret_cast<unsigned long long *>(smem + bt_off + (size_t)GV_KARG(nb_pad) * 16);
+    const int nmask = bt.tiles_x * bt.tiles_y * bt.mask_words;
+    for (int q = tid; q < nb; q += kPartThreads) l_bbox[q] = bt.bbox_f[q];
+    for (int q = tid; q < nmask; q += kPartThreads) l_mask[q] = bt.tile_mask[q];
   }
   __syncthreads();
 
@@ -117,67 +124,85 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
   // phase are fetched once per step instead of once per point (chunk % (PP * kPartThreads) == 0).  The rare exact
   // divisions are taken by the whole wavefront when any of its PP * 64 quotients needs one.
   constexpr int PP = GV_PART_BATCH;
-  for (uint32_t k0 = tid; k0 < a.chunk; k0 += PP * kPartThreads) {
+  for (uint32_t k0 = tid; k0 < chunk; k0 += PP * kPartThreads) {
     float px[PP], py[PP], pz[PP];
-    bool live[PP];
+    {
+      const float *xs = GV_KARG(x), *ys = GV_KARG(y), *zs = GV_KARG(z);
 #pragma unroll
-    for (int u = 0; u < PP; ++u) {
-      const uint32_t k = k0 + (uint32_t)u * kPartThreads;
-      live[u] = k < npts;
-      const uint32_t i = base + (live[u] ? k : 0u);   // base < n: a valid address for the idle lanes of the last chunk
-      px[u] = a.x[i]; py[u] = a.y[i]; pz[u] = a.z[i];
+      for (int u = 0; u < PP; ++u) {
+        const uint32_t k = k0 + (uint32_t)u * kPartThreads;
+        const bool live = k < npts;
+        const uint32_t i = base + (live ? k : 0u);   // base < n: a valid address for the idle lanes of the last chunk
+        // an idle lane's point is NaN from here on: it fails the finite tests of both phases like a NaN of the cloud,
+        // so no phase carries a `live` mask (a scalar register pair per point) next to its own predicates
+        px[u] = live ? xs[i] : __builtin_nanf(""); py[u] = ys[i]; pz[u] = zs[i];
+      }
     }
+    // The predicates of a step are 64-bit lane masks, a scalar register pair each; PP points times a dozen of them,
+    // alive from one phase to the next, overflow the scalar file and spill to vector lanes (a VALU-class move per
+    // spill and per reload).  So only the masks a later loop cannot do without outlive the loop that computes them
+    // (three classes per point in the base phase, `ok` in the camera phase): a point outside the rectangle carries a
+    // cell quotient that fails the index test, the rare exact-division branches recompute their own conditions, and
+    // the stores recompute k < npts from a k0 the optimiser cannot match with the one above.
+    asm volatile("" : "+v"(k0));
     // ---- base frame: cell, tile, key
     {
       const Mat34f mb = GV_KARG(m_base);   // constants are fetched where they are used (gv_device.hpp, load_karg)
       const GridParams g = GV_KARG(g);
       const HeightBand hb = GV_KARG(band);
+      const bool rayv = RAY && GV_KARG(org).valid != 0;
+      const bool clears = rayv && hb.clears != 0;
       double dx[PP], dy[PP], qx[PP], qy[PP];
-      bool fin[PP], in0[PP], rx[PP], ry[PP], obs[PP], gnd[PP];
+      bool chit[PP], cend[PP], cout[PP];   // once inside is known: a hit, a ground ray end; when outside: a clipped end
       bool any_risky = false;
+      const int tiles_x = GV_KARG(tiles_x);
+      int32_t *cell_idx = KEEPCELL ? GV_KARG(cell_idx) : nullptr;
 #pragma unroll
       for (int u = 0; u < PP; ++u) {
         float bx, by, bz;
         xform34(mb, px[u], py[u], pz[u], bx, by, bz);
-        fin[u] = live[u] & isfinite(bx) & isfinite(by) & isfinite(bz);   // (bitwise: no short-circuit branches)
+        const bool fin = isfinite(bx) & isfinite(by) & isfinite(bz);   // (bitwise: no short-circuit branches)
         // X4 height band on the fp32 base-frame z: z_ground <= bz <= z_max is an obstacle, bz < z_ground a ground
         // return that ends a free-space ray when the band clears (band off: every finite point is an obstacle)
-        obs[u] = !(bz < hb.z_ground) & !(bz > hb.z_max);
-        gnd[u] = (bz < hb.z_ground) & (hb.clears != 0);
+        const bool gnd = bz < hb.z_ground;
+        chit[u] = fin & !gnd & !(bz > hb.z_max);
+        cend[u] = fin & gnd & clears;
+        cout[u] = (chit[u] & rayv) | cend[u];
         // get_index_fast (gv_device.hpp), flattened
         const double x = (double)bx, y = (double)by;
         const double tx = -((x - g.pos_x) - g.off_x);
         const double ty = -((y - g.pos_y) - g.off_y);
-        in0[u] = fin[u] & (tx >= 0.0) & (ty >= 0.0) & (tx < g.len_x) & (ty < g.len_y);
+        const bool in0 = fin & (tx >= 0.0) & (ty >= 0.0) & (tx < g.len_x) & (ty < g.len_y);
         dx[u] = (x - g.off_x) - g.pos_x;
         dy[u] = (y - g.off_y) - g.pos_y;
-        qx[u] = -dx[u] * g.inv_res;
-        qy[u] = -dy[u] * g.inv_res;
-        rx[u] = in0[u] & (fabs(qx[u] - rint(qx[u])) < 1e-6);
-        ry[u] = in0[u] & (fabs(qy[u] - rint(qy[u])) < 1e-6);
-        any_risky = any_risky | rx[u] | ry[u];
+        // a point outside the rectangle gets the quotient -1.5: cell -1, outside below, and not near an integer
+        qx[u] = in0 ? -dx[u] * g.inv_res : -1.5;
+        qy[u] = in0 ? -dy[u] * g.inv_res : -1.5;
+        any_risky = any_risky | (fabs(qx[u] - rint(qx[u])) < 1e-6) | (fabs(qy[u] - rint(qy[u])) < 1e-6);
       }
       if (__ballot(any_risky) != 0ull) {
+        const double res = load_karg<double>(offsetof(BinArgs, g) + offsetof(GridParams, res));
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
-          if (rx[u]) qx[u] = -(dx[u] / g.res);
-          if (ry[u]) qy[u] = -(dy[u] / g.res);
+          double lx = qx[u], ly = qy[u];
+          asm volatile("" : "+v"(lx), "+v"(ly));   // the same tests again, on values of their own
+          if (fabs(lx - rint(lx)) < 1e-6) qx[u] = -(dx[u] / res);
+          if (fabs(ly - rint(ly)) < 1e-6) qy[u] = -(dy[u] / res);
         }
       }
 #pragma unroll
       for (int u = 0; u < PP; ++u) {
         const uint32_t k = k0 + (uint32_t)u * kPartThreads;
-        const int jx = (int)(in0[u] ? qx[u] : 0.0);
-        const int jy = (int)(in0[u] ? qy[u] : 0.0);
-        const bool inside = in0[u] & (jx >= 0) & (jy >= 0) & (jx < g.nx) & (jy < g.ny);
-        const unsigned tile = (unsigned)((jy >> kBinTileLog) * a.tiles_x + (jx >> kBinTileLog));
+        const int jx = (int)qx[u];
+        const int jy = (int)qy[u];
+        const bool inside = (jx >= 0) & (jy >= 0) & (jx < g.nx) & (jy < g.ny);
+        const unsigned tile = (unsigned)((jy >> kBinTileLog) * tiles_x + (jx >> kBinTileLog));
         const unsigned key = (tile << 16) | (unsigned)(((jy & (kBinTile - 1)) << kBinTileLog) | (jx & (kBinTile - 1)));
         // in map: an obstacle is a hit key; a clearing ground return a ray end at its own cell, own cell included
         // (the clipped-end key kind).  Out of map: the clipped end of an obstacle or a clearing ground return.
-        const bool ray = RAY & fin[u] & (a.org.valid != 0);
-        const bool hit = inside & obs[u];
-        const bool gend = ray & inside & gnd[u];
-        const unsigned st = hit ? key : (gend ? (key | kKeyClip) : ((ray & !inside & (obs[u] | gnd[u])) ? kStagedOutside : kStagedNone));
+        const bool hit = inside & chit[u];
+        const bool gend = inside & cend[u];
+        const unsigned st = hit ? key : (gend ? (key | kKeyClip) : ((!inside & cout[u]) ? kStagedOutside : kStagedNone));
         if (hit | gend) atomicAdd(&hist[tile], 1u);
         staged[k] = st;
         if (RAY) {
@@ -192,39 +217,44 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
             if (o) outl[wbase + (unsigned)__popcll(bm & ((1ull << lane) - 1ull))] = (unsigned short)k;
           }
         }
-        if (KEEPCELL && live[u]) a.cell_idx[base + k] = inside ? jy * g.nx + jx : -1;
+        if (KEEPCELL && k < npts) cell_idx[base + k] = inside ? jy * g.nx + jx : -1;
       }
     }
     // ---- camera frame: index of the first bbox containing the projection (first_bbox, gv_device.hpp, flattened)
     if (BBOX) {
       const Mat34f mc = GV_KARG(m_cam);
       const CamK ck = GV_KARG(cam);
+      // thresholds and candidate masks: the copies staged in LDS above
+      const int bt_tiles_x = GV_KARG(bt).tiles_x, mask_words = GV_KARG(bt).mask_words;
+      const float4 *l_bbox = reinterpret_cast<const float4 *>(smem + bt_off);
+      const unsigned long long *l_mask = reinterpret_cast<const unsigned long long *>(smem + bt_off + (size_t)GV_KARG(nb_pad) * 16);
       float uu[PP], vv[PP];
       double n0[PP], n1[PP], zz[PP];
-      bool ok[PP], k0r[PP], k1r[PP];
+      bool ok[PP];
       bool any_risky = false;
 #pragma unroll
       for (int u = 0; u < PP; ++u) {
         float cx, cy, cz;
         xform34(mc, px[u], py[u], pz[u], cx, cy, cz);
-        ok[u] = live[u] & isfinite(cx) & isfinite(cy) & isfinite(cz) & !(cz <= 0.001f);   // :264
+        ok[u] = isfinite(cx) & isfinite(cy) & isfinite(cz) & !(cz <= 0.001f);   // :264
         const double X = (double)cx, Y = (double)cy, Z = (double)cz;
         zz[u] = ok[u] ? Z : 1.0;
         const double riz = rcp_newton(zz[u]);
         n0[u] = ck.k[0] * X + ck.k[2] * Z;   // K's zero and unit entries dropped: see first_bbox
         n1[u] = ck.k[4] * Y + ck.k[5] * Z;
         const double q0 = n0[u] * riz, q1 = n1[u] * riz;
-        k0r[u] = ok[u] & div_risky(q0);
-        k1r[u] = ok[u] & div_risky(q1);
-        any_risky = any_risky | k0r[u] | k1r[u];
+        any_risky = any_risky | (ok[u] & (div_risky(q0) | div_risky(q1)));
         uu[u] = (float)q0;
         vv[u] = (float)q1;
       }
       if (__ballot(any_risky) != 0ull) {
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
-          if (k0r[u]) uu[u] = (float)(n0[u] / zz[u]);
-          if (k1r[u]) vv[u] = (float)(n1[u] / zz[u]);
+          double lz = zz[u];
+          asm volatile("" : "+v"(lz));   // the same tests again, on values of their own
+          const double riz = rcp_newton(lz);
+          if (ok[u] & div_risky(n0[u] * riz)) uu[u] = (float)(n0[u] / zz[u]);
+          if (ok[u] & div_risky(n1[u] * riz)) vv[u] = (float)(n1[u] / zz[u]);
         }
       }
       int id[PP];
@@ -234,15 +264,15 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
       for (int u = 0; u < PP; ++u) {
         img[u] = ok[u] & !((uu[u] < 0) | (uu[u] >= (float)ck.W) | (vv[u] < 0) | (vv[u] >= (float)ck.H));   // :276
         const int tx = (int)(img[u] ? uu[u] : 0.0f) >> 4, ty = (int)(img[u] ? vv[u] : 0.0f) >> 4;
-        moff[u] = (unsigned)((ty * lbt.tiles_x + tx) * lbt.mask_words);
+        moff[u] = (unsigned)((ty * bt_tiles_x + tx) * mask_words);
         id[u] = -1;
       }
-      for (int wd = 0; wd < lbt.mask_words; ++wd) {   // :280-288 first match wins; one word = 64 boxes
+      for (int wd = 0; wd < mask_words; ++wd) {   // :280-288 first match wins; one word = 64 boxes
         unsigned long long m[PP];
         bool more = false;
 #pragma unroll
         for (int u = 0; u < PP; ++u) {
-          const unsigned long long mw = lbt.tile_mask[moff[u] + (unsigned)wd];
+          const unsigned long long mw = l_mask[moff[u] + (unsigned)wd];
           m[u] = (img[u] & (id[u] < 0)) ? mw : 0ull;
           more = more | (m[u] != 0ull);
         }
@@ -252,7 +282,7 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
           for (int u = 0; u < PP; ++u) {
             const bool have = m[u] != 0ull;
             const int b = have ? wd * 64 + (__ffsll((long long)m[u]) - 1) : 0;
-            const float4 f = lbt.bbox_f[b];
+            const float4 f = l_bbox[b];
             const bool hit = have & (uu[u] >= f.x) & (uu[u] <= f.z) & (vv[u] >= f.y) & (vv[u] <= f.w);
             id[u] = hit ? b : id[u];
             m[u] = hit ? 0ull : (m[u] & (m[u] - 1ull));
@@ -260,10 +290,11 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
           }
         }
       }
+      int16_t *bbox_id = GV_KARG(bbox_id);
 #pragma unroll
       for (int u = 0; u < PP; ++u) {
         const uint32_t k = k0 + (uint32_t)u * kPartThreads;
-        if (live[u]) __builtin_nontemporal_store((int16_t)id[u], &a.bbox_id[base + k]);   // host-read output
+        if (k < npts) __builtin_nontemporal_store((int16_t)id[u], &bbox_id[base + k]);   // host-read output
       }
     }
   }
@@ -276,10 +307,10 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
       const unsigned k = outl[j];
       const uint32_t i = base + k;
       float bx, by, bz;
-      xform34(a.m_base, a.x[i], a.y[i], a.z[i], bx, by, bz);
+      xform34(GV_KARG(m_base), GV_KARG(x)[i], GV_KARG(y)[i], GV_KARG(z)[i], bx, by, bz);
       int ex, ey;
-      clip_ray_end(a.g, a.org, (double)bx, (double)by, ex, ey);
-      const unsigned tile = (unsigned)((ey >> kBinTileLog) * a.tiles_x + (ex >> kBinTileLog));
+      clip_ray_end(GV_KARG(g), GV_KARG(org), (double)bx, (double)by, ex, ey);
+      const unsigned tile = (unsigned)((ey >> kBinTileLog) * GV_KARG(tiles_x) + (ex >> kBinTileLog));
       staged[k] = (tile << 16) | kKeyClip | (unsigned)(((ey & (kBinTile - 1)) << kBinTileLog) | (ex & (kBinTile - 1)));
       atomicAdd(&hist[tile], 1u);
     }
@@ -302,19 +333,20 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
     if (wv < wave) run += s;
     total += s;
   }
-  unsigned short *row = a.tab + (size_t)w * (size_t)(T + 1);
+  unsigned short *row = GV_KARG(tab) + (size_t)w * (size_t)(T + 1);
+  uint32_t *tile_total = GV_KARG(tile_total);
   for (int t = t0; t < t1; ++t) {
     const unsigned c = hist[t];
     row[t] = (unsigned short)run;
     hist[t] = run;   // placement cursor
-    if (c) atomicAdd(&a.tile_total[t], c);   // no-return; 256 B contiguous per wavefront when per == 1
+    if (c) atomicAdd(&tile_total[t], c);   // no-return; 256 B contiguous per wavefront when per == 1
     run += c;
   }
   if (tid == 0) row[T] = (unsigned short)total;
   __syncthreads();
   GV_STAMP(a.dbg, 3);   // scan + table row
 
-  for (uint32_t k = tid; k < a.chunk; k += kPartThreads) {
+  for (uint32_t k = tid; k < chunk; k += kPartThreads) {
     const unsigned st = staged[k];
     if (st < kStagedOutside) sorted[atomicAdd(&hist[st >> 16], 1u)] = (unsigned short)(st & 0xFFFFu);
   }
@@ -322,7 +354,7 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
   GV_STAMP(a.dbg, 4);   // sorted in LDS
   // one contiguous run per workgroup (base of the chunk's key region is 4-byte aligned: chunk is even)
   const unsigned *src = reinterpret_cast<const unsigned *>(sorted);
-  unsigned *dst = reinterpret_cast<unsigned *>(a.keys + (size_t)w * a.chunk);
+  unsigned *dst = reinterpret_cast<unsigned *>(GV_KARG(keys) + (size_t)w * chunk);
   for (unsigned j = tid; j < (total + 1) / 2; j += kPartThreads) dst[j] = src[j];
   GV_STAMP(a.dbg, 5);
   GV_TL_END(a.tl);
