@@ -107,6 +107,18 @@ int copy_out(gv_context *h, void *dst, const void *src, size_t bytes)
   return GV_OK;
 }
 
+// the device's view of `p` when it is pinned host memory aligned to `align` bytes, else null (the copy command then)
+void *pinned_device_view(void *p, size_t align)
+{
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer ||
+      (reinterpret_cast<uintptr_t>(at.devicePointer) & (align - 1)) != 0) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return at.devicePointer;
+}
+
 // convertPixelsTo3D (grid_vision_node.cpp:309-335): B points, fp64, on the host, with the given K^-1 and camera->base
 // transform (the tick's wait passes the transform it was enqueued with)
 void convert_pixels_host(const double Kinv[9], const Xform64 &x_bc, const gv_bbox *bboxes, const float *depths, int32_t nb,
@@ -172,6 +184,7 @@ void read_tuning(Tuning &t)
   if (num("GV_MARCH_LIMIT", v)) t.march_limit = (uint32_t)std::max(0, v);
   if (num("GV_LOG2M", v)) t.log2m = std::min(9, std::max(4, v));
   num("GV_SECTOR_REV", t.sector_rev);
+  if (num("GV_NAV_PASS_CAP", v)) t.nav_pass_cap = std::max(1, v);
 #ifdef GV_DIAG
   num("GV_ABLATE", t.ablate);
   if (num("GV_BIN_DBG", v)) t.bin_dbg = v > 0;
@@ -422,6 +435,7 @@ int gv_reset(gv_handle h)
   h->move_residue = host::Se2{0.0, 0.0, 0.0};
   h->layers_in_step = true;   // 0.0 / 0.5 / 50: what the grid pass derives from the prior
   h->infl.have_cost = h->infl.have_dist2 = false;   // the costmap was a snapshot of the grid that is gone
+  h->nav.have_field = false;                        // ... and so was the distance field over it
   return GV_OK;
   GV_CATCH
 }
@@ -901,18 +915,6 @@ int gv_set_footprint(gv_handle h, const gv_footprint *fp)
   for (int32_t i = fp->n_vertices; i < host::kFootprintMaxVertices; ++i) h->traj.fp.vx[i] = h->traj.fp.vy[i] = 0.0;
   h->traj.set = true;
   return GV_OK;
-}
-
-// the device's view of `p` when it is pinned host memory aligned to `align` bytes, else null (the copy command then)
-static void *pinned_device_view(void *p, size_t align)
-{
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer ||
-      (reinterpret_cast<uintptr_t>(at.devicePointer) & (align - 1)) != 0) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  return at.devicePointer;
 }
 
 // A copy of the poses (host poses only), one kernel, and a copy per result the kernel cannot write in place, all on

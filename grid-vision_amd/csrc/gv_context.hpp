@@ -115,6 +115,7 @@ struct Tuning {
   int reorder = 1;                  // GV_SECTOR_REORDER=0: workgroups in natural (octant, sector) order
   int helpers = -1;                 // GV_SECTOR_HELPERS: -1 automatic, 0 off, 1 on
   int32_t sector_rev = -1;          // GV_SECTOR_REV (sweeps)
+  int32_t nav_pass_cap = kNavPassCap;   // GV_NAV_PASS_CAP: passes of a tile per round of gv_nav_field (tests: the cap's own path)
   int32_t log2s_oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // GV_LOG2S_OCT="a,b,..." per octant index (sweeps)
   uint32_t march_limit = 64u * 512u;   // GV_MARCH_LIMIT
   uint32_t flat_direct = 2048;         // GV_FLAT_DIRECT
@@ -257,6 +258,24 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<gv_traj_score> d_scores;
     DevBuf<uint8_t> d_pose_cost;
   } traj;
+  // [EXTENSION] X9 goal / path distance field (gv_set_nav_config / gv_nav_field / gv_score_nav*).  The configuration is
+  // handle state; the buffers are made by the first call that needs them.  gv_nav_field is the one call here that waits
+  // on the host between its launches (rounds until one changes nothing), so its staging block is never in flight when
+  // the next call fills it.  The sampler's buffers follow TrajScore's rules.
+  struct NavField {
+    static constexpr int kBatchMax = 64;    // rounds enqueued between two host waits, at most
+    bool set = false;
+    gv_nav_config cfg{};
+    DevBuf<uint32_t> field;                 // G rounded up to a multiple of 4
+    bool have_field = false;                // a gv_nav_field since gv_create / gv_reset
+    DevBuf<uint32_t> flags;                 // [2][tiles]: this round's and the next round's active tiles
+    DevBuf<uint32_t> counters;              // [0] seeds used, [1 + i] tiles changed by round i of the batch
+    DevBuf<int32_t> d_seeds;
+    PinnedBuf stage;                        // the counters' landing place, then the seed cells on their way in
+    Event done;                             // public stream: a batch's counters have landed
+    DevBuf<float> d_poses;                  // the sampler: device copy of host poses
+    DevBuf<gv_nav_score> d_scores;          // ... and the landing place of records bound for pageable memory
+  } nav;
   // per-frame count grids (sb[k].hits; generic path: sb[0].hits)
   DevBuf<uint8_t> clip_end;                 // generic path only
   DevBuf<uint32_t> ray_list;
@@ -386,6 +405,7 @@ int ensure_tbuf(gv_context *h, size_t n);
 int copy_out(gv_context *h, void *dst, const void *src, size_t bytes);
 void convert_pixels_host(const double Kinv[9], const Xform64 &x_bc, const gv_bbox *bboxes, const float *depths, int32_t nb,
                          double *base_points_xyz);
+void *pinned_device_view(void *p, size_t align);
 // gv_api_frame.hip
 int ensure_point_buffers(gv_context *h, size_t n, size_t n_slice = 0);
 int ensure_det(gv_context *h, DetSet &d, int32_t n);

@@ -294,6 +294,34 @@ inline bool footprint_cells(const GridParams &g, const gv_footprint &f, float x,
   return true;
 }
 
+// ---- [EXTENSION] X9 goal / path distance field (gv_nav_field) ----
+// what gv_nav_step_table accepts; gv_set_nav_config adds nav_config_fits
+inline bool nav_config_valid(const gv_nav_config &c)
+{
+  return c.obstacle_cost >= 1 && c.obstacle_cost <= 255 && c.cost_weight >= 0 && c.cost_weight <= 255 && c.flags == 0;
+}
+
+// the longest simple path, G - 1 cells entered at the largest step, stays below the two sentinels
+inline bool nav_config_fits(const gv_nav_config &c, int32_t G)
+{
+  const uint64_t max_step = 1u + (uint64_t)c.cost_weight * (uint64_t)(c.obstacle_cost - 1);
+  return max_step * (uint64_t)(G - 1) <= 0xFFFFFFFDull;
+}
+
+inline void nav_step_table(const gv_nav_config &c, uint32_t table[256])
+{
+  const NavStep s{c.obstacle_cost, c.cost_weight};
+  for (uint32_t v = 0; v < 256; ++v) table[v] = nav_step(s, v);
+}
+
+// the field entry (OccupancyGrid.data order) of a seed, through the grid's own getIndex; -1 off the map or non-finite
+inline int32_t nav_seed_entry(const GridParams &g, float x, float y)
+{
+  int ix = 0, iy = 0;
+  if (!get_index(g, (double)x, (double)y, ix, iy)) return -1;
+  return g.G - 1 - (iy * g.nx + ix);
+}
+
 // ---- [EXTENSION] ego-motion compensation (gv_grid_move) ----
 // Planar rigid motion (yaw, x, y) in fp64.
 struct Se2 {

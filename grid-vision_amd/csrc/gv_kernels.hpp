@@ -137,6 +137,34 @@ struct TrajArgs {
   uint8_t *pose_cost;           // K * P, or null
 };
 void launch_score_trajectories(const TrajArgs &a, hipStream_t s);
+// [EXTENSION] X9 goal / path distance field (gv_navfield.hip).  Everything is in OccupancyGrid.data order, as in X6.
+// The field is relaxed tile by tile (kNavTile x kNavTile cells, one workgroup each) in rounds, one launch per round;
+// flags_in[t] != 0: tile t has something to do this round (cleared by the tile), flags_out: the next round's.
+constexpr int32_t kNavTile = 64;
+constexpr int32_t kNavPassCap = 40;   // passes of a tile per round (gv_navfield.hip says where it comes from)
+struct NavArgs {
+  int32_t nx, ny, G;
+  int32_t tiles_x, tiles_y;
+  NavStep step;
+  int32_t pass_cap;
+  const uint8_t *cost;          // G (+ the costmap buffer's 16 bytes of slack)
+  uint32_t *field;              // G rounded up to a multiple of 4
+  const int32_t *seeds;         // n_seeds entries of the field (device)
+  int32_t n_seeds;
+  uint32_t *flags_in, *flags_out;   // tiles_x * tiles_y each
+  uint32_t *counter;            // seeds: seeds used; a round: tiles that changed
+};
+void launch_nav_init(const NavArgs &a, hipStream_t s);    // BLOCKED / UNREACHABLE from the cost byte
+void launch_nav_seeds(const NavArgs &a, hipStream_t s);   // 0 at the seeds, their tiles into flags_out
+void launch_nav_relax(const NavArgs &a, hipStream_t s);   // one round
+struct NavScoreArgs {
+  GridParams g;
+  const float *poses;           // K * P * 3 (device)
+  int32_t K, P;
+  const uint32_t *field;        // G
+  gv_nav_score *scores;         // K records (device memory, or the device view of pinned host memory; 8-byte aligned)
+};
+void launch_score_nav(const NavScoreArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

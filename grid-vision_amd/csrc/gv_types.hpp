@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/gridvision_hip.h"
+#include "gv_line.hpp"   // GV_HD
 
 namespace gv {
 
@@ -50,6 +51,16 @@ struct HeightBand {
   float z_ground, z_max;
   int32_t clears;
 };
+
+// [EXTENSION] X9 distance field (gv_set_nav_config): what entering a cell of cost byte v costs, 0 for a blocked cell.
+// The one text of the definition: gv_nav_step_table on the host, the kernels of gv_navfield.hip on the device.
+struct NavStep {
+  int32_t obstacle_cost, cost_weight;
+};
+GV_HD uint32_t nav_step(NavStep s, uint32_t v)
+{
+  return (int32_t)v >= s.obstacle_cost ? 0u : 1u + (uint32_t)s.cost_weight * v;
+}
 
 // Inclusive index rectangle of one object (updateGridCellsFast block).
 struct Rect {

@@ -38,6 +38,11 @@ TRAJ_DEVICE_POSES = 1 << 1
 TRAJ_SCORE_DTYPE = np.dtype([("max_cost", np.int32), ("first_collision", np.int32), ("cost_sum", np.uint32),
                              ("n_off_map", np.int32)])   # gv_traj_score
 
+NAV_BLOCKED = 0xFFFFFFFF
+NAV_UNREACHABLE = 0xFFFFFFFE
+NAV_SCORE_DTYPE = np.dtype([("sum", np.uint64), ("last", np.uint32), ("best", np.uint32), ("best_pose", np.int32),
+                            ("n_bad", np.int32)])   # gv_nav_score
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -62,6 +67,8 @@ ABI_SYMBOLS = [
     "gv_inflation_cost_table", "gv_set_inflation", "gv_inflate", "gv_get_costmap", "gv_get_obstacle_dist2",
     "gv_publish_costmap_async",
     "gv_set_footprint", "gv_score_trajectories_async", "gv_score_trajectories", "gv_footprint_cells",
+    "gv_nav_step_table", "gv_set_nav_config", "gv_nav_field", "gv_get_nav_field", "gv_device_nav_field",
+    "gv_score_nav_async", "gv_score_nav",
 ]
 
 
@@ -112,6 +119,17 @@ class Footprint(C.Structure):
             f.vx[i], f.vy[i] = float(x), float(y)
         f.collision_cost, f.off_map_cost, f.flags = int(collision_cost), int(off_map_cost), int(flags)
         return f
+
+
+class NavConfig(C.Structure):
+    """gv_nav_config: a cell of cost >= obstacle_cost is blocked, entering a traversable cell of cost v costs
+    1 + cost_weight * v"""
+    _fields_ = [("obstacle_cost", C.c_int32), ("cost_weight", C.c_int32), ("flags", C.c_uint32)]
+
+
+class NavInfo(C.Structure):
+    """gv_nav_info: what one gv_nav_field did"""
+    _fields_ = [("n_seeds_used", C.c_int32), ("rounds", C.c_int32)]
 
 
 class FrameDesc(C.Structure):
@@ -255,6 +273,15 @@ def footprint_cells(grid_x, grid_y, resolution, footprint, x, y, yaw):
             break
         cells = np.zeros(n.value, np.int32)
     raise GVError(rc, "gv_footprint_cells")
+
+
+def nav_step_table(cfg):
+    """the uint32 step table (256 entries, 0 = blocked) a NavConfig gives (host only; needs no GPU)"""
+    table = np.zeros(256, np.uint32)
+    rc = load().gv_nav_step_table(C.byref(cfg), _ptr(table))
+    if rc:
+        raise GVError(rc, "gv_nav_step_table")
+    return table
 
 
 def shard_slice_words(words, world):
@@ -604,6 +631,58 @@ class GridVisionHIP:
         self._ck(self._lib.gv_score_trajectories(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores),
                                                  _ptr(pc)), "gv_score_trajectories")
         return (scores, pc.reshape(K, P)) if keep_pose_cost else scores
+
+    # ---- [EXTENSION] goal / path distance field over the resident costmap
+    def set_nav_config(self, obstacle_cost=253, cost_weight=0):
+        """the configuration of the nav_field() calls that follow: a NavConfig, or its two fields; set_nav_config(None)
+        turns it off"""
+        if obstacle_cost is None:
+            self._ck(self._lib.gv_set_nav_config(self._h, None), "gv_set_nav_config")
+            return
+        cfg = obstacle_cost if isinstance(obstacle_cost, NavConfig) else NavConfig(int(obstacle_cost), int(cost_weight), 0)
+        self._ck(self._lib.gv_set_nav_config(self._h, C.byref(cfg)), "gv_set_nav_config")
+
+    def nav_field(self, seeds_xy):
+        """the distance field from seeds (S, 2) float32 in the grid's frame over the costmap of the last inflate(); waits
+        until the field is complete on the device.  Returns dict(n_seeds_used, rounds)."""
+        s = _f32(seeds_xy).reshape(-1, 2)
+        info = NavInfo()
+        self._ck(self._lib.gv_nav_field(self._h, _ptr(s), C.c_int32(len(s)), C.byref(info)), "gv_nav_field")
+        return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
+
+    def nav_field_array(self):
+        """the field of the last nav_field(): uint32 (G,) in OccupancyGrid.data order"""
+        out = np.empty(self.G, np.uint32)
+        self._ck(self._lib.gv_get_nav_field(self._h, _ptr(out)), "gv_get_nav_field")
+        return out
+
+    def device_nav_field(self):
+        """the device address of the field's G uint32 values (read-only)"""
+        p = C.c_void_p()
+        self._ck(self._lib.gv_device_nav_field(self._h, C.byref(p)), "gv_device_nav_field")
+        return p.value
+
+    def score_nav_async(self, poses, K, P, scores, device_ptr=None):
+        """enqueue on stream(): poses as in score_trajectories_async, scores a NAV_SCORE_DTYPE array of K; complete
+        after synchronize()"""
+        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(poses)
+        self._ck(self._lib.gv_score_nav_async(self._h, src, C.c_int32(K), C.c_int32(P),
+                                              C.c_uint32(TRAJ_DEVICE_POSES if device_ptr is not None else 0), _ptr(scores)),
+                 "gv_score_nav_async")
+
+    def score_nav(self, poses, device_ptr=None):
+        """poses: float32 (K, P, 3) as in score_trajectories (the yaw is never read).  Returns the NAV_SCORE_DTYPE array
+        of K."""
+        shape = np.shape(poses)
+        assert len(shape) == 3 and shape[2] == 3, "poses is (K, P, 3)"
+        K, P = int(shape[0]), int(shape[1])
+        p = _f32(poses) if device_ptr is None else None
+        scores = np.zeros(K, NAV_SCORE_DTYPE)
+        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(p)
+        self._ck(self._lib.gv_score_nav(self._h, src, C.c_int32(K), C.c_int32(P),
+                                        C.c_uint32(TRAJ_DEVICE_POSES if device_ptr is not None else 0), _ptr(scores)),
+                 "gv_score_nav")
+        return scores
 
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):

@@ -239,6 +239,33 @@ public:
                                     pose_cost ? pose_cost->data() : nullptr), ctx_.handle(), "gv_score_trajectories");
     return scores;
   }
+  // [EXTENSION] X9 goal / path distance field over the costmap of the last inflate(): configure once, solve from goal
+  // or path seeds (seeds_xy[S * 2] in the grid's frame; waits until the field is complete on the device), then sample
+  // it along the same poses scoreTrajectories takes.  navField() reads the G values back.
+  void setNavConfig(const gv_nav_config &cfg) { gv::check(gv_set_nav_config(ctx_.handle(), &cfg), ctx_.handle(), "gv_set_nav_config"); }
+  void clearNavConfig() { gv::check(gv_set_nav_config(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_nav_config"); }
+  gv_nav_info solveNavField(const std::vector<float> &seeds_xy)
+  {
+    gv_nav_info info{};
+    gv::check(gv_nav_field(ctx_.handle(), seeds_xy.data(), (int32_t)(seeds_xy.size() / 2), &info), ctx_.handle(), "gv_nav_field");
+    return info;
+  }
+  std::vector<uint32_t> navField()
+  {
+    int32_t nx = 0, ny = 0;
+    gv::check(gv_grid_geometry(ctx_.handle(), &nx, &ny, nullptr, nullptr), ctx_.handle(), "gv_grid_geometry");
+    std::vector<uint32_t> out((size_t)nx * (size_t)ny);
+    gv::check(gv_get_nav_field(ctx_.handle(), out.data()), ctx_.handle(), "gv_get_nav_field");
+    return out;
+  }
+  std::vector<gv_nav_score> scoreNav(const std::vector<float> &poses, int32_t K, int32_t P)
+  {
+    if (K < 0 || P < 1 || poses.size() < (size_t)K * (size_t)P * 3) throw gv::Error(GV_ERR_BAD_ARG, "scoreNav: poses is K * P * 3");
+    std::vector<gv_nav_score> scores((size_t)K);
+    if (K == 0) return scores;
+    gv::check(gv_score_nav(ctx_.handle(), poses.data(), K, P, 0u, scores.data()), ctx_.handle(), "gv_score_nav");
+    return scores;
+  }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {

@@ -452,6 +452,96 @@ int gv_score_trajectories(gv_handle h, const float *poses, int32_t K, int32_t P,
 int gv_footprint_cells(uint8_t grid_x, uint8_t grid_y, double resolution, const gv_footprint *fp, float x, float y,
                        float yaw, int32_t *cells, int32_t cap, int32_t *n);
 
+/* --------------------------------- [EXTENSION] goal / path distance field (planner) -- */
+/* X9.  A controller ranks its candidates by the obstacle cost (X7) plus a goal-directed term: DWB's GoalDist and
+ * PathDist critics, the obstacle heuristic of Smac and MPPI.  That term is a shortest-path distance field over the
+ * costmap.  gv_nav_field computes it on the device from goal or path seeds over the resident costmap of the last
+ * gv_inflate, and gv_score_nav samples it along the poses[K][P][3] that gv_score_trajectories scores; the costmap never
+ * leaves the device.  The reference has no such step; this text is its definition, modelled on nav2's
+ * dwb_critics::MapGridCritic (propogateManhattanDistances, GoalDistCritic, PathDistCritic).  One addition, the cost
+ * weight, makes the same field a clearance-aware heuristic.
+ *
+ * Configuration (gv_nav_config).  step[v], for a cost byte v = 0..255, is 0 (blocked) for v >= obstacle_cost and
+ *   1 + cost_weight * v otherwise; cost_weight = 0 gives MapGridCritic's hop count.  gv_set_nav_config is handle
+ *   configuration like gv_set_footprint: no device work, kept through gv_reset, gv_set_log_odds and gv_grid_move; NULL
+ *   turns it off (the state after gv_create).  GV_ERR_BAD_ARG, configuration unchanged, for a null handle,
+ *   obstacle_cost outside 1..255, cost_weight outside 0..255, flags other than 0, or
+ *     (1 + cost_weight * (obstacle_cost - 1)) * (G - 1) > 0xFFFFFFFD
+ *   (G = nx * ny cells): every distance then fits 32 bits below the two sentinels.  On a 2000 x 2000 grid with
+ *   obstacle_cost = 253 that allows the weights 0..4.
+ *   gv_nav_step_table is host only and takes no handle, like gv_inflation_cost_table: table[v] = step[v];
+ *   GV_ERR_BAD_ARG for a null pointer, a field out of range or flags other than 0.
+ * Field.  field[G] is uint32 in OccupancyGrid.data order, like the costmap: cell (ix, iy) is field[G - 1 - (iy * nx + ix)],
+ *   and the neighbours of entry y * nx + x are x - 1 and x + 1 of the same row y and the same x of the rows y - 1 and
+ *   y + 1 (4-connectivity is its own mirror image under the 180 degree turn between the two orders).
+ *     a blocked cell (step[cost] == 0)         GV_NAV_BLOCKED
+ *     a seed cell                              0
+ *     any other traversable cell               the minimum, over 4-connected paths of traversable cells from any seed
+ *                                              cell, of the sum of step[cost[c]] over the cells ENTERED: every cell of
+ *                                              the path except its seed
+ *     a traversable cell no such path reaches  GV_NAV_UNREACHABLE
+ *   There are no diagonal moves, nothing wraps from the end of one row into the next, cells off the map do not exist.
+ *   The value is an exact integer and unique: the result does not depend on how the work is scheduled.
+ * Seeds.  seeds_xy[S][2], float32 in the grid's frame, S in 1..65536, host memory, copied before the call returns.
+ *   Each goes through the grid's own getIndex on ((double)x, (double)y), exactly as gv_score_trajectories treats a pose
+ *   centre.  A seed off the map, non-finite or on a blocked cell is skipped (PathDistCritic skips such path poses
+ *   too).  No usable seed is not an error: the field is then GV_NAV_BLOCKED or GV_NAV_UNREACHABLE everywhere.
+ *
+ * gv_nav_field reads the costmap as the last enqueued gv_inflate left it, with the configuration in force, and is
+ * ordered on gv_stream(h) behind everything enqueued before it.  UNLIKE ITS NEIGHBOURS IT WAITS ON THE HOST: it returns
+ * when the field is complete on the device.  The solver relaxes the field in rounds until a round changes nothing, and
+ * how many rounds that takes depends on the map (convergence is data dependent), so the host has to see the rounds'
+ * counters before it knows whether to enqueue more.  The field is a snapshot: a later gv_inflate, frame, move or
+ * configuration change does not change it, gv_reset invalidates it.  Allowed between gv_tick_enqueue and
+ * gv_tick_wait, where it waits for the tick's device work first.  info, when not NULL, receives n_seeds_used and the
+ * number of relaxation rounds run (a diagnostic that depends on scheduling).  GV_ERR_BAD_ARG for a null handle or
+ * seeds_xy or S outside 1..65536; GV_ERR_STATE when no configuration is set, when no gv_inflate has run since
+ * gv_create / gv_reset, and with a communicator of more than one rank (ranks own row bands of the grid).
+ * gv_get_nav_field (G values) is a synchronous read-back like gv_get_costmap; gv_device_nav_field gives the device
+ * pointer of the same G values for device-side consumers, read-only, valid until gv_destroy.  Both return
+ * GV_ERR_STATE before the first field since gv_create / gv_reset, GV_ERR_BAD_ARG for a null pointer.
+ *
+ * Sampling along trajectories (MapGridCritic::scoreTrajectory, all three of its aggregations at once).  A pose is
+ *   GOOD when its centre ((double)x, (double)y) passes getIndex and the field at that cell is neither GV_NAV_BLOCKED
+ *   nor GV_NAV_UNREACHABLE.  The yaw is never read.  Per trajectory (gv_nav_score, 24 bytes):
+ *     sum        the sum of the field at the centre cell over the good poses;
+ *     last       the field value of pose P - 1, GV_NAV_BLOCKED / GV_NAV_UNREACHABLE kept, GV_NAV_BLOCKED off the map;
+ *     best       the smallest value over the good poses, GV_NAV_UNREACHABLE when there is none;
+ *     best_pose  the smallest pose index that attains best, -1 when there is none;
+ *     n_bad      the number of poses that are not good.
+ *   Integer sums, minima and counts only: no order shows in the record.
+ * gv_score_nav_async follows gv_score_trajectories_async in everything but the record: the pose layout and limits
+ * (P in 1..4096, K in 0..2^20), GV_TRAJ_DEVICE_POSES, the ordering on gv_stream(h), and the destination rules -- pinned
+ * scores aligned to 8 bytes are written by the kernel, anything else goes through a copy command.  It reads the field
+ * of the last gv_nav_field.  K == 0 is a successful no-op.  GV_ERR_BAD_ARG for a null handle, poses or scores, P or K
+ * out of range, or any flag other than GV_TRAJ_DEVICE_POSES (GV_TRAJ_KEEP_POSE_COST included); GV_ERR_STATE before the
+ * first field and with a communicator of more than one rank.  gv_score_nav is the same call followed by the wait. */
+#define GV_NAV_BLOCKED     0xFFFFFFFFu
+#define GV_NAV_UNREACHABLE 0xFFFFFFFEu
+typedef struct {
+  int32_t obstacle_cost;   /* 1..255: a cell whose cost is >= this is blocked */
+  int32_t cost_weight;     /* 0..255: entering a traversable cell of cost v costs 1 + cost_weight * v */
+  uint32_t flags;          /* 0 */
+} gv_nav_config;
+typedef struct {
+  int32_t n_seeds_used;   /* seeds that named a traversable map cell (duplicates counted) */
+  int32_t rounds;         /* relaxation rounds run (diagnostic: depends on scheduling, never compared) */
+} gv_nav_info;
+typedef struct {
+  uint64_t sum;        /* sum of the field at the centre cell over the good poses */
+  uint32_t last;       /* field value of pose P-1; GV_NAV_BLOCKED / _UNREACHABLE kept; GV_NAV_BLOCKED if off map */
+  uint32_t best;       /* smallest value over the good poses; GV_NAV_UNREACHABLE when there is none */
+  int32_t best_pose;   /* smallest pose index that attains best; -1 when there is none */
+  int32_t n_bad;       /* poses off the map (getIndex's own test), on a blocked or on an unreachable cell */
+} gv_nav_score;        /* 24 bytes */
+int gv_nav_step_table(const gv_nav_config *cfg, uint32_t table[256]);
+int gv_set_nav_config(gv_handle h, const gv_nav_config *cfg);
+int gv_nav_field(gv_handle h, const float *seeds_xy, int32_t S, gv_nav_info *info /* may be NULL */);
+int gv_get_nav_field(gv_handle h, uint32_t *out);            /* synchronous read-back, G values */
+int gv_device_nav_field(gv_handle h, uint32_t **field);     /* for device-side consumers, read-only */
+int gv_score_nav_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_nav_score *scores);
+int gv_score_nav(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_nav_score *scores);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
