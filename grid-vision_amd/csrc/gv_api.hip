@@ -1,6 +1,7 @@
 // gv_api.hip -- C ABI (include/gridvision_hip.h) over the gfx950 kernels: the handle's life, transforms, getters,
-// plain map updates, grid publishing, ego motion, the inflated costmap layer, and the host-only helpers.  The frame pipeline is
-// gv_api_frame.hip, the sharded frame gv_api_shard.hip, the kNN / RANSAC / PCA path and the tick gv_api_pose.hip.
+// plain map updates, grid publishing, ego motion, and the host-only helpers.  The frame pipeline is gv_api_frame.hip,
+// the sharded frame gv_api_shard.hip, the kNN / RANSAC / PCA path and the tick gv_api_pose.hip, everything that reads or
+// makes the costmap (inflation, trajectory scoring, the distance field) gv_api_planner.hip.
 // One gv_context = one device + one resident grid + its HIP streams.  No exception
 // leaves these files; every entry point returns a gv_status.
 #include <chrono>
@@ -25,7 +26,7 @@ void refresh_origin(gv_context *h)
   h->org.ox = (double)h->m_base.m[3];
   h->org.oy = (double)h->m_base.m[7];
   int ix = 0, iy = 0;
-  h->org.valid = host::get_index(h->g, h->org.ox, h->org.oy, ix, iy) ? 1 : 0;
+  h->org.valid = get_index(h->g, h->org.ox, h->org.oy, ix, iy) ? 1 : 0;
   h->org.cx = ix;
   h->org.cy = iy;
 }
@@ -117,6 +118,29 @@ void *pinned_device_view(void *p, size_t align)
     return nullptr;
   }
   return at.devicePointer;
+}
+
+// The packed grid to PINNED host memory by a small kernel on the public stream, right behind the grid pass.  Measured
+// with a cloud streaming in per frame (tools/stream_run.py, profiles/r04/publish_variants.txt): hipMemcpyAsync on the
+// public stream 292-349 us per frame and erratic (the download's copy engine interleaves with the upload's: one
+// download in six took 300 us instead of 85); the download ordered on the upload stream between two uploads 381 us
+// (steady, but every copy command costs ~25 us of engine turn-around); this kernel 262 us, within 0.3 % frame after
+// frame -- the copy engines stay with the uploads, PCIe carries both directions at once.
+// One layer of G bytes in OccupancyGrid.data order (the packed grid, the costmap) to the caller's memory on the public
+// stream: by that kernel, else (pageable memory, or not 16-byte aligned: the kernel stores 16 bytes per lane) by a copy command.
+int publish_layer_async(gv_context *h, const int8_t *src, int8_t *data)
+{
+  int rc = set_device_only(h);
+  if (rc) return rc;
+  const size_t G = (size_t)h->g.G;
+  size_t body = 0;   // bytes the kernel takes
+  if (int8_t *view = static_cast<int8_t *>(pinned_device_view(data, 16))) {
+    body = G & ~(size_t)15;
+    launch_publish_grid(src, view, body, 32, h->stream);
+    GV_HIP(hipGetLastError());
+  }
+  if (G > body) GV_HIP(hipMemcpyAsync(data + body, src + body, G - body, hipMemcpyDeviceToHost, h->stream));
+  return GV_OK;
 }
 
 // convertPixelsTo3D (grid_vision_node.cpp:309-335): B points, fp64, on the host, with the given K^-1 and camera->base
@@ -670,41 +694,6 @@ int gv_to_occupancy_grid_async(gv_handle h, int8_t *data)
   GV_CATCH
 }
 
-// The packed grid to PINNED host memory by a small kernel on the public stream, right behind the grid pass.  Measured
-// with a cloud streaming in per frame (tools/stream_run.py, profiles/r04/publish_variants.txt): hipMemcpyAsync on the
-// public stream 292-349 us per frame and erratic (the download's copy engine interleaves with the upload's: one
-// download in six took 300 us instead of 85); the download ordered on the upload stream between two uploads 381 us
-// (steady, but every copy command costs ~25 us of engine turn-around); this kernel 262 us, within 0.3 % frame after
-// frame -- the copy engines stay with the uploads, PCIe carries both directions at once.
-// `src`: G bytes of a device layer in OccupancyGrid.data order (the packed grid, the costmap).
-static int publish_by_kernel(gv_context *h, const int8_t *src, int8_t *data, hipStream_t s, bool *done)
-{
-  *done = false;
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, data) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer ||
-      (reinterpret_cast<uintptr_t>(at.devicePointer) & 15u) != 0) {
-    (void)hipGetLastError();   // pageable memory, or not 16-byte aligned (the kernel stores 16 bytes per lane): the copy command instead
-    return GV_OK;
-  }
-  const size_t G = (size_t)h->g.G, body = G & ~(size_t)15;
-  launch_publish_grid(src, static_cast<int8_t *>(at.devicePointer), body, 32, s);
-  GV_HIP(hipGetLastError());
-  if (G > body) GV_HIP(hipMemcpyAsync(data + body, src + body, G - body, hipMemcpyDeviceToHost, s));
-  *done = true;
-  return GV_OK;
-}
-
-// one layer of G bytes to the caller's memory on the public stream: by the kernel where that works, else by a copy command
-static int publish_layer_async(gv_context *h, const int8_t *src, int8_t *data)
-{
-  int rc = set_device_only(h);
-  if (rc) return rc;
-  bool done = false;
-  if ((rc = publish_by_kernel(h, src, data, h->stream, &done))) return rc;
-  if (!done) GV_HIP(hipMemcpyAsync(data, src, (size_t)h->g.G, hipMemcpyDeviceToHost, h->stream));
-  return GV_OK;
-}
-
 int gv_publish_grid_async(gv_handle h, int8_t *data)
 {
   if (!h || !data) return GV_ERR_BAD_ARG;
@@ -746,7 +735,7 @@ int gv_grid_move(gv_handle h, const gv_transform *motion, gv_grid_move_info *inf
   GV_TRY
   host::Se2 d;
   if (!host::se2_from_motion(*motion, d)) return GV_ERR_BAD_ARG;
-  if (h->world > 1) { h->err = "gv_grid_move: ranks own row bands of the grid, a move crosses them"; return GV_ERR_STATE; }
+  if (int rc = refuse_state(h, "gv_grid_move", nullptr, 0, "a move crosses them")) return rc;
   const host::GridMoveStep st = host::plan_grid_move(h->move_residue, d, h->g);
   if (!std::isfinite(st.residue.x) || !std::isfinite(st.residue.y) || !std::isfinite(st.tx) || !std::isfinite(st.ty))
     return GV_ERR_BAD_ARG;   // finite fields whose sum overflows
@@ -792,213 +781,6 @@ int gv_set_height_band(gv_handle h, const gv_height_band *band)
     return GV_ERR_BAD_ARG;
   h->band = HeightBand{band->z_ground, band->z_max, band->ground_clears};
   return GV_OK;
-}
-
-// [EXTENSION] X6: handle configuration, the table is built here on the host and reaches the device with the next
-// gv_inflate (gv_context::Inflation).  A rejected configuration leaves the one in force alone.
-int gv_inflation_cost_table(const gv_inflation *cfg, double resolution, uint8_t *table, int32_t cap, int32_t *n)
-{
-  gv_context *h = nullptr;
-  if (!cfg) return GV_ERR_BAD_ARG;
-  GV_TRY
-  host::InflationTable t;
-  if (!host::inflation_table(*cfg, resolution, t)) return GV_ERR_BAD_ARG;
-  if (n) *n = t.d2max + 1;
-  if (!table || cap < t.d2max + 1) return GV_ERR_BAD_ARG;
-  std::memcpy(table, t.cost.data(), t.cost.size());
-  return GV_OK;
-  GV_CATCH
-}
-
-int gv_set_inflation(gv_handle h, const gv_inflation *cfg)
-{
-  if (!h) return GV_ERR_BAD_ARG;
-  GV_TRY
-  if (!cfg) {
-    h->infl.set = false;
-    return GV_OK;
-  }
-  host::InflationTable t;
-  if (!host::inflation_table(*cfg, h->g.res, t)) return GV_ERR_BAD_ARG;
-  h->infl.tab = std::move(t);
-  h->infl.thr = cfg->lethal_threshold;
-  h->infl.flags = cfg->flags;
-  h->infl.dirty = true;
-  h->infl.set = true;
-  return GV_OK;
-  GV_CATCH
-}
-
-// Two kernels on the public stream, between the grid passes of the frames around them (set_device_only: the streams
-// are not drained).  No host wait once the buffers exist.
-int gv_inflate(gv_handle h)
-{
-  if (!h) return GV_ERR_BAD_ARG;
-  GV_TRY
-  gv_context::Inflation &f = h->infl;
-  if (!f.set) { h->err = "gv_inflate: no inflation set (gv_set_inflation)"; return GV_ERR_STATE; }
-  if (h->world > 1) { h->err = "gv_inflate: ranks own row bands of the grid, the stencil crosses them"; return GV_ERR_STATE; }
-  int rc = set_device_only(h);
-  if (rc) return rc;
-  const size_t G = (size_t)h->g.G;
-  const bool keep = (f.flags & GV_INFLATE_KEEP_DIST2) != 0;
-  const int32_t row_words = inflate_row_words(h->g.nx);
-  if ((rc = f.bits.reserve_zeroed(h, (size_t)h->g.ny * (size_t)row_words, h->stream))) return rc;
-  if ((rc = f.cost.reserve(h, G + 16))) return rc;
-  if (keep && (rc = f.dist2.reserve(h, G))) return rc;
-  constexpr size_t kTableBytes = (size_t)(host::kInflateMaxRc + 1) * (host::kInflateMaxRc + 1);
-  if (f.dirty) {
-    const int k = f.slot ^ 1;
-    if ((rc = f.d_table[k].reserve(h, kTableBytes))) return rc;
-    if ((rc = f.stage[k].reserve(h, kTableBytes, hipHostMallocDefault))) return rc;
-    if (!f.staged[k]) GV_HIP(f.staged[k].create(hipEventDisableTiming));
-    if (f.staged_used[k]) GV_HIP(hipEventSynchronize(f.staged[k]));
-    std::memcpy(f.stage[k].get(), f.tab.cost.data(), f.tab.cost.size());
-    GV_HIP(hipMemcpyAsync(f.d_table[k], f.stage[k].get(), f.tab.cost.size(), hipMemcpyHostToDevice, h->stream));
-    GV_HIP(hipEventRecord(f.staged[k], h->stream));
-    f.staged_used[k] = true;
-    f.slot = k;
-    f.dirty = false;
-  }
-  InflateArgs a{};
-  a.nx = h->g.nx; a.ny = h->g.ny;
-  a.row_words = row_words;
-  a.thr = f.thr;
-  a.rc = f.tab.rc; a.d2max = f.tab.d2max;
-  a.i8 = h->occ_i8;
-  a.bits = f.bits;
-  a.table = f.d_table[f.slot];
-  a.cost = f.cost;
-  a.dist2 = keep ? f.dist2.get() : nullptr;
-  launch_lethal_bits(a, h->stream);
-  launch_inflate_tiles(a, h->stream);
-  GV_HIP(hipGetLastError());
-  f.have_cost = true;
-  f.have_dist2 = keep;
-  return GV_OK;
-  GV_CATCH
-}
-
-int gv_get_costmap(gv_handle h, uint8_t *out)
-{
-  if (!h || !out) return GV_ERR_BAD_ARG;
-  if (!h->infl.have_cost) return GV_ERR_STATE;
-  return copy_out(h, out, h->infl.cost, (size_t)h->g.G);
-}
-
-int gv_get_obstacle_dist2(gv_handle h, uint16_t *out)
-{
-  if (!h || !out) return GV_ERR_BAD_ARG;
-  if (!h->infl.have_cost || !h->infl.have_dist2) return GV_ERR_STATE;
-  return copy_out(h, out, h->infl.dist2, (size_t)h->g.G * sizeof(uint16_t));
-}
-
-int gv_publish_costmap_async(gv_handle h, uint8_t *data)
-{
-  if (!h || !data) return GV_ERR_BAD_ARG;
-  if (!h->infl.have_cost) return GV_ERR_STATE;
-  GV_TRY
-  return publish_layer_async(h, reinterpret_cast<const int8_t *>(h->infl.cost.get()), reinterpret_cast<int8_t *>(data));
-  GV_CATCH
-}
-
-// [EXTENSION] X7: handle configuration only; every scoring call copies h->traj.fp into its kernel arguments.
-int gv_set_footprint(gv_handle h, const gv_footprint *fp)
-{
-  if (!h) return GV_ERR_BAD_ARG;
-  if (!fp) {
-    h->traj.set = false;
-    return GV_OK;
-  }
-  if (!host::footprint_valid(*fp)) return GV_ERR_BAD_ARG;
-  h->traj.fp = *fp;
-  for (int32_t i = fp->n_vertices; i < host::kFootprintMaxVertices; ++i) h->traj.fp.vx[i] = h->traj.fp.vy[i] = 0.0;
-  h->traj.set = true;
-  return GV_OK;
-}
-
-// A copy of the poses (host poses only), one kernel, and a copy per result the kernel cannot write in place, all on
-// the public stream: between the grid passes of the frames around them, behind the last gv_inflate.
-int gv_score_trajectories_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags,
-                                gv_traj_score *scores, uint8_t *pose_cost)
-{
-  if (!h) return GV_ERR_BAD_ARG;
-  GV_TRY
-  const bool keep = (flags & GV_TRAJ_KEEP_POSE_COST) != 0;
-  if (!poses || !scores || P < 1 || P > 4096 || K < 0 || K > (1 << 20) || (flags & ~host::kTrajFlags) != 0 ||
-      (keep && !pose_cost))
-    return GV_ERR_BAD_ARG;
-  gv_context::TrajScore &t = h->traj;
-  if (!t.set) { h->err = "gv_score_trajectories: no footprint set (gv_set_footprint)"; return GV_ERR_STATE; }
-  if (!h->infl.have_cost) { h->err = "gv_score_trajectories: no costmap (gv_inflate)"; return GV_ERR_STATE; }
-  if (h->world > 1) { h->err = "gv_score_trajectories: ranks own row bands of the grid, there is no whole costmap"; return GV_ERR_STATE; }
-  if (K == 0) return GV_OK;
-  int rc = set_device_only(h);
-  if (rc) return rc;
-  const size_t n_poses = (size_t)K * (size_t)P;
-  TrajArgs a{};
-  a.g = h->g;
-  a.fp = t.fp;
-  a.K = K; a.P = P;
-  a.cost = h->infl.cost;
-  if (flags & GV_TRAJ_DEVICE_POSES) {
-    a.poses = poses;
-  } else {
-    if ((rc = t.d_poses.reserve(h, n_poses * 3))) return rc;
-    GV_HIP(hipMemcpyAsync(t.d_poses, poses, n_poses * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    a.poses = t.d_poses;
-  }
-  a.scores = static_cast<gv_traj_score *>(pinned_device_view(scores, 16));
-  const bool copy_scores = a.scores == nullptr;
-  if (copy_scores) {
-    if ((rc = t.d_scores.reserve(h, (size_t)K))) return rc;
-    a.scores = t.d_scores;
-  }
-  bool copy_pose_cost = false;
-  if (keep) {
-    a.pose_cost = static_cast<uint8_t *>(pinned_device_view(pose_cost, 1));
-    copy_pose_cost = a.pose_cost == nullptr;
-    if (copy_pose_cost) {
-      if ((rc = t.d_pose_cost.reserve(h, n_poses))) return rc;
-      a.pose_cost = t.d_pose_cost;
-    }
-  }
-  launch_score_trajectories(a, h->stream);
-  GV_HIP(hipGetLastError());
-  if (copy_scores) GV_HIP(hipMemcpyAsync(scores, a.scores, (size_t)K * sizeof(gv_traj_score), hipMemcpyDeviceToHost, h->stream));
-  if (copy_pose_cost) GV_HIP(hipMemcpyAsync(pose_cost, a.pose_cost, n_poses, hipMemcpyDeviceToHost, h->stream));
-  return GV_OK;
-  GV_CATCH
-}
-
-int gv_score_trajectories(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_traj_score *scores,
-                          uint8_t *pose_cost)
-{
-  const int rc = gv_score_trajectories_async(h, poses, K, P, flags, scores, pose_cost);
-  if (rc || K == 0) return rc;
-  GV_HIP(hipStreamSynchronize(h->stream));
-  return GV_OK;
-}
-
-// host only: the twin of the kernel's geometry (host::footprint_cells), on the geometry gv_create gives
-int gv_footprint_cells(uint8_t grid_x, uint8_t grid_y, double resolution, const gv_footprint *fp, float x, float y, float yaw,
-                       int32_t *cells, int32_t cap, int32_t *n)
-{
-  gv_context *h = nullptr;
-  if (!fp || !n) return GV_ERR_BAD_ARG;
-  GV_TRY
-  GridParams g{};
-  if (!host::footprint_valid(*fp) || !host::grid_params(grid_x, grid_y, resolution, g)) return GV_ERR_BAD_ARG;
-  std::vector<int32_t> out;
-  if (!host::footprint_cells(g, *fp, x, y, yaw, out)) {
-    *n = -1;
-    return GV_OK;
-  }
-  *n = (int32_t)out.size();
-  if (!cells || cap < *n) return GV_ERR_BAD_ARG;
-  std::memcpy(cells, out.data(), out.size() * sizeof(int32_t));
-  return GV_OK;
-  GV_CATCH
 }
 
 int gv_get_hits(gv_handle h, int32_t *out)

@@ -1,0 +1,428 @@
+// gv_api_planner.hip -- the planner side of the C ABI, everything that makes or reads the costmap:
+//   [EXTENSION] X6  the inflated costmap layer (gv_set_inflation, gv_inflate, its getters and publisher),
+//   [EXTENSION] X7  footprint scoring of trajectories against it (gv_set_footprint, gv_score_trajectories*),
+//   [EXTENSION] X9  the goal / path distance field over it (gv_set_nav_config, gv_nav_field and its getters) and its
+//                   sampler along trajectories (gv_score_nav*).
+// The kernels are gv_inflate.hip, gv_trajscore.hip and gv_navfield.hip (which also argues why the rounds end at the
+// exact field).  What the two samplers do alike is written once, in front of the entry points.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "gv_context.hpp"
+
+namespace gv_internal __attribute__((visibility("hidden"))) {
+
+// What a call refuses with GV_ERR_STATE, checked in this order: `missing` (the call's own configuration is not set:
+// the caller passes the text, or null), a layer in `needs` that no call has made since gv_create / gv_reset, and a
+// communicator of more than one rank (`sharded`: why a row band of the grid will not do).  h->err says which.
+int refuse_state(gv_context *h, const char *call, const char *missing, unsigned needs, const char *sharded)
+{
+  std::string why;
+  if (missing) why = missing;
+  else if ((needs & kNeedCostmap) && !h->infl.have_cost) why = "no costmap (gv_inflate)";
+  else if ((needs & kNeedField) && !h->nav.have_field) why = "no distance field (gv_nav_field)";
+  else if (h->world > 1) why = std::string("ranks own row bands of the grid, ") + sharded;
+  else return GV_OK;
+  h->err = std::string(call) + ": " + why;
+  return GV_ERR_STATE;
+}
+
+}  // namespace gv_internal
+
+namespace {
+
+// a sampler's batch: (K, P, 3) poses and K records, flags within `allowed`
+bool batch_ok(const float *poses, const void *scores, int32_t K, int32_t P, uint32_t flags, uint32_t allowed)
+{
+  return poses && scores && P >= 1 && P <= 4096 && K >= 0 && K <= (1 << 20) && (flags & ~allowed) == 0;
+}
+
+// the poses where the kernel reads them: the caller's device pointer as given, else the handle's copy of host poses
+int stage_poses(gv_context *h, const float *poses, size_t n_poses, uint32_t flags, const float **dev)
+{
+  *dev = poses;
+  if (flags & GV_TRAJ_DEVICE_POSES) return GV_OK;
+  if (int rc = h->d_poses.reserve(h, n_poses * 3)) return rc;
+  GV_HIP(hipMemcpyAsync(h->d_poses, poses, n_poses * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  *dev = h->d_poses;
+  return GV_OK;
+}
+
+// Where a kernel writes n results bound for `dst`: dst's own device view when it is pinned host memory aligned to
+// `align` bytes, else `landing`, which copy_back empties into dst on the public stream behind the kernel.
+template <typename T>
+struct ResultDest {
+  T *dev = nullptr;    // what the kernel is given
+  T *host = nullptr;   // non-null: the results land in device memory and are copied here
+  size_t n = 0;
+  int open(gv_context *h, T *dst, size_t count, size_t align, DevBuf<T> &landing)
+  {
+    n = count;
+    if ((dev = static_cast<T *>(pinned_device_view(dst, align)))) return GV_OK;
+    if (int rc = landing.reserve(h, n)) return rc;
+    dev = landing;
+    host = dst;
+    return GV_OK;
+  }
+  int copy_back(gv_context *h) const
+  {
+    if (host) GV_HIP(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    return GV_OK;
+  }
+};
+
+// the synchronous form of a sampler: rc is what its asynchronous form returned
+int wait_scored(gv_context *h, int rc, int32_t K)
+{
+  if (rc || K == 0) return rc;
+  GV_HIP(hipStreamSynchronize(h->stream));
+  return GV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// [EXTENSION] X6: handle configuration, the table is built here on the host and reaches the device with the next
+// gv_inflate (gv_context::Inflation).  A rejected configuration leaves the one in force alone.
+int gv_inflation_cost_table(const gv_inflation *cfg, double resolution, uint8_t *table, int32_t cap, int32_t *n)
+{
+  gv_context *h = nullptr;
+  if (!cfg) return GV_ERR_BAD_ARG;
+  GV_TRY
+  host::InflationTable t;
+  if (!host::inflation_table(*cfg, resolution, t)) return GV_ERR_BAD_ARG;
+  if (n) *n = t.d2max + 1;
+  if (!table || cap < t.d2max + 1) return GV_ERR_BAD_ARG;
+  std::memcpy(table, t.cost.data(), t.cost.size());
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_set_inflation(gv_handle h, const gv_inflation *cfg)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!cfg) {
+    h->infl.set = false;
+    return GV_OK;
+  }
+  host::InflationTable t;
+  if (!host::inflation_table(*cfg, h->g.res, t)) return GV_ERR_BAD_ARG;
+  h->infl.tab = std::move(t);
+  h->infl.thr = cfg->lethal_threshold;
+  h->infl.flags = cfg->flags;
+  h->infl.dirty = true;
+  h->infl.set = true;
+  return GV_OK;
+  GV_CATCH
+}
+
+// Two kernels on the public stream, between the grid passes of the frames around them (set_device_only: the streams
+// are not drained).  No host wait once the buffers exist.
+int gv_inflate(gv_handle h)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  gv_context::Inflation &f = h->infl;
+  int rc = refuse_state(h, "gv_inflate", f.set ? nullptr : "no inflation set (gv_set_inflation)", 0, "the stencil crosses them");
+  if (rc || (rc = set_device_only(h))) return rc;
+  const size_t G = (size_t)h->g.G;
+  const bool keep = (f.flags & GV_INFLATE_KEEP_DIST2) != 0;
+  const int32_t row_words = inflate_row_words(h->g.nx);
+  if ((rc = f.bits.reserve_zeroed(h, (size_t)h->g.ny * (size_t)row_words, h->stream))) return rc;
+  if ((rc = f.cost.reserve(h, G + 16))) return rc;
+  if (keep && (rc = f.dist2.reserve(h, G))) return rc;
+  constexpr size_t kTableBytes = (size_t)(host::kInflateMaxRc + 1) * (host::kInflateMaxRc + 1);
+  if (f.dirty) {
+    const int k = f.slot ^ 1;
+    if ((rc = f.d_table[k].reserve(h, kTableBytes))) return rc;
+    if ((rc = f.stage[k].reserve(h, kTableBytes, hipHostMallocDefault))) return rc;
+    if (!f.staged[k]) GV_HIP(f.staged[k].create(hipEventDisableTiming));
+    if (f.staged_used[k]) GV_HIP(hipEventSynchronize(f.staged[k]));
+    std::memcpy(f.stage[k].get(), f.tab.cost.data(), f.tab.cost.size());
+    GV_HIP(hipMemcpyAsync(f.d_table[k], f.stage[k].get(), f.tab.cost.size(), hipMemcpyHostToDevice, h->stream));
+    GV_HIP(hipEventRecord(f.staged[k], h->stream));
+    f.staged_used[k] = true;
+    f.slot = k;
+    f.dirty = false;
+  }
+  InflateArgs a{};
+  a.nx = h->g.nx; a.ny = h->g.ny;
+  a.row_words = row_words;
+  a.thr = f.thr;
+  a.rc = f.tab.rc; a.d2max = f.tab.d2max;
+  a.i8 = h->occ_i8;
+  a.bits = f.bits;
+  a.table = f.d_table[f.slot];
+  a.cost = f.cost;
+  a.dist2 = keep ? f.dist2.get() : nullptr;
+  launch_lethal_bits(a, h->stream);
+  launch_inflate_tiles(a, h->stream);
+  GV_HIP(hipGetLastError());
+  f.have_cost = true;
+  f.have_dist2 = keep;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_get_costmap(gv_handle h, uint8_t *out)
+{
+  if (!h || !out) return GV_ERR_BAD_ARG;
+  if (!h->infl.have_cost) return GV_ERR_STATE;
+  return copy_out(h, out, h->infl.cost, (size_t)h->g.G);
+}
+
+int gv_get_obstacle_dist2(gv_handle h, uint16_t *out)
+{
+  if (!h || !out) return GV_ERR_BAD_ARG;
+  if (!h->infl.have_cost || !h->infl.have_dist2) return GV_ERR_STATE;
+  return copy_out(h, out, h->infl.dist2, (size_t)h->g.G * sizeof(uint16_t));
+}
+
+int gv_publish_costmap_async(gv_handle h, uint8_t *data)
+{
+  if (!h || !data) return GV_ERR_BAD_ARG;
+  if (!h->infl.have_cost) return GV_ERR_STATE;
+  GV_TRY
+  return publish_layer_async(h, reinterpret_cast<const int8_t *>(h->infl.cost.get()), reinterpret_cast<int8_t *>(data));
+  GV_CATCH
+}
+
+// [EXTENSION] X7: handle configuration only; every scoring call copies h->traj.fp into its kernel arguments.
+int gv_set_footprint(gv_handle h, const gv_footprint *fp)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  if (!fp) {
+    h->traj.set = false;
+    return GV_OK;
+  }
+  if (!host::footprint_valid(*fp)) return GV_ERR_BAD_ARG;
+  h->traj.fp = *fp;
+  for (int32_t i = fp->n_vertices; i < host::kFootprintMaxVertices; ++i) h->traj.fp.vx[i] = h->traj.fp.vy[i] = 0.0;
+  h->traj.set = true;
+  return GV_OK;
+}
+
+// A copy of the poses (host poses only), one kernel, and a copy per result the kernel cannot write in place, all on
+// the public stream: between the grid passes of the frames around them, behind the last gv_inflate.
+int gv_score_trajectories_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags,
+                                gv_traj_score *scores, uint8_t *pose_cost)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  const bool keep = (flags & GV_TRAJ_KEEP_POSE_COST) != 0;
+  if (!batch_ok(poses, scores, K, P, flags, host::kTrajFlags) || (keep && !pose_cost)) return GV_ERR_BAD_ARG;
+  gv_context::TrajScore &t = h->traj;
+  int rc = refuse_state(h, "gv_score_trajectories", t.set ? nullptr : "no footprint set (gv_set_footprint)", kNeedCostmap,
+                        "there is no whole costmap");
+  if (rc || K == 0 || (rc = set_device_only(h))) return rc;
+  const size_t n_poses = (size_t)K * (size_t)P;
+  TrajArgs a{};
+  a.g = h->g;
+  a.fp = t.fp;
+  a.K = K; a.P = P;
+  a.cost = h->infl.cost;
+  ResultDest<gv_traj_score> to_scores;
+  ResultDest<uint8_t> to_pose_cost;   // stays closed (null, no copy) without GV_TRAJ_KEEP_POSE_COST
+  if ((rc = stage_poses(h, poses, n_poses, flags, &a.poses)) || (rc = to_scores.open(h, scores, (size_t)K, 16, t.d_scores)) ||
+      (keep && (rc = to_pose_cost.open(h, pose_cost, n_poses, 1, t.d_pose_cost))))
+    return rc;
+  a.scores = to_scores.dev;
+  a.pose_cost = to_pose_cost.dev;
+  launch_score_trajectories(a, h->stream);
+  GV_HIP(hipGetLastError());
+  if ((rc = to_scores.copy_back(h)) || (rc = to_pose_cost.copy_back(h))) return rc;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_score_trajectories(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_traj_score *scores,
+                          uint8_t *pose_cost)
+{
+  return wait_scored(h, gv_score_trajectories_async(h, poses, K, P, flags, scores, pose_cost), K);
+}
+
+// host only: the twin of the kernel's geometry (host::footprint_cells), on the geometry gv_create gives
+int gv_footprint_cells(uint8_t grid_x, uint8_t grid_y, double resolution, const gv_footprint *fp, float x, float y, float yaw,
+                       int32_t *cells, int32_t cap, int32_t *n)
+{
+  gv_context *h = nullptr;
+  if (!fp || !n) return GV_ERR_BAD_ARG;
+  GV_TRY
+  GridParams g{};
+  if (!host::footprint_valid(*fp) || !host::grid_params(grid_x, grid_y, resolution, g)) return GV_ERR_BAD_ARG;
+  std::vector<int32_t> out;
+  if (!host::footprint_cells(g, *fp, x, y, yaw, out)) {
+    *n = -1;
+    return GV_OK;
+  }
+  *n = (int32_t)out.size();
+  if (!cells || cap < *n) return GV_ERR_BAD_ARG;
+  std::memcpy(cells, out.data(), out.size() * sizeof(int32_t));
+  return GV_OK;
+  GV_CATCH
+}
+
+// ---- [EXTENSION] X9: the distance field and its sampler ----
+int gv_nav_step_table(const gv_nav_config *cfg, uint32_t table[256])
+{
+  if (!cfg || !table || !host::nav_config_valid(*cfg)) return GV_ERR_BAD_ARG;
+  host::nav_step_table(*cfg, table);
+  return GV_OK;
+}
+
+// handle configuration only; gv_nav_field copies it into its kernel arguments
+int gv_set_nav_config(gv_handle h, const gv_nav_config *cfg)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  if (!cfg) {
+    h->nav.set = false;
+    return GV_OK;
+  }
+  if (!host::nav_config_valid(*cfg) || !host::nav_config_fits(*cfg, h->g.G)) return GV_ERR_BAD_ARG;
+  h->nav.cfg = *cfg;
+  h->nav.set = true;
+  return GV_OK;
+}
+
+// Everything goes on the public stream, behind what was enqueued before (a pending tick's grid pass and inflate
+// included).  Seeds become field entries here on the host (the exact getIndex); whether a seed's cell is blocked only
+// the device knows, so k_nav_seeds drops those and counts the rest.  Then rounds in batches of 4, 8, .. kBatchMax
+// launches; a batch ends with its counters copied into the pinned block and one event wait, and the loop stops after
+// the first round whose counter is 0 (the rounds behind it in the batch found no active tile and did nothing).
+int gv_nav_field(gv_handle h, const float *seeds_xy, int32_t S, gv_nav_info *info)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!seeds_xy || S < 1 || S > 65536) return GV_ERR_BAD_ARG;
+  gv_context::NavField &f = h->nav;
+  int rc = refuse_state(h, "gv_nav_field", f.set ? nullptr : "no configuration set (gv_set_nav_config)", kNeedCostmap,
+                        "there is no whole costmap");
+  if (rc || (rc = set_device_only(h))) return rc;
+  constexpr int kBatchMax = gv_context::NavField::kBatchMax;
+  constexpr size_t kSeedOff = 512;   // bytes of the pinned block in front of the seeds: the counters land there
+  static_assert((1 + kBatchMax) * sizeof(uint32_t) <= kSeedOff, "the counters fit in front of the seeds");
+  const int32_t G = h->g.G;
+  const int32_t tiles_x = (h->g.nx + kNavTile - 1) / kNavTile, tiles_y = (h->g.ny + kNavTile - 1) / kNavTile;
+  const size_t n_tiles = (size_t)tiles_x * (size_t)tiles_y;
+  if ((rc = f.field.reserve(h, ((size_t)G + 3) / 4 * 4))) return rc;
+  if ((rc = f.flags.reserve(h, 2 * n_tiles))) return rc;
+  if ((rc = f.counters.reserve(h, 1 + kBatchMax))) return rc;
+  if ((rc = f.d_seeds.reserve(h, (size_t)S))) return rc;
+  if ((rc = f.stage.reserve(h, kSeedOff + (size_t)S * sizeof(int32_t), hipHostMallocDefault))) return rc;
+  if (!f.done) GV_HIP(f.done.create(hipEventDisableTiming));
+  f.have_field = false;   // until this call has converged
+
+  int32_t *cells = reinterpret_cast<int32_t *>(f.stage.get() + kSeedOff);
+  int32_t n = 0;
+  for (int32_t i = 0; i < S; ++i) {
+    const int32_t e = host::nav_seed_entry(h->g, seeds_xy[2 * i], seeds_xy[2 * i + 1]);
+    if (e >= 0) cells[n++] = e;
+  }
+  const volatile uint32_t *landed = reinterpret_cast<const volatile uint32_t *>(f.stage.get());
+
+  NavArgs a{};
+  a.nx = h->g.nx; a.ny = h->g.ny; a.G = G;
+  a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+  a.step = NavStep{f.cfg.obstacle_cost, f.cfg.cost_weight};
+  a.pass_cap = h->tune.nav_pass_cap;
+  a.cost = h->infl.cost;
+  a.field = f.field;
+  a.seeds = f.d_seeds;
+  a.n_seeds = n;
+  a.flags_out = f.flags;          // round 0 reads the first half
+  a.counter = f.counters;         // [0]: seeds used
+  GV_HIP(hipMemsetAsync(f.flags, 0, 2 * n_tiles * sizeof(uint32_t), h->stream));
+  GV_HIP(hipMemsetAsync(f.counters, 0, sizeof(uint32_t), h->stream));
+  if (n > 0) GV_HIP(hipMemcpyAsync(f.d_seeds, cells, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  launch_nav_init(a, h->stream);
+  launch_nav_seeds(a, h->stream);
+  GV_HIP(hipGetLastError());
+
+  const int64_t max_rounds = (int64_t)G + 2;
+  int64_t rounds = 0;
+  int batch = 4;
+  for (bool converged = false; !converged;) {
+    if (rounds >= max_rounds) {
+      h->err = "gv_nav_field: no convergence within G + 2 rounds";
+      return GV_ERR_STATE;
+    }
+    const int nb = (int)std::min<int64_t>(batch, max_rounds - rounds);
+    GV_HIP(hipMemsetAsync(f.counters.get() + 1, 0, (size_t)nb * sizeof(uint32_t), h->stream));
+    for (int i = 0; i < nb; ++i) {
+      const int64_t r = rounds + i;
+      a.flags_in = f.flags.get() + (size_t)(r & 1) * n_tiles;
+      a.flags_out = f.flags.get() + (size_t)((r + 1) & 1) * n_tiles;
+      a.counter = f.counters.get() + 1 + i;
+      launch_nav_relax(a, h->stream);
+    }
+    GV_HIP(hipGetLastError());
+    GV_HIP(hipMemcpyAsync(f.stage.get(), f.counters, (size_t)(1 + nb) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipEventRecord(f.done, h->stream));
+    GV_HIP(hipEventSynchronize(f.done));
+    int used = nb;
+    for (int i = 0; i < nb; ++i)
+      if (landed[1 + i] == 0u) {
+        used = i + 1;
+        converged = true;
+        break;
+      }
+    rounds += used;
+    batch = std::min(batch * 2, kBatchMax);
+  }
+  f.have_field = true;
+  if (info) {
+    info->n_seeds_used = (int32_t)landed[0];
+    info->rounds = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+  }
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_get_nav_field(gv_handle h, uint32_t *out)
+{
+  if (!h || !out) return GV_ERR_BAD_ARG;
+  if (!h->nav.have_field) return GV_ERR_STATE;
+  return copy_out(h, out, h->nav.field, (size_t)h->g.G * sizeof(uint32_t));
+}
+
+int gv_device_nav_field(gv_handle h, uint32_t **field)
+{
+  if (!h || !field) return GV_ERR_BAD_ARG;
+  if (!h->nav.have_field) return GV_ERR_STATE;
+  *field = h->nav.field.get();
+  return GV_OK;
+}
+
+// gv_score_trajectories_async with another kernel and another record
+int gv_score_nav_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_nav_score *scores)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!batch_ok(poses, scores, K, P, flags, GV_TRAJ_DEVICE_POSES)) return GV_ERR_BAD_ARG;
+  gv_context::NavField &f = h->nav;
+  int rc = refuse_state(h, "gv_score_nav", nullptr, kNeedField, "there is no whole field");
+  if (rc || K == 0 || (rc = set_device_only(h))) return rc;
+  NavScoreArgs a{};
+  a.g = h->g;
+  a.K = K; a.P = P;
+  a.field = f.field;
+  ResultDest<gv_nav_score> to_scores;
+  if ((rc = stage_poses(h, poses, (size_t)K * (size_t)P, flags, &a.poses)) || (rc = to_scores.open(h, scores, (size_t)K, 8, f.d_scores)))
+    return rc;
+  a.scores = to_scores.dev;
+  launch_score_nav(a, h->stream);
+  GV_HIP(hipGetLastError());
+  return to_scores.copy_back(h);
+  GV_CATCH
+}
+
+int gv_score_nav(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_nav_score *scores)
+{
+  return wait_scored(h, gv_score_nav_async(h, poses, K, P, flags, scores), K);
+}
+
+}  // extern "C"

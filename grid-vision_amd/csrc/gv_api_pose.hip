@@ -152,14 +152,6 @@ int gv_compute_depth_for_bboxes(gv_handle h, const gv_bbox *bboxes, int32_t nb, 
   GV_CATCH
 }
 
-// smallest float >= the fp64 threshold: for a float f, f < thr_f <=> (double)f < thr
-static float ceil_to_float(double v)
-{
-  float f = (float)v;
-  if ((double)f < v) f = std::nextafterf(f, INFINITY);
-  return f;
-}
-
 static int ensure_ransac_buffers(gv_context *h, size_t n, int32_t iterations)
 {
   int rc;
@@ -246,7 +238,7 @@ static int compute_bbox_pose_impl(gv_handle h, const gv_bbox *bboxes, int32_t nb
   if (st_out) *st_out = RansacState{};
   if (n == 0 || (with_ground && n < 3)) return GV_OK;
   if (nb && (rc = upload_scratch_bboxes(h, bboxes, nb))) return rc;
-  const float thr_f = ceil_to_float(0.04);
+  const float thr_f = host::ceil_to_float(0.04);   // for a float f: f < thr_f <=> (double)f < 0.04
   if (with_ground) {   // segmentGroundPlane(0.04, 50 hypotheses) on the camera-frame cloud (grid_vision_node.cpp:215-216)
     if ((rc = ensure_ransac_buffers(h, n, 50))) return rc;
     launch_ransac_plane(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, 50, 12345ull, h->d_planes, h->d_plane_counts,
@@ -297,7 +289,7 @@ static int segment_ground_device(gv_context *h, double threshold, int32_t iterat
   int rc;
   if ((rc = ensure_ransac_buffers(h, n, iterations))) return rc;
   if ((rc = h->d_ground.reserve(h, n))) return rc;
-  const float thr_f = ceil_to_float(threshold);
+  const float thr_f = host::ceil_to_float(threshold);
   // camera-frame cloud (the reference segments transformed_cloud, grid_vision_node.cpp:215-216): transformed on the fly
   launch_ransac_plane(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, iterations, seed, h->d_planes, h->d_plane_counts,
                       h->d_rscratch, h->d_rstate, h->stream);
@@ -472,7 +464,7 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
     n_rects = nd;
     T.vision_ran = true;
   } else if (pca) {   // cloud_detections::computeBBoxPose (:210-231)
-    const float thr_f = ceil_to_float(0.04);
+    const float thr_f = host::ceil_to_float(0.04);
     if ((rc = ensure_ransac_buffers(h, n, 50))) return rc;
     launch_ransac_plane(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, 50, 12345ull, h->d_planes, h->d_plane_counts,
                         h->d_rscratch, h->d_rstate, s);

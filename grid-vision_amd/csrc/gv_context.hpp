@@ -248,13 +248,12 @@ struct __attribute__((visibility("hidden"))) gv_context {
   } infl;
   // [EXTENSION] X7 trajectory scoring (gv_set_footprint / gv_score_trajectories*).  The footprint is handle
   // configuration, copied into the kernel arguments of every call at enqueue.  The buffers are made by the first call
-  // that needs them and grow with K * P: the device copy of host poses, and the landing places of results whose
-  // destination the kernel cannot write itself (pageable memory).  All three are used on the public stream only, so a
-  // call's copies and kernel run behind those of the call before it.
+  // that needs them and grow with K * P: the landing places of results whose destination the kernel cannot write
+  // itself (pageable memory).  Both are used on the public stream only, so a call's kernel and copies run behind
+  // those of the call before it.
   struct TrajScore {
     bool set = false;
     gv_footprint fp{};
-    DevBuf<float> d_poses;
     DevBuf<gv_traj_score> d_scores;
     DevBuf<uint8_t> d_pose_cost;
   } traj;
@@ -273,9 +272,13 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<int32_t> d_seeds;
     PinnedBuf stage;                        // the counters' landing place, then the seed cells on their way in
     Event done;                             // public stream: a batch's counters have landed
-    DevBuf<float> d_poses;                  // the sampler: device copy of host poses
-    DevBuf<gv_nav_score> d_scores;          // ... and the landing place of records bound for pageable memory
+    DevBuf<gv_nav_score> d_scores;          // the sampler: the landing place of records bound for pageable memory
   } nav;
+  // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
+  // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
+  // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in
+  // flight reads is not released under it.
+  DevBuf<float> d_poses;
   // per-frame count grids (sb[k].hits; generic path: sb[0].hits)
   DevBuf<uint8_t> clip_end;                 // generic path only
   DevBuf<uint32_t> ray_list;
@@ -406,6 +409,7 @@ int copy_out(gv_context *h, void *dst, const void *src, size_t bytes);
 void convert_pixels_host(const double Kinv[9], const Xform64 &x_bc, const gv_bbox *bboxes, const float *depths, int32_t nb,
                          double *base_points_xyz);
 void *pinned_device_view(void *p, size_t align);
+int publish_layer_async(gv_context *h, const int8_t *src, int8_t *data);
 // gv_api_frame.hip
 int ensure_point_buffers(gv_context *h, size_t n, size_t n_slice = 0);
 int ensure_det(gv_context *h, DetSet &d, int32_t n);
@@ -431,4 +435,7 @@ int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, 
 int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k);
 // gv_api_shard.hip
 void comm_destroy(gv_context *h);
+// gv_api_planner.hip
+enum : unsigned { kNeedCostmap = 1u, kNeedField = 2u };
+int refuse_state(gv_context *h, const char *call, const char *missing, unsigned needs, const char *sharded);
 }  // namespace gv_internal

@@ -49,24 +49,7 @@ __device__ __forceinline__ void xform34(const Mat34f &m, float px, float py, flo
   oz = __fadd_rn(__fmul_rn(px, m.m[8]), __fadd_rn(__fmul_rn(py, m.m[9]), __fadd_rn(__fmul_rn(pz, m.m[10]), m.m[11])));
 }
 
-// grid_map::GridMap::getIndex (called at src/occupancy_grid.cpp:152):
-//   indexVector = (position - 0.5*length - mapPosition) / resolution, index = (int)(-indexVector)
-//   inside iff t = -(position - mapPosition - 0.5*length), 0 <= t < length
-__device__ __forceinline__ bool get_index(const GridParams &g, double x, double y, int &ix, int &iy)
-{
-  const double tx = -((x - g.pos_x) - g.off_x);
-  const double ty = -((y - g.pos_y) - g.off_y);
-  if (!(tx >= 0.0 && ty >= 0.0 && tx < g.len_x && ty < g.len_y)) return false;  // NaN/inf land here
-  const double vx = ((x - g.off_x) - g.pos_x) / g.res;
-  const double vy = ((y - g.off_y) - g.pos_y) / g.res;
-  const int jx = (int)(-vx);
-  const int jy = (int)(-vy);
-  if (jx < 0 || jy < 0 || jx >= g.nx || jy >= g.ny) return false;
-  ix = jx;
-  iy = jy;
-  return true;
-}
-
+// (the exact getIndex, get_index, is gv_types.hpp's: one text for host and device)
 // Same result as get_index without the two fp64 divisions (the points pass is bound by fp64
 // issue, a division is ~15 dependent fp64 ops): (int)(-(d / res)) only depends on which side
 // of an integer the correctly rounded quotient lies.  q' = (-d) * fl(1/res) is within 3 roundings

@@ -27,7 +27,7 @@ __device__ __forceinline__ int move_source(const GridMoveArgs &a, double hx, dou
 
 // nx % 4 == 0: a lane resamples 4 consecutive cells of one row and writes them as one float4 per float layer and one
 // dword of the packed layer (data[G-1-c] order: cells c..c+3 are the bytes G-4-c .. G-1-c, reversed).  A workgroup
-// covers 256 x 4 destination cells; for small yaw their sources are a compact, nearly aligned patch.
+// covers 256 x 4 destination cells (G - 1 - c: data_entry, gv_types.hpp, of the linear cell c); for small yaw their sources are a compact, nearly aligned patch.
 __global__ void __launch_bounds__(256) k_grid_move4(GridMoveArgs a)
 {
   const int ix0 = (int)(blockIdx.x * 64u + threadIdx.x) * 4;

@@ -213,21 +213,6 @@ inline float floor_to_float(double v)
   return f;
 }
 
-// host getIndex (same arithmetic as the device one) for geometry-only queries
-inline bool get_index(const GridParams &g, double x, double y, int &ix, int &iy)
-{
-  const double tx = -((x - g.pos_x) - g.off_x);
-  const double ty = -((y - g.pos_y) - g.off_y);
-  if (!(tx >= 0.0 && ty >= 0.0 && tx < g.len_x && ty < g.len_y)) return false;
-  const double vx = ((x - g.off_x) - g.pos_x) / g.res;
-  const double vy = ((y - g.off_y) - g.pos_y) / g.res;
-  const int jx = (int)(-vx), jy = (int)(-vy);
-  if (jx < 0 || jy < 0 || jx >= g.nx || jy >= g.ny) return false;
-  ix = jx;
-  iy = jy;
-  return true;
-}
-
 // grid_map::GridMap::setGeometry + setPosition as the constructor calls them (src/occupancy_grid.cpp:10-11): the
 // geometry gv_create gives a handle.  false for what gv_create rejects.
 inline bool grid_params(uint8_t grid_x, uint8_t grid_y, double resolution, GridParams &g)
@@ -314,12 +299,12 @@ inline void nav_step_table(const gv_nav_config &c, uint32_t table[256])
   for (uint32_t v = 0; v < 256; ++v) table[v] = nav_step(s, v);
 }
 
-// the field entry (OccupancyGrid.data order) of a seed, through the grid's own getIndex; -1 off the map or non-finite
+// the field entry (data_entry) of a seed, through the grid's own getIndex (gv_types.hpp: the kernels' text); -1 off the map or non-finite
 inline int32_t nav_seed_entry(const GridParams &g, float x, float y)
 {
   int ix = 0, iy = 0;
   if (!get_index(g, (double)x, (double)y, ix, iy)) return -1;
-  return g.G - 1 - (iy * g.nx + ix);
+  return data_entry(g, ix, iy);
 }
 
 // ---- [EXTENSION] ego-motion compensation (gv_grid_move) ----

@@ -786,7 +786,7 @@ __global__ void __launch_bounds__(256) k_finalize_vec4(FinalizeArgs a)
     p4.x = sigmoid_ref(l4.x); p4.y = sigmoid_ref(l4.y); p4.z = sigmoid_ref(l4.z); p4.w = sigmoid_ref(l4.w);
     *reinterpret_cast<float4 *>(a.log_odds + c) = l4;
     *reinterpret_cast<float4 *>(a.occupancy + c) = p4;
-    // data[G-1-cell]: cells c..c+3 land at G-4-c .. G-1-c in reverse order
+    // data[G-1-cell] (data_entry, gv_types.hpp, of the linear cell): cells c..c+3 land at G-4-c .. G-1-c in reverse order
     const uint32_t packed = ((uint32_t)(uint8_t)pack_i8(p4.w)) | ((uint32_t)(uint8_t)pack_i8(p4.z) << 8)
                             | ((uint32_t)(uint8_t)pack_i8(p4.y) << 16) | ((uint32_t)(uint8_t)pack_i8(p4.x) << 24);
     *reinterpret_cast<uint32_t *>(a.occ_i8 + ((int64_t)a.g.G - 4 - c)) = packed;

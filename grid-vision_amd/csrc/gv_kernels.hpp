@@ -132,7 +132,7 @@ struct TrajArgs {
   gv_footprint fp;
   const float *poses;           // K * P * 3 (device)
   int32_t K, P;
-  const uint8_t *cost;          // G, OccupancyGrid.data order: cell (ix, iy) is byte G - 1 - (iy * nx + ix)
+  const uint8_t *cost;          // G, OccupancyGrid.data order: cell (ix, iy) is byte data_entry(g, ix, iy)
   gv_traj_score *scores;        // K records (device memory, or the device view of pinned host memory; 16-byte aligned)
   uint8_t *pose_cost;           // K * P, or null
 };

@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(256) k_score_nav(NavScoreArgs a)
   const int lane = (int)threadIdx.x & 63;
   const int k = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
   if (k >= a.K) return;
-  const int P = a.P, nx = a.g.nx, G = a.g.G;
+  const int P = a.P, G = a.g.G;
   const float *traj = a.poses + (size_t)k * (size_t)P * 3u;
   unsigned long long sum = 0ull;        // per lane
   unsigned long long key = ~0ull;       // per lane: (value << 32) | pose of the smallest good value this lane saw
@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(256) k_score_nav(NavScoreArgs a)
       const float *q = traj + (size_t)p * 3u;
       int ix = 0, iy = 0;
       if (get_index(a.g, (double)q[0], (double)q[1], ix, iy)) {
-        const int c = G - 1 - (iy * nx + ix);
+        const int c = data_entry(a.g, ix, iy);
         if ((unsigned)c < (unsigned)G) v = a.field[c];
       }
     }

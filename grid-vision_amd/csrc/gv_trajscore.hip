@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(256) k_score_trajectories(TrajArgs a)
   const int k = (int)blockIdx.x;
   if (k >= a.K) return;
   const int n = a.fp.n_vertices, P = a.P;
-  const int nx = a.g.nx, ny = a.g.ny, last = a.g.G - 1;
+  const int nx = a.g.nx, ny = a.g.ny, last = a.g.G - 1;   // last - (iy * nx + ix) is data_entry (gv_types.hpp), G - 1 hoisted
   const float *traj = a.poses + (size_t)k * (size_t)P * 3u;
 
   if (tid < kChunk) {

@@ -1,5 +1,6 @@
 // gv_types.hpp -- POD parameter blocks shared by the host side (gv_api*.hip)
-// and the gfx950 kernels (gv_kernels.hip).  Passed by value as kernel arguments.
+// and the gfx950 kernels (gv_kernels.hip), passed by value as kernel arguments, and the few functions of the grid's
+// geometry that host and device evaluate from one text (GV_HD, as gv_line.hpp does).
 #pragma once
 
 #include <stdint.h>
@@ -20,6 +21,30 @@ struct GridParams {
   double off_x, off_y;   // 0.5 * len
   double inv_res;        // fl64(1 / res): quotient estimate of the points pass (never the result itself)
 };
+
+// grid_map::GridMap::getIndex (called at src/occupancy_grid.cpp:152), the one text of it for the kernels and for the
+// host twins of gv_host_math.hpp (footprint_cells, nav_seed_entry, the sensor origin's cell):
+//   indexVector = (position - 0.5*length - mapPosition) / resolution, index = (int)(-indexVector)
+//   inside iff t = -(position - mapPosition - 0.5*length), 0 <= t < length
+// Built with -ffp-contract=off everywhere: separate roundings, exact fp64 divisions.
+GV_HD bool get_index(const GridParams &g, double x, double y, int &ix, int &iy)
+{
+  const double tx = -((x - g.pos_x) - g.off_x);
+  const double ty = -((y - g.pos_y) - g.off_y);
+  if (!(tx >= 0.0 && ty >= 0.0 && tx < g.len_x && ty < g.len_y)) return false;  // NaN/inf land here
+  const double vx = ((x - g.off_x) - g.pos_x) / g.res;
+  const double vy = ((y - g.off_y) - g.pos_y) / g.res;
+  const int jx = (int)(-vx);
+  const int jy = (int)(-vy);
+  if (jx < 0 || jy < 0 || jx >= g.nx || jy >= g.ny) return false;
+  ix = jx;
+  iy = jy;
+  return true;
+}
+
+// The OccupancyGrid.data order rule (toOccupancyGrid, src/occupancy_grid.cpp): cell (ix, iy) of a layer stored in that
+// order -- the packed grid, the costmap, the distance field -- is entry G - 1 - (iy * nx + ix).
+GV_HD int32_t data_entry(const GridParams &g, int ix, int iy) { return g.G - 1 - (iy * g.nx + ix); }
 
 // Row-major 3x4 fp32 rigid transform (the top of PCL's 4x4).
 struct Mat34f {

@@ -210,6 +210,21 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _pose_batch(poses, device_ptr, K=None, P=None):
+    """(src, K, P, flags) of a (K, P, 3) pose batch for the scoring calls.  The asynchronous calls give K and P and their
+    array is used where it is (it stays the caller's until completion); otherwise K and P come from the shape and host
+    poses are read from a contiguous float32 copy, which the returned pointer keeps alive.  device_ptr: the floats are
+    read from that device address and only the shape of `poses` is used."""
+    if K is None:
+        shape = np.shape(poses)
+        assert len(shape) == 3 and shape[2] == 3, "poses is (K, P, 3)"
+        K, P = int(shape[0]), int(shape[1])
+        poses = _f32(poses) if device_ptr is None else None
+    if device_ptr is not None:
+        return C.c_void_p(device_ptr), K, P, TRAJ_DEVICE_POSES
+    return _ptr(poses), K, P, 0
+
+
 def make_tf(v):
     return Transform(*[float(t) for t in v]) if v is not None else None
 
@@ -611,8 +626,8 @@ class GridVisionHIP:
         """enqueue on stream(): poses float32 (K, P, 3) host array that stays unchanged until completion (or
         device_ptr: the address of K * P * 3 floats in device memory), scores a TRAJ_SCORE_DTYPE array of K, pose_cost
         None or a uint8 array of K * P; both complete after synchronize()"""
-        flags = (TRAJ_KEEP_POSE_COST if pose_cost is not None else 0) | (TRAJ_DEVICE_POSES if device_ptr is not None else 0)
-        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(poses)
+        src, K, P, flags = _pose_batch(poses, device_ptr, K, P)
+        flags |= TRAJ_KEEP_POSE_COST if pose_cost is not None else 0
         self._ck(self._lib.gv_score_trajectories_async(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags),
                                                        _ptr(scores), _ptr(pose_cost)), "gv_score_trajectories_async")
 
@@ -620,14 +635,10 @@ class GridVisionHIP:
         """poses: float32 (K, P, 3) of (x, y, yaw) in the grid's frame (with device_ptr only its shape is used: the
         floats are read from that device address).  Returns the TRAJ_SCORE_DTYPE array of K, and with keep_pose_cost
         also the uint8 (K, P) pose costs."""
-        shape = np.shape(poses)
-        assert len(shape) == 3 and shape[2] == 3, "poses is (K, P, 3)"
-        K, P = int(shape[0]), int(shape[1])
-        p = _f32(poses) if device_ptr is None else None
+        src, K, P, flags = _pose_batch(poses, device_ptr)
+        flags |= TRAJ_KEEP_POSE_COST if keep_pose_cost else 0
         scores = np.zeros(K, TRAJ_SCORE_DTYPE)
         pc = np.zeros(K * P, np.uint8) if keep_pose_cost else None
-        flags = (TRAJ_KEEP_POSE_COST if keep_pose_cost else 0) | (TRAJ_DEVICE_POSES if device_ptr is not None else 0)
-        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(p)
         self._ck(self._lib.gv_score_trajectories(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores),
                                                  _ptr(pc)), "gv_score_trajectories")
         return (scores, pc.reshape(K, P)) if keep_pose_cost else scores
@@ -665,22 +676,16 @@ class GridVisionHIP:
     def score_nav_async(self, poses, K, P, scores, device_ptr=None):
         """enqueue on stream(): poses as in score_trajectories_async, scores a NAV_SCORE_DTYPE array of K; complete
         after synchronize()"""
-        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(poses)
-        self._ck(self._lib.gv_score_nav_async(self._h, src, C.c_int32(K), C.c_int32(P),
-                                              C.c_uint32(TRAJ_DEVICE_POSES if device_ptr is not None else 0), _ptr(scores)),
+        src, K, P, flags = _pose_batch(poses, device_ptr, K, P)
+        self._ck(self._lib.gv_score_nav_async(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores)),
                  "gv_score_nav_async")
 
     def score_nav(self, poses, device_ptr=None):
         """poses: float32 (K, P, 3) as in score_trajectories (the yaw is never read).  Returns the NAV_SCORE_DTYPE array
         of K."""
-        shape = np.shape(poses)
-        assert len(shape) == 3 and shape[2] == 3, "poses is (K, P, 3)"
-        K, P = int(shape[0]), int(shape[1])
-        p = _f32(poses) if device_ptr is None else None
+        src, K, P, flags = _pose_batch(poses, device_ptr)
         scores = np.zeros(K, NAV_SCORE_DTYPE)
-        src = C.c_void_p(device_ptr) if device_ptr is not None else _ptr(p)
-        self._ck(self._lib.gv_score_nav(self._h, src, C.c_int32(K), C.c_int32(P),
-                                        C.c_uint32(TRAJ_DEVICE_POSES if device_ptr is not None else 0), _ptr(scores)),
+        self._ck(self._lib.gv_score_nav(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores)),
                  "gv_score_nav")
         return scores
 

@@ -12,6 +12,7 @@ import pytest
 import inflate_cases as ic
 import inflate_ref as ref
 from gvamd import synth
+from planner_util import plant_grid
 from test_gpu_parity import _ground_scene, make_handle
 
 pytestmark = pytest.mark.gpu
@@ -50,16 +51,6 @@ def _want(i8, nx, ny, cfg, res):
     return _REF[key]
 
 
-def _plant(h, mask):
-    """lethal (97) where the data-order mask says so, free (11) elsewhere; returns the int8 readback"""
-    lo = np.where(mask.reshape(-1)[::-1], np.float32(10.0), np.float32(-10.0)).astype(np.float32)   # cell = G-1-byte
-    h.set_log_odds(lo)
-    h.update_map()
-    i8 = h.to_occupancy_grid()[0]
-    assert np.array_equal(i8.reshape(mask.shape) >= 65, mask)
-    return i8
-
-
 def _set(h, cfg):
     h.set_inflation(cfg.inscribed, cfg.inflation, cfg.scaling, cfg.thr, keep_dist2=bool(cfg.flags & ref.KEEP_DIST2),
                     occupancy_scale=bool(cfg.flags & ref.OCCUPANCY_SCALE))
@@ -95,7 +86,7 @@ def test_single_cell(gvamd, grid, pset):
     h, res = _handle(gvamd, grid)
     pres, cfg = ic.PSETS[pset]
     assert pres == res
-    i8 = _plant(h, ic.single_cell(h.nx, h.ny))
+    i8 = plant_grid(h, ic.single_cell(h.nx, h.ny))
     cost, d2 = _check(h, i8, cfg, res, (grid, pset))
     table = ref.cost_table(cfg, res)
     assert (cost == 254).sum() == 1 and (d2 != ref.NONE).sum() > 4 and int(d2[d2 != ref.NONE].max()) <= len(table) - 1
@@ -111,7 +102,7 @@ def test_borders(gvamd, grid, pset):
     h, res = _handle(gvamd, grid)
     _, cfg = ic.PSETS[pset]
     rc = int(np.sqrt(ref.d2max_of(cfg, res)))
-    i8 = _plant(h, ic.border_fixture(h.nx, h.ny, rc))
+    i8 = plant_grid(h, ic.border_fixture(h.nx, h.ny, rc))
     cost, d2 = _check(h, i8, cfg, res, (grid, pset))
     y = h.ny // 2
     assert cost[y, h.nx - 1] == 254 and cost[y + 1, 0] == 0 and d2[y + 1, 0] == ref.NONE   # the reference: no wrap
@@ -120,7 +111,7 @@ def test_borders(gvamd, grid, pset):
 def test_seams_p1(gvamd):
     h, res = _handle(gvamd, "2000x2000")
     mask, probes = ic.seam_fixture(h.nx, h.ny, 30, ic.seam_anchors_p1(), spacing=16)
-    i8 = _plant(h, mask)
+    i8 = plant_grid(h, mask)
     cost, d2 = _check(h, i8, ic.PSETS["P1"][1], res, "seams P1")
     for x, y, d in probes:
         assert d2[y, x] == (d if d <= 30 else ref.NONE)
@@ -130,7 +121,7 @@ def test_seams_p1(gvamd):
 def test_seams_p3(gvamd, k):
     h, res = _handle(gvamd, "200x200")
     mask, probes = ic.seam_fixture(h.nx, h.ny, 4019, ic.seam_anchors_p3(k), spacing=97)
-    i8 = _plant(h, mask)
+    i8 = plant_grid(h, mask)
     cost, d2 = _check(h, i8, ic.PSETS["P3"][1], res, ("seams P3", k))
     for x, y, d in probes:
         assert d2[y, x] == (d if d <= 4019 else ref.NONE)
@@ -141,7 +132,7 @@ def test_seams_p3(gvamd, k):
 @pytest.mark.parametrize("density", [5e-4, 0.3])
 def test_random_masks(gvamd, grid, pset, density):
     h, res = _handle(gvamd, grid)
-    i8 = _plant(h, ic.random_mask(h.nx, h.ny, density, seed=11))
+    i8 = plant_grid(h, ic.random_mask(h.nx, h.ny, density, seed=11))
     _check(h, i8, ic.PSETS[pset][1], res, (grid, pset, density))
 
 
@@ -149,10 +140,10 @@ def test_random_masks(gvamd, grid, pset, density):
 def test_row_column_empty_and_full(gvamd, grid, pset):
     h, res = _handle(gvamd, grid)
     cfg = ic.PSETS[pset][1]
-    _check(h, _plant(h, ic.row_and_column(h.nx, h.ny)), cfg, res, "row and column")
-    cost, d2 = _check(h, _plant(h, np.zeros((h.ny, h.nx), bool)), cfg, res, "empty")
+    _check(h, plant_grid(h, ic.row_and_column(h.nx, h.ny)), cfg, res, "row and column")
+    cost, d2 = _check(h, plant_grid(h, np.zeros((h.ny, h.nx), bool)), cfg, res, "empty")
     assert not cost.any() and (d2 == ref.NONE).all()
-    cost, d2 = _check(h, _plant(h, np.ones((h.ny, h.nx), bool)), cfg, res, "full")
+    cost, d2 = _check(h, plant_grid(h, np.ones((h.ny, h.nx), bool)), cfg, res, "full")
     assert (cost == 254).all() and not d2.any()
 
 
@@ -192,7 +183,7 @@ def test_threshold(gvamd, thr):
 def test_flags(gvamd):
     h, res = _handle(gvamd, "250x100")
     cfg = ic.PSETS["P2"][1]
-    i8 = _plant(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=4))
+    i8 = plant_grid(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=4))
     plain, _ = _check(h, i8, cfg, res, "plain")
     scaled, _ = _check(h, i8, cfg._replace(flags=ref.OCCUPANCY_SCALE), res, "occupancy scale")
     assert scaled.max() == 100 and plain.max() == 254 and np.array_equal(scaled == 0, plain == 0)
@@ -287,7 +278,7 @@ def test_reconfiguration_in_flight(gvamd):
     """inflate with P1, publish, set P2, inflate, publish, (and P1 again: the first table's slot is reused), one
     synchronize: each buffer matches its own table"""
     h, res = _handle(gvamd, "500x200")
-    i8 = _plant(h, ic.random_mask(h.nx, h.ny, 1e-3, seed=21))
+    i8 = plant_grid(h, ic.random_mask(h.nx, h.ny, 1e-3, seed=21))
     cfgs = [ic.PSETS["P1"][1], ic.PSETS["P2"][1], ic.PSETS["P1"][1]._replace(flags=ref.OCCUPANCY_SCALE)]
     want = [_want(i8, h.nx, h.ny, c, res)[0] for c in cfgs]
     pins = [gvamd.PinnedI8(h.G) for _ in cfgs]
@@ -326,12 +317,12 @@ def test_state_rules(gvamd):
         with pytest.raises(gvamd.GVError) as e:             # a rejected configuration leaves the one in force alone
             h.set_inflation(0.35, 0.2, 10.0, 65)
         assert e.value.code == 1
-        i8 = _plant(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=8))
+        i8 = plant_grid(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=8))
         want, want_d = _want(i8, h.nx, h.ny, cfg, res)
         h.inflate()
         assert h.costmap().tobytes() == want.tobytes() and h.obstacle_dist2().tobytes() == want_d.tobytes()
         # a later map update leaves the snapshot alone until the next inflate
-        i8b = _plant(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=9))
+        i8b = plant_grid(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=9))
         assert i8b.tobytes() != i8.tobytes()
         assert h.costmap().tobytes() == want.tobytes()
         h.inflate()
@@ -340,7 +331,7 @@ def test_state_rules(gvamd):
         # gv_reset invalidates the costmap and keeps the configuration; so does gv_grid_move keep it
         h.reset()
         assert state_error(h.costmap) and state_error(h.obstacle_dist2)
-        _plant(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=9))
+        plant_grid(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=9))
         assert h.grid_move([0.0, 0.0, 0.0, 1.0, 3 * res, -2 * res, 0.0])["applied"]
         h.inflate()
         moved = h.to_occupancy_grid()[0]

@@ -1,5 +1,5 @@
 """[EXTENSION] X9 goal / path distance field on the device: gv_nav_field against nav_ref (a heap Dijkstra, one cell after
-the other) and gv_score_nav against nav_ref's loops, with zero tolerance.  Walls are planted as test_gpu_traj._plant does,
+the other) and gv_score_nav against nav_ref's loops, with zero tolerance.  Walls are planted by planner_util.plant,
 inflated on the device, and the costmap() READBACK goes to the reference.  Every comparison is tobytes() equality, every
 call is made three times with the same bytes.  Then the 2000 x 2000 map against a closed form, the sampler's input and
 output paths, the ordering and state rules of the header, the pass cap's own path, and the example."""
@@ -14,8 +14,8 @@ import pytest
 import nav_cases as nc
 import nav_ref as ref
 import traj_cases as tc
+from planner_util import first_diff, hip_runtime, plant
 from test_gpu_parity import _ground_scene, make_handle
-from test_gpu_traj import _hip, _plant
 
 pytestmark = pytest.mark.gpu
 
@@ -54,11 +54,6 @@ def _want(g, cost, cfg, seeds):
     return _WANT[key]
 
 
-def _first_diff(got, want):
-    bad = np.flatnonzero(np.asarray(got).reshape(-1) != np.asarray(want).reshape(-1))
-    return None if not len(bad) else dict(n=len(bad), at=int(bad[0]), got=int(got.reshape(-1)[bad[0]]), want=int(want.reshape(-1)[bad[0]]))
-
-
 def _solve(h, g, cost, cfg, seeds, tag=""):
     """three calls, each equal to the reference byte for byte; returns (field, the last call's info)"""
     want, used = _want(g, cost, cfg, seeds)
@@ -66,7 +61,7 @@ def _solve(h, g, cost, cfg, seeds, tag=""):
     for rep in range(3):
         info = h.nav_field(seeds)
         got = h.nav_field_array()
-        assert got.dtype == np.uint32 and got.tobytes() == want.tobytes(), (tag, cfg, rep, _first_diff(got, want))
+        assert got.dtype == np.uint32 and got.tobytes() == want.tobytes(), (tag, cfg, rep, first_diff(got, want))
         assert info["n_seeds_used"] == used and info["rounds"] >= 1, (tag, cfg, rep, info)
     return want, info
 
@@ -85,7 +80,7 @@ def test_fixtures(gvamd, name, seeds):
     c = nc.cases()[name]
     g = nc.grid_of(c["grid"])
     h = _handle(gvamd, c["grid"])
-    cost = _plant(h, c["mask"], c["inflation"])
+    cost = plant(h, c["mask"], c["inflation"])
     assert cost.tobytes() == c["cost"].tobytes()          # the host tests ran on the same costmap
     for cfg in nc.CONFIGS:
         want, info = _solve(h, g, cost, cfg, c[seeds], tag=(name, seeds))
@@ -107,18 +102,18 @@ def test_empty_and_full_map(gvamd):
     and on each border; the full map is blocked everywhere and no seed is used."""
     g = nc.grid_of("250x100")
     h = _handle(gvamd, "250x100")
-    cost = _plant(h, np.zeros((g.ny, g.nx), bool), nc.EXACT)
+    cost = plant(h, np.zeros((g.ny, g.nx), bool), nc.EXACT)
     ys, xs = np.mgrid[0:g.ny, 0:g.nx]
     for sx, sy in ((g.nx // 2, g.ny // 2), (0, 0), (g.nx - 1, g.ny - 1), (0, g.ny // 2), (g.nx - 1, g.ny // 2), (g.nx // 2, 0),
                    (g.nx // 2, g.ny - 1)):
         seeds = np.array([nc.world_of(g, sx, sy)], np.float32)
         want, _ = _solve(h, g, cost, (253, 0), seeds, tag=("empty", sx, sy))
         assert np.array_equal(want.reshape(g.ny, g.nx), np.abs(xs - sx) + np.abs(ys - sy))
-    cost = _plant(h, np.ones((g.ny, g.nx), bool), nc.EXACT)
+    cost = plant(h, np.ones((g.ny, g.nx), bool), nc.EXACT)
     want, info = _solve(h, g, cost, (253, 0), seeds, tag="full")
     assert (want == ref.BLOCKED).all() and info["n_seeds_used"] == 0
     # no usable seed on a map with free cells: unreachable everywhere, not an error
-    cost = _plant(h, np.zeros((g.ny, g.nx), bool), nc.EXACT)
+    cost = plant(h, np.zeros((g.ny, g.nx), bool), nc.EXACT)
     want, info = _solve(h, g, cost, (253, 0), np.array([(1e6, 0.0), (np.nan, 0.0)], np.float32), tag="no seed")
     assert (want == ref.UNREACHABLE).all() and info["n_seeds_used"] == 0
 
@@ -135,7 +130,7 @@ def test_2000x2000_wall_with_one_gap(gvamd):
         mask = np.zeros((ny, nx), bool)
         mask[:, xw] = True
         mask[yg, xw] = False
-        _plant(h, mask, nc.EXACT)
+        plant(h, mask, nc.EXACT)
         ys, xs = np.mgrid[0:ny, 0:nx]
         to_gap = abs(xw - sx) + abs(yg - sy)
         want = np.where(xs < xw, np.abs(xs - sx) + np.abs(ys - sy), to_gap + (xs - xw) + np.abs(ys - yg)).astype(np.uint32)
@@ -146,7 +141,7 @@ def test_2000x2000_wall_with_one_gap(gvamd):
         for rep in range(3):
             info = h.nav_field(seeds)
             got = h.nav_field_array()
-            assert got.tobytes() == want.tobytes(), (rep, _first_diff(got, want))
+            assert got.tobytes() == want.tobytes(), (rep, first_diff(got, want))
             assert info["n_seeds_used"] == 1
         # the overflow rule: (1 + w * 252) * (G - 1) <= 0xFFFFFFFD admits the weights 0..4 here
         h.set_nav_config(253, 4)
@@ -171,11 +166,11 @@ def test_pass_cap_path(gvamd):
     finally:
         del os.environ["GV_NAV_PASS_CAP"]
     try:
-        cost = _plant(h, c["mask"], c["inflation"])
+        cost = plant(h, c["mask"], c["inflation"])
         want, info = _solve(h, g, cost, (253, 0), c["goal"], tag="cap 3")
         assert info["rounds"] >= 10
         h2 = _handle(gvamd, c["grid"])
-        _plant(h2, c["mask"], c["inflation"])
+        plant(h2, c["mask"], c["inflation"])
         _, info2 = _solve(h2, g, cost, (253, 0), c["goal"], tag="cap 40")
         assert info2["rounds"] < info["rounds"]
     finally:
@@ -195,7 +190,7 @@ def test_sampler_paths(gvamd, family, case):
     assert f["grid"] == c["grid"]
     g = nc.grid_of(c["grid"])
     h = _handle(gvamd, c["grid"])
-    cost = _plant(h, c["mask"], c["inflation"])
+    cost = plant(h, c["mask"], c["inflation"])
     fld, _ = _solve(h, g, cost, (253, 3), c["goal"], tag=case)
     poses = f["poses"]
     K, P = poses.shape[:2]
@@ -207,7 +202,7 @@ def test_sampler_paths(gvamd, family, case):
         assert want[6].tobytes() == want[0].tobytes() == want[7].tobytes()
     if family == "point_257x2":
         assert (want["best_pose"] == -1).any() and (want["best_pose"] >= 0).any()
-    hip, dptr = _hip(), C.c_void_p()
+    hip, dptr = hip_runtime(), C.c_void_p()
     assert hip.hipMalloc(C.byref(dptr), poses.nbytes) == 0
     pin_s, pin_in = gvamd.PinnedI8(K * 24 + 16), gvamd.PinnedF32(poses.size)
     try:
@@ -215,7 +210,7 @@ def test_sampler_paths(gvamd, family, case):
         pin_in.array[:] = poses.reshape(-1)
         for rep in range(3):
             got = h.score_nav(poses)
-            assert got.dtype == ref.SCORE_DTYPE and got.tobytes() == want.tobytes(), (rep, _first_diff(got.view(np.uint32), want.view(np.uint32)))
+            assert got.dtype == ref.SCORE_DTYPE and got.tobytes() == want.tobytes(), (rep, first_diff(got.view(np.uint32), want.view(np.uint32)))
             assert h.score_nav(poses, device_ptr=dptr.value).tobytes() == want.tobytes(), ("device poses", rep)
             for src, dev in ((pin_in.array, None), (poses, None), (None, dptr.value)):
                 pin_s.array[:] = 77
@@ -237,6 +232,48 @@ def test_sampler_paths(gvamd, family, case):
         pin_in.close()
 
 
+def test_samplers_back_to_back_share_the_pose_copy(gvamd):
+    """gv_score_trajectories_async (3 x 65: across the 64-pose chunk), gv_score_nav_async (5 x 130, other poses: the
+    handle's device copy of host poses grows while the first call may be in flight) and gv_score_trajectories_async
+    (2 x 1) with no synchronisation between them, pageable poses and destinations: every record equals the reference
+    of its own poses.  Then the same with the middle call's poses read from device memory."""
+    import traj_ref
+    c = nc.cases()["random_5e-4"]
+    g, fp = nc.grid_of(c["grid"]), tc.fp_of("rect")
+    h = _handle(gvamd, c["grid"])
+    cost = plant(h, c["mask"], c["inflation"])
+    fld, _ = _solve(h, g, cost, (253, 3), c["goal"], tag="shared poses")
+    h.set_footprint(tc.FOOTPRINTS["rect"])
+    box = (0.0, 32.0, -4.0, 4.0)
+    first = tc.arcs("shared_first", g, fp, 3, 65, 900, box, 0.04)
+    middle = tc.arcs("shared_middle", g, tc.fp_of("point"), 5, 130, 910, box, 0.1)
+    last = tc.arcs("shared_last", g, fp, 2, 1, 920, box, 0.04)
+    want_first, want_last = traj_ref.score(g, fp, cost, first), traj_ref.score(g, fp, cost, last)
+    want_middle = ref.score(g, fld, middle)
+    assert first.tobytes() != middle[:3, :65].tobytes()
+    hip, dptr = hip_runtime(), C.c_void_p()
+    assert hip.hipMalloc(C.byref(dptr), middle.nbytes) == 0
+    try:
+        assert hip.hipMemcpy(dptr, middle.ctypes.data, middle.nbytes, 1) == 0   # hipMemcpyHostToDevice
+        for dev in (None, dptr.value):
+            s1, p1 = np.zeros(3, traj_ref.SCORE_DTYPE), np.full(3 * 65, 77, np.uint8)
+            s2 = np.zeros(5, ref.SCORE_DTYPE)
+            s3, p3 = np.zeros(2, traj_ref.SCORE_DTYPE), np.full(2, 77, np.uint8)
+            h.score_trajectories_async(first, 3, 65, s1, p1)
+            h.score_nav_async(None if dev else middle, 5, 130, s2, device_ptr=dev)
+            h.score_trajectories_async(last, 2, 1, s3, p3)
+            h.synchronize()
+            for name in traj_ref.SCORE_DTYPE.names:
+                assert np.array_equal(s1[name], want_first[0][name]), (dev is not None, "first", name, s1, want_first[0])
+                assert np.array_equal(s3[name], want_last[0][name]), (dev is not None, "last", name, s3, want_last[0])
+            for name in ref.SCORE_DTYPE.names:
+                assert np.array_equal(s2[name], want_middle[name]), (dev is not None, "middle", name, s2, want_middle)
+            assert p1.tobytes() == want_first[1].tobytes(), (dev is not None, "first", first_diff(p1, want_first[1]))
+            assert p3.tobytes() == want_last[1].tobytes(), (dev is not None, "last", first_diff(p3, want_last[1]))
+    finally:
+        hip.hipFree(dptr)
+
+
 # ------------------------------------------------------------------------------------------- ordering and state --
 def _code(gvamd, call):
     with pytest.raises(gvamd.GVError) as e:
@@ -249,10 +286,10 @@ def test_snapshot_config_change_and_reset(gvamd):
     g = nc.grid_of("250x100")
     h = _handle(gvamd, "250x100")
     poses = tc.families()["nonfinite_8x3"]["poses"]
-    cost1 = _plant(h, c1["mask"], c1["inflation"])
+    cost1 = plant(h, c1["mask"], c1["inflation"])
     f1, _ = _solve(h, g, cost1, (253, 0), c1["goal"])
     # a second gv_inflate of another map, a move and a changed configuration do not touch the field: it is a snapshot
-    cost2 = _plant(h, c2["mask"], c2["inflation"])
+    cost2 = plant(h, c2["mask"], c2["inflation"])
     assert cost2.tobytes() != cost1.tobytes()
     h.set_nav_config(254, 3)
     assert h.grid_move([0.0, 0.0, 0.0, 1.0, 3 * g.res, -2 * g.res, 0.0])["applied"]
@@ -265,7 +302,7 @@ def test_snapshot_config_change_and_reset(gvamd):
     c3 = nc.cases()["random_5e-4"]
     g5 = nc.grid_of("500x200")
     h5 = _handle(gvamd, "500x200")
-    cost3 = _plant(h5, c3["mask"], c3["inflation"])
+    cost3 = plant(h5, c3["mask"], c3["inflation"])
     a, _ = _solve(h5, g5, cost3, (253, 0), c3["goal"])
     b, _ = _solve(h5, g5, cost3, (253, 3), c3["goal"])
     assert a.tobytes() != b.tobytes()
@@ -277,7 +314,7 @@ def test_snapshot_config_change_and_reset(gvamd):
     h.reset()
     for call in (h.nav_field_array, h.device_nav_field, lambda: h.score_nav(poses), lambda: h.nav_field(c1["goal"])):
         assert _code(gvamd, call) == GV_ERR_STATE
-    cost1b = _plant(h, c1["mask"], c1["inflation"])
+    cost1b = plant(h, c1["mask"], c1["inflation"])
     info = h.nav_field(c1["goal"])
     assert info["n_seeds_used"] == 1 and h.nav_field_array().tobytes() == _want(g, cost1b, (254, 3), c1["goal"])[0].tobytes()
     assert h.device_nav_field()
@@ -298,7 +335,7 @@ def test_state_and_argument_rules(gvamd):
         assert _code(gvamd, h.nav_field_array) == GV_ERR_STATE and _code(gvamd, h.device_nav_field) == GV_ERR_STATE
         assert _code(gvamd, lambda: h.score_nav(poses)) == GV_ERR_STATE
         h.set_nav_config(None)
-        cost = _plant(h, c["mask"], c["inflation"])
+        cost = plant(h, c["mask"], c["inflation"])
         assert _code(gvamd, solve) == GV_ERR_STATE                    # a costmap, no configuration
         # a rejected configuration leaves the one in force alone
         h.set_nav_config(253, 3)
@@ -330,7 +367,7 @@ def test_state_and_argument_rules(gvamd):
         # the configuration is kept through gv_set_log_odds and gv_reset; gv_reset invalidates the field
         h.reset()
         assert _code(gvamd, h.nav_field_array) == GV_ERR_STATE
-        cost = _plant(h, c["mask"], c["inflation"])
+        cost = plant(h, c["mask"], c["inflation"])
         h.nav_field(c["goal"])
         assert h.nav_field_array().tobytes() == want.tobytes()
     finally:

@@ -16,6 +16,7 @@ import pytest
 import traj_cases as tc
 import traj_ref as ref
 from gvamd import synth
+from planner_util import first_diff, hip_runtime, plant
 from test_gpu_parity import _ground_scene, make_handle
 
 pytestmark = pytest.mark.gpu
@@ -53,16 +54,8 @@ def _handle(gvamd, grid):
 
 
 def _plant(h, mask, inflation=None):
-    """lethal (97) where the data-order mask says so, free (11) elsewhere, then gv_inflate; returns the costmap readback"""
-    lo = np.where(mask.reshape(-1)[::-1], np.float32(10.0), np.float32(-10.0)).astype(np.float32)   # cell = G-1-byte
-    h.set_log_odds(lo)
-    h.update_map()
-    assert np.array_equal(h.to_occupancy_grid()[0].reshape(mask.shape) >= 65, mask)
-    h.set_inflation(*(inflation or INFLATION[_RES[(h.nx, h.ny)]]))
-    h.inflate()
-    cost = h.costmap()
-    assert np.array_equal(cost.reshape(mask.shape) == 254, mask)
-    return cost
+    """planner_util.plant with the module's inflation for the grid's resolution unless one is given"""
+    return plant(h, mask, inflation or INFLATION[_RES[(h.nx, h.ny)]])
 
 
 def _want(name, cost, collision=253, off_map=255):
@@ -73,12 +66,6 @@ def _want(name, cost, collision=253, off_map=255):
     return ref.score(g, fp, cost, f["poses"], _CELLS[name])
 
 
-def _first_diff(got, want):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    bad = np.flatnonzero(got != want)
-    return None if not len(bad) else dict(n=len(bad), at=int(bad[0]), got=got[bad[0]], want=want[bad[0]])
-
-
 def _check(h, name, cost, collision=253, off_map=255, tag=""):
     """score three times with and without the pose costs; records and pose costs equal the reference byte for byte"""
     f = tc.families()[name]
@@ -86,8 +73,8 @@ def _check(h, name, cost, collision=253, off_map=255, tag=""):
     h.set_footprint(tc.FOOTPRINTS[f["fp"]], collision, off_map)
     for rep in range(3):
         got_s, got_p = h.score_trajectories(f["poses"], keep_pose_cost=True)
-        assert got_p.dtype == np.uint8 and got_p.tobytes() == want_p.tobytes(), (name, tag, rep, "pose_cost", _first_diff(got_p, want_p))
-        assert got_s.dtype == ref.SCORE_DTYPE and got_s.tobytes() == want_s.tobytes(), (name, tag, rep, _first_diff(got_s, want_s))
+        assert got_p.dtype == np.uint8 and got_p.tobytes() == want_p.tobytes(), (name, tag, rep, "pose_cost", first_diff(got_p, want_p))
+        assert got_s.dtype == ref.SCORE_DTYPE and got_s.tobytes() == want_s.tobytes(), (name, tag, rep, first_diff(got_s, want_s))
         only = h.score_trajectories(f["poses"])
         assert only.tobytes() == want_s.tobytes(), (name, tag, rep, "without pose costs")
     return want_s, want_p
@@ -177,14 +164,6 @@ def test_outline_ends_and_interior(gvamd):
         assert int(got_s["cost_sum"][0]) == (254 if tag == "centre" else 0), tag
 
 
-def _hip():
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipFree.argtypes = [C.c_void_p]
-    return hip
-
-
 @pytest.mark.parametrize("name", ["rect_3x130", "triangle_64x63", "poly16_65x1"])
 def test_device_poses_and_destinations(gvamd, name):
     """poses read in place from a hipMalloc buffer, results into pinned memory (written by the kernel) and into pageable
@@ -196,7 +175,7 @@ def test_device_poses_and_destinations(gvamd, name):
     h.set_footprint(tc.FOOTPRINTS[f["fp"]])
     poses = f["poses"]
     K, P = poses.shape[:2]
-    hip, dptr = _hip(), C.c_void_p()
+    hip, dptr = hip_runtime(), C.c_void_p()
     assert hip.hipMalloc(C.byref(dptr), poses.nbytes) == 0
     pin_s, pin_p, pin_in = gvamd.PinnedI8(K * 16 + 16), gvamd.PinnedI8(K * P), gvamd.PinnedF32(poses.size)
     try:

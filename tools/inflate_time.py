@@ -12,9 +12,6 @@ order, the mean duration of each kernel over the timed passes.  --out FILE appen
 from __future__ import annotations
 
 import argparse
-import csv
-import ctypes as C
-import glob
 import os
 import sys
 
@@ -22,6 +19,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "grid-vision_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import planner_time_common as common  # noqa: E402
 
 # (label, (grid_x, grid_y, res), (inscribed, inflation, scaling), keep_dist2)
 P1, P2, P3 = (0.35, 0.55, 10.0), (0.52, 3.03, 3.0), (0.31, 3.17, 1.5)
@@ -36,19 +35,6 @@ CASES = [
 ]
 THRESHOLD = 65
 KERNELS = ("k_lethal_bits", "k_inflate_tiles")
-
-
-def _poses(synth, h, res, n, seed):
-    rng = np.random.default_rng(seed)
-    lx, ly = h.nx * res, h.ny * res
-    p = np.zeros(n, dtype=synth.LSHAPE_DTYPE)
-    p["px"] = rng.uniform(h.pos_x - 0.55 * lx, h.pos_x + 0.55 * lx, n)
-    p["py"] = rng.uniform(h.pos_y - 0.55 * ly, h.pos_y + 0.55 * ly, n)
-    p["qw"] = 1.0
-    p["length"] = rng.uniform(0.5, 0.1 * lx, n)
-    p["width"] = rng.uniform(0.5, 0.1 * ly, n)
-    p["height"] = 1.5
-    return p
 
 
 def empty_share(lethal, rc):
@@ -69,11 +55,11 @@ def empty_share(lethal, rc):
 def time_case(label, grid, pset, keep, n, warmup):
     import gvamd
     from gvamd import synth
-    hip = C.CDLL("libamdhip64.so")
+    hip = common.load_hip()
     gx, gy, res = grid
     h = gvamd.GridVisionHIP(gx, gy, res)
     for t in range(12):
-        h.update_map_poses(_poses(synth, h, res, 40, 100 + t))
+        h.update_map_poses(common.fill_poses(synth, h, res, 40, 100 + t))
     cfg = gvamd.Inflation(pset[0], pset[1], pset[2], THRESHOLD, gvamd.INFLATE_KEEP_DIST2 if keep else 0)
     table = gvamd.inflation_cost_table(cfg, res)
     rc = int(np.sqrt(len(table) - 1))
@@ -82,22 +68,10 @@ def time_case(label, grid, pset, keep, n, warmup):
     for _ in range(warmup):
         h.inflate()
     h.synchronize()
-    s = C.c_void_p(h.stream())
-    e0, e1 = C.c_void_p(), C.c_void_p()
-    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
-    assert hip.hipEventRecord(e0, s) == 0
-    for _ in range(n):
-        h.inflate()
-    assert hip.hipEventRecord(e1, s) == 0
-    assert hip.hipEventSynchronize(e1) == 0
-    ms = C.c_float()
-    assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-    hip.hipEventDestroy(e0)
-    hip.hipEventDestroy(e1)
+    us = common.event_us_per_call(hip, h, n, h.inflate)
     cost = h.costmap()
     G = h.G
     h.close()
-    us = 1000.0 * ms.value / n
     moved = G + G // 8 + G + (2 * G if keep else 0)
     return (f"{label:20s} {h.nx} x {h.ny} cells at {res} m, Rc {rc:2d}, d2max {len(table) - 1:4d}, lethal {lethal.mean() * 100:5.2f} %, "
             f"cost > 0 {np.count_nonzero(cost) / G * 100:5.2f} %, empty tiles {empty_share(lethal, rc) * 100:5.1f} %: "
@@ -107,15 +81,7 @@ def time_case(label, grid, pset, keep, n, warmup):
 def kernel_times(trace_dir, n, warmup):
     """per case and kernel: mean duration in us of the timed dispatches, from rocprofv3's kernel trace of one run of
     this script (dispatch order = CASES order, warmup + n passes of two kernels each)"""
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    assert files, "no *kernel_trace.csv under " + trace_dir
-    rows = []
-    for f in files:
-        with open(f, newline="") as fh:
-            rows += list(csv.DictReader(fh))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    per = {k: [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if k in r["Kernel_Name"]]
-           for k in KERNELS}
+    per = common.kernel_durations(trace_dir, KERNELS)
     lines = []
     for i, (label, _, _, _) in enumerate(CASES):
         parts = []
@@ -144,9 +110,7 @@ def main():
     if a.trace:
         print("\n".join(lines), flush=True)
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        common.append_out(a.out, lines)
 
 
 if __name__ == "__main__":

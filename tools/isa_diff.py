@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Device assembly of two source trees, file by file (no GPU): the check that a host-side change left the kernels alone.
+
+Compiles every csrc/*.hip of each tree for gfx950 with gvamd/build.py's FLAGS plus --cuda-device-only -S, drops the
+lines that differ between any two builds of one text (the __hip_cuid_* symbol, .file, .ident) and prints, per file,
+`identical` or the number of differing lines.  A file only one tree has is reported as such (a rename: compare it by
+hand with --pair).
+
+    python3 tools/isa_diff.py PARENT_TREE THIS_TREE [--pair OLD.hip=NEW.hip ...] [--keep DIR]
+
+Exit status 0 when every compared file is identical."""
+from __future__ import annotations
+
+import argparse
+import difflib
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "grid-vision_amd"))
+from gvamd import build as gvbuild  # noqa: E402
+
+_VOLATILE = re.compile(r"__hip_cuid_|^\s*\.file\b|^\s*\.ident\b")
+
+
+def csrc_of(tree: str) -> str:
+    return os.path.join(os.path.abspath(tree), "grid-vision_amd", "csrc")
+
+
+def device_asm(csrc: str, src: str, out: str) -> list:
+    """The device assembly of csrc/src without the lines no two builds share."""
+    cmd = [gvbuild.hipcc(), *gvbuild.FLAGS, "--cuda-device-only", "-S", "-o", out, os.path.join(csrc, src)]
+    r = subprocess.run(cmd, cwd=csrc, stderr=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stderr)
+        raise RuntimeError("compile failed: " + os.path.join(csrc, src))
+    with open(out) as f:
+        return [ln for ln in f.read().splitlines() if not _VOLATILE.search(ln)]
+
+
+def differing_lines(a: list, b: list) -> int:
+    return sum(1 for ln in difflib.unified_diff(a, b, lineterm="", n=0)
+               if ln[:1] in "+-" and not ln.startswith(("+++", "---")))
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("parent")
+    ap.add_argument("this")
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW", help="a renamed file: parent's name = this tree's name")
+    ap.add_argument("--keep", metavar="DIR", help="keep the assembly files there")
+    a = ap.parse_args()
+    ca, cb = csrc_of(a.parent), csrc_of(a.this)
+    hips = lambda d: sorted(f for f in os.listdir(d) if f.endswith(".hip"))   # noqa: E731
+    fa, fb = hips(ca), hips(cb)
+    pairs = [tuple(p.split("=", 1)) for p in a.pair]
+    pairs += [(f, f) for f in fa if f in fb and f not in [p[0] for p in pairs]]
+    paired_a, paired_b = {p[0] for p in pairs}, {p[1] for p in pairs}
+    out_dir = a.keep or tempfile.mkdtemp(prefix="gv_isa_")
+    os.makedirs(out_dir, exist_ok=True)
+    try:
+        jobs = [(ca, o, os.path.join(out_dir, "a_" + o + ".s")) for o, _ in pairs]
+        jobs += [(cb, n, os.path.join(out_dir, "b_" + n + ".s")) for _, n in pairs]
+        with ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
+            asm = list(ex.map(lambda j: device_asm(*j), jobs))
+    finally:
+        if not a.keep:
+            shutil.rmtree(out_dir, ignore_errors=True)
+    print("flags: " + " ".join(gvbuild.FLAGS) + " --cuda-device-only -S")
+    worst = 0
+    for k, (o, n) in sorted(enumerate(pairs), key=lambda kp: kp[1][1]):
+        d = differing_lines(asm[k], asm[len(pairs) + k])
+        worst = max(worst, d)
+        name = n if o == n else o + " -> " + n
+        print(f"{name:44s} {'identical' if d == 0 else str(d) + ' lines differ'}  ({len(asm[len(pairs) + k])} lines)")
+    for f in fa:
+        if f not in paired_a:
+            print(f"{f:44s} only in the parent tree")
+    for f in fb:
+        if f not in paired_b:
+            print(f"{f:44s} only in this tree")
+    return 0 if worst == 0 else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

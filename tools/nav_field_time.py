@@ -18,13 +18,9 @@ is printed."""
 from __future__ import annotations
 
 import argparse
-import csv
-import ctypes as C
-import glob
 import os
-import re
-import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -32,6 +28,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "grid-vision_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import planner_time_common as common  # noqa: E402
 
 GRIDS = [(200, 200, 0.1), (50, 20, 0.1)]
 P1 = (0.35, 0.55, 10.0, 65)
@@ -96,25 +93,10 @@ def seed_entries(gvamd, grid, h, seeds):
     return out
 
 
-def arcs(h, K, P, seed, step=0.25):
-    rng = np.random.default_rng(seed)
-    curv = rng.uniform(-0.3, 0.3, K)
-    yaw0 = 0.3 + rng.normal(0.0, 0.05, K)
-    s = step * np.arange(P)[None, :]
-    yaw = yaw0[:, None] + curv[:, None] * s
-    x = h.pos_x - 4.0 + np.cumsum(step * np.cos(yaw), axis=1)
-    y = h.pos_y + 1.0 + np.cumsum(step * np.sin(yaw), axis=1)
-    return np.ascontiguousarray(np.stack([x, y, yaw], axis=2), np.float32)
-
-
 def run(n, m, warmup):
     import gvamd
     from gvamd import synth
-    from traj_score_time import _fill_poses
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipFree.argtypes = [C.c_void_p]
+    hip = common.load_hip()
     lines = []
 
     def say(s):
@@ -125,7 +107,7 @@ def run(n, m, warmup):
         gx, gy, res = grid
         h = gvamd.GridVisionHIP(gx, gy, res)
         for t in range(12):
-            h.update_map_poses(_fill_poses(synth, h, res, 40, 100 + t))
+            h.update_map_poses(common.fill_poses(synth, h, res, 40, 100 + t))
         h.set_inflation(*P1)
         h.inflate()
         h.synchronize()
@@ -162,14 +144,11 @@ def run(n, m, warmup):
                     f"{n} calls), rounds {sorted(rounds)}, seeds used {info['n_seeds_used']}, reachable {reach}; host: download "
                     f"{np.median(t_get) * 1e3:.2f} ms + dijkstra {t_dij * 1e3:9.1f} ms (graph built once in {t_graph * 1e3:.0f} ms); fields equal")
         # the sampler, against the last field
-        s_ = C.c_void_p(h.stream())
         for K, P in SHAPES:
-            poses = arcs(h, K, P, seed=K)
+            poses = common.arcs(h, K, P, seed=K, start=(-4.0, 1.0))
             pin_in, pin_s = gvamd.PinnedF32(poses.size), gvamd.PinnedI8(K * 24)
             pin_in.array[:] = poses.reshape(-1)
-            dptr = C.c_void_p()
-            assert hip.hipMalloc(C.byref(dptr), poses.nbytes) == 0
-            assert hip.hipMemcpy(dptr, poses.ctypes.data, poses.nbytes, 1) == 0
+            dptr = common.device_copy(hip, poses)
             scores = pin_s.array.view(gvamd.NAV_SCORE_DTYPE)
             want = h.score_nav(poses)
             for label, device in (("pinned poses", False), ("device poses", True)):
@@ -179,18 +158,8 @@ def run(n, m, warmup):
                     call()
                 h.synchronize()
                 assert scores.tobytes() == want.tobytes()
-                e0, e1 = C.c_void_p(), C.c_void_p()
-                assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
-                assert hip.hipEventRecord(e0, s_) == 0
-                for _ in range(m):
-                    call()
-                assert hip.hipEventRecord(e1, s_) == 0
-                assert hip.hipEventSynchronize(e1) == 0
-                ms = C.c_float()
-                assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-                hip.hipEventDestroy(e0)
-                hip.hipEventDestroy(e1)
-                say(f"{h.nx:4d} x {h.ny:4d} gv_score_nav_async {K:5d} x {P:2d} {label:12s}: {m} calls, {1000.0 * ms.value / m:8.2f} us per call, "
+                us = common.event_us_per_call(hip, h, m, call)
+                say(f"{h.nx:4d} x {h.ny:4d} gv_score_nav_async {K:5d} x {P:2d} {label:12s}: {m} calls, {us:8.2f} us per call, "
                     f"bad poses {int(want['n_bad'].sum())} of {K * P}")
             hip.hipFree(dptr)
             pin_in.close()
@@ -200,15 +169,10 @@ def run(n, m, warmup):
 
 
 def kernel_times(trace_dir):
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    assert files, "no *kernel_trace.csv under " + trace_dir
-    rows = []
-    for f in files:
-        with open(f, newline="") as fh:
-            rows += list(csv.DictReader(fh))
+    per = common.kernel_durations(trace_dir, KERNELS)
     lines = []
     for k in KERNELS:
-        d = np.array([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if k in r["Kernel_Name"]])
+        d = np.array(per[k])
         if len(d):
             lines.append(f"{k:12s}: {len(d):7d} dispatches, mean {d.mean():8.2f} us, median {np.median(d):8.2f}, max {d.max():8.2f}, "
                          f"total {d.sum() / 1e3:9.2f} ms")
@@ -216,22 +180,16 @@ def kernel_times(trace_dir):
 
 
 def resources():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    csrc = os.path.join(ROOT, "grid-vision_amd", "csrc")
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC",
-                          "-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, "gv_navfield.hip"], cwd=csrc,
-                         capture_output=True, text=True, check=True).stderr
-    lines, name = [], None
-    for ln in out.splitlines():
-        m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|"
-                      r"VGPRs Spill|LDS Size \[bytes/block\]): (\S+)", ln)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            name = [k for k in KERNELS if k in m.group(2)]
-            lines.append((name[0] if name else m.group(2)) + ":")
-        else:
-            lines[-1] += f" {m.group(1)} {m.group(2)};"
+    """the kernels of gv_navfield.hip as tools/kernel_resources.py compiles and reads them"""
+    import kernel_resources as kr
+    fields = (("sgprs", "TotalSGPRs"), ("vgprs", "VGPRs"), ("scratch", "ScratchSize [bytes/lane]"), ("waves", "Occupancy [waves/SIMD]"),
+              ("sgpr_spill", "SGPRs Spill"), ("vgpr_spill", "VGPRs Spill"), ("lds", "LDS Size [bytes/block]"))
+    with tempfile.TemporaryDirectory() as d:
+        res = kr.parse_remarks(kr.compile_file("gv_navfield.hip", d)[1])
+    lines = []
+    for sym, r in res.items():
+        name = [k for k in KERNELS if k in sym]
+        lines.append((name[0] if name else sym) + ":" + "".join(f" {label} {r[key]};" for key, label in fields if key in r))
     return lines
 
 
@@ -255,9 +213,7 @@ def main():
         print(head, flush=True)
         lines = [head] + run(a.calls, a.score_calls, a.warmup)
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        common.append_out(a.out, lines)
 
 
 if __name__ == "__main__":

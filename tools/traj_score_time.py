@@ -18,9 +18,7 @@ equal the device's byte for byte, or the script fails.  --out FILE appends what 
 from __future__ import annotations
 
 import argparse
-import csv
 import ctypes as C
-import glob
 import os
 import sys
 import time
@@ -29,6 +27,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "grid-vision_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import planner_time_common as common  # noqa: E402
 
 GRID = (200, 200, 0.1)
 P1 = (0.35, 0.55, 10.0, 65)
@@ -38,32 +38,6 @@ SHAPES = [(2000, 56), (250, 20)]
 MODES = [("pinned poses", False, False), ("pinned poses +pose_cost", False, True), ("device poses", True, False),
          ("device poses +pose_cost", True, True)]
 KERNEL = "k_score_trajectories"
-
-
-def _fill_poses(synth, h, res, n, seed):
-    rng = np.random.default_rng(seed)
-    lx, ly = h.nx * res, h.ny * res
-    p = np.zeros(n, dtype=synth.LSHAPE_DTYPE)
-    p["px"] = rng.uniform(h.pos_x - 0.55 * lx, h.pos_x + 0.55 * lx, n)
-    p["py"] = rng.uniform(h.pos_y - 0.55 * ly, h.pos_y + 0.55 * ly, n)
-    p["qw"] = 1.0
-    p["length"] = rng.uniform(0.5, 0.1 * lx, n)
-    p["width"] = rng.uniform(0.5, 0.1 * ly, n)
-    p["height"] = 1.5
-    return p
-
-
-def arcs(h, res, K, P, seed, step=0.25):
-    """K constant-curvature rollouts of P poses from one start pose near the map's centre, as a sampling controller
-    makes them: float32 (K, P, 3)"""
-    rng = np.random.default_rng(seed)
-    curv = rng.uniform(-0.3, 0.3, K)
-    yaw0 = 0.3 + rng.normal(0.0, 0.05, K)
-    s = step * np.arange(P)[None, :]
-    yaw = yaw0[:, None] + curv[:, None] * s
-    x = h.pos_x - 20.0 + np.cumsum(step * np.cos(yaw), axis=1)
-    y = h.pos_y + 5.0 + np.cumsum(step * np.sin(yaw), axis=1)
-    return np.ascontiguousarray(np.stack([x, y, yaw], axis=2), np.float32)
 
 
 def host_alternative(gvamd, h, fp, poses):
@@ -119,27 +93,21 @@ def count_cells(gvamd, fp, poses, stride=7):
 def run(n, warmup):
     import gvamd
     from gvamd import synth
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipFree.argtypes = [C.c_void_p]
+    hip = common.load_hip()
     gx, gy, res = GRID
     h = gvamd.GridVisionHIP(gx, gy, res)
     for t in range(12):
-        h.update_map_poses(_fill_poses(synth, h, res, 40, 100 + t))
+        h.update_map_poses(common.fill_poses(synth, h, res, 40, 100 + t))
     h.set_inflation(*P1)
     h.inflate()
     fp = gvamd.Footprint.of(RECT)
     h.set_footprint(fp)
-    s = C.c_void_p(h.stream())
     lines = []
     for K, P in SHAPES:
-        poses = arcs(h, res, K, P, seed=K)
+        poses = common.arcs(h, K, P, seed=K, start=(-20.0, 5.0))
         pin_in, pin_s, pin_p = gvamd.PinnedF32(poses.size), gvamd.PinnedI8(K * 16), gvamd.PinnedI8(K * P)
         pin_in.array[:] = poses.reshape(-1)
-        dptr = C.c_void_p()
-        assert hip.hipMalloc(C.byref(dptr), poses.nbytes) == 0
-        assert hip.hipMemcpy(dptr, poses.ctypes.data, poses.nbytes, 1) == 0
+        dptr = common.device_copy(hip, poses)
         scores, pc = pin_s.array.view(gvamd.TRAJ_SCORE_DTYPE), pin_p.array.view(np.uint8)
         want_s, want_p, t_get, t_cells, t_loop = host_alternative(gvamd, h, fp, poses)
         n_cells = None
@@ -153,18 +121,7 @@ def run(n, warmup):
             assert scores.tobytes() == want_s.tobytes(), (K, P, label, "the host loop's records differ from the device's")
             if keep:
                 assert pc.tobytes() == want_p.tobytes(), (K, P, label, "pose costs differ")
-            e0, e1 = C.c_void_p(), C.c_void_p()
-            assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
-            assert hip.hipEventRecord(e0, s) == 0
-            for _ in range(n):
-                call()
-            assert hip.hipEventRecord(e1, s) == 0
-            assert hip.hipEventSynchronize(e1) == 0
-            ms = C.c_float()
-            assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
-            hip.hipEventDestroy(e0)
-            hip.hipEventDestroy(e1)
-            us = 1000.0 * ms.value / n
+            us = common.event_us_per_call(hip, h, n, call)
             if n_cells is None:
                 n_cells = count_cells(gvamd, fp, poses)
             lines.append(f"{K:5d} x {P:2d} {label:24s}: {n} calls, {us:8.2f} us per call, {K * P} poses, ~{n_cells / 1e6:5.2f} M cells, "
@@ -185,14 +142,7 @@ def run(n, warmup):
 def kernel_times(trace_dir, n, warmup):
     """per case: mean duration in us of the timed dispatches of the kernel, from rocprofv3's kernel trace of one run of
     this script (dispatch order = SHAPES x MODES order, warmup + n dispatches each)"""
-    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
-    assert files, "no *kernel_trace.csv under " + trace_dir
-    rows = []
-    for f in files:
-        with open(f, newline="") as fh:
-            rows += list(csv.DictReader(fh))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if KERNEL in r["Kernel_Name"]]
+    d = common.kernel_durations(trace_dir, [KERNEL])[KERNEL]
     lines, i = [], 0
     for K, P in SHAPES:
         for label, _, _ in MODES:
@@ -219,9 +169,7 @@ def main():
         lines = ["per call (HIP events around %d back-to-back gv_score_trajectories_async), 2000 x 2000 cells at 0.1 m, P1, "
                  "rectangle footprint:" % a.calls] + run(a.calls, a.warmup)
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        common.append_out(a.out, lines)
 
 
 if __name__ == "__main__":
