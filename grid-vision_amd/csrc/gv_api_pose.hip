@@ -2,6 +2,8 @@
 // post-processing and the node's tick (gv_tick_*).
 #include <atomic>
 #include <algorithm>
+#include <cassert>
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
@@ -18,6 +20,21 @@ static gv_lshape_pose pose_of_vision_out(const VisionOut &vo)
   p.qx = q.x; p.qy = q.y; p.qz = q.z; p.qw = q.w;
   p.length = vo.dims[0]; p.width = vo.dims[1]; p.height = vo.dims[2];
   return p;
+}
+
+// the valid VisionOuts' poses, compacted (vision_orientation.cpp:496-499); tf: into that frame (transformLShapeObjects);
+// out null: counted only
+static int32_t collect_vision_poses(const VisionOut *vo, int32_t n, const gv_transform *tf, gv_lshape_pose *out)
+{
+  int32_t m = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    if (!vo[i].valid) continue;
+    gv_lshape_pose p = pose_of_vision_out(vo[i]);
+    if (tf) host::transform_pose(*tf, p);
+    if (out) out[m] = p;
+    ++m;
+  }
+  return m;
 }
 
 int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, const float *dims,
@@ -37,12 +54,7 @@ int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, 
   std::vector<VisionOut> vo((size_t)nb);
   GV_HIP(hipMemcpyAsync(vo.data(), h->sb[0].vout, (size_t)nb * sizeof(VisionOut), hipMemcpyDeviceToHost, h->stream));
   GV_HIP(hipStreamSynchronize(h->stream));
-  int32_t m = 0;
-  for (int32_t i = 0; i < nb; ++i) {
-    if (!vo[i].valid) continue;   // vision_orientation.cpp:496-499
-    poses_out[m++] = pose_of_vision_out(vo[i]);
-  }
-  *n_out = m;
+  *n_out = collect_vision_poses(vo.data(), nb, nullptr, poses_out);
   return GV_OK;
   GV_CATCH
 }
@@ -70,29 +82,26 @@ int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, con
   GV_CATCH
 }
 
-// ---- the result block (see gv_context::res_host) ----
-constexpr size_t kResHeader = 64;
-
-// a block with room for `bytes` of payload; the CallDone of the call about to be enqueued
-static int begin_result(gv_context *h, size_t bytes, CallDone &done)
+// ---- the result block (ResultBlock, gv_context.hpp) ----
+int ResultBlock::begin(gv_context *h, size_t bytes, CallDone &done)
 {
   // a tick between gv_tick_enqueue and gv_tick_wait owns the result block (and the standalone detection set): the
   // calls that would reuse them are refused until the tick has been waited for
   if (h->tick.pending) { h->err = "a tick is pending: call gv_tick_wait first"; return GV_ERR_STATE; }
   int rc;
-  if (bytes + kResHeader > h->res_host.cap()) {
+  if (bytes + kHeader > host.cap()) {
     GV_HIP(hipStreamSynchronize(h->stream));   // nothing in flight writes the old block
-    const size_t want = std::max<size_t>(2 * (bytes + kResHeader), 16384);
+    const size_t want = std::max<size_t>(2 * (bytes + kHeader), 16384);
     // coherent (fine-grained) explicitly: the host must see the payload and the flag while the kernel that stores them
     // is still running, whatever HIP_HOST_COHERENT says
-    if ((rc = h->res_host.reserve(h, want, hipHostMallocCoherent | hipHostMallocMapped))) return rc;
-    std::memset(h->res_host, 0, want);
+    if ((rc = host.reserve(h, want, hipHostMallocCoherent | hipHostMallocMapped))) return rc;
+    std::memset(host, 0, want);
   }
-  if ((rc = h->d_res_ticket.reserve_zeroed(h, 16, h->stream))) return rc;   // 64 bytes
-  if (++h->res_seq == 0u) h->res_seq = 1u;   // 0 = "nothing published yet"
-  done.ticket = h->d_res_ticket;
-  done.flag = reinterpret_cast<unsigned *>(h->res_host.get());
-  done.seq = h->res_seq;
+  if ((rc = ticket.reserve_zeroed(h, 16, h->stream))) return rc;   // 64 bytes
+  if (++seq == 0u) seq = 1u;   // 0 = "nothing published yet"
+  done.ticket = ticket;
+  done.flag = reinterpret_cast<unsigned *>(host.get());
+  done.seq = seq;
   return GV_OK;
 }
 
@@ -105,10 +114,9 @@ static inline void cpu_relax()
 
 // Host side of CallDone: spin on the block's first word.  The stream is looked at now and then so that a call
 // whose kernels failed ends in an error instead of a hang.
-static int wait_result(gv_context *h)
+int ResultBlock::wait(gv_context *h)
 {
-  volatile unsigned *flag = reinterpret_cast<volatile unsigned *>(h->res_host.get());
-  const unsigned seq = h->res_seq;
+  volatile unsigned *flag = reinterpret_cast<volatile unsigned *>(host.get());
   for (unsigned spins = 1;; ++spins) {
     if (*flag == seq) break;
     cpu_relax();   // the calls take 80-400 us: leave the core's other thread its issue slots
@@ -124,6 +132,20 @@ static int wait_result(gv_context *h)
   return GV_OK;
 }
 
+// buildKDTree projection (cloud_detections.cpp:8-33) into the transformed-cloud buffers, then the exact k nearest (:43-87)
+// of nb boxes; depths | knn_d2 (or null) may lie in the result block
+static KnnArgs knn_args(const gv_context *h, const gv_bbox *boxes, int32_t nb, int32_t k, float *depths, float *knn_d2)
+{
+  KnnArgs a{};
+  a.x = h->cx; a.y = h->cy; a.z = h->cz; a.n = (uint32_t)h->n;
+  a.m_cam = h->m_cam; a.cam = h->camk;
+  a.pu = h->tx; a.pv = h->ty; a.pd = h->tz;
+  a.bboxes = boxes; a.nb = nb; a.k = k;
+  a.partial = h->pose.knn_partial;
+  a.depths = depths; a.knn_d2 = knn_d2;
+  return a;
+}
+
 int gv_compute_depth_for_bboxes(gv_handle h, const gv_bbox *bboxes, int32_t nb, int32_t k, float *depths,
                                 float *knn_d2)
 {
@@ -135,92 +157,155 @@ int gv_compute_depth_for_bboxes(gv_handle h, const gv_bbox *bboxes, int32_t nb, 
   if (rc) return rc;
   if ((rc = upload_scratch_bboxes(h, bboxes, nb, false))) return rc;   // the kNN reads the boxes' centres only
   if ((rc = ensure_tbuf(h, std::max<size_t>(h->n, 1)))) return rc;
-  if ((rc = h->knn_partial.reserve(h, knn_partial_entries(nb, k)))) return rc;
+  if ((rc = h->pose.knn_partial.reserve(h, knn_partial_entries(nb, k)))) return rc;
   // depths | sorted squared distances, stored by the merge kernel straight into the result block
+  ResultBlock &R = h->pose.res;
   CallDone done;
-  if ((rc = begin_result(h, (size_t)nb * (1 + (size_t)k) * sizeof(float), done))) return rc;
-  float *r_depths = reinterpret_cast<float *>(h->res_host + kResHeader), *r_d2 = r_depths + nb;
-  // buildKDTree projection (cloud_detections.cpp:8-33) then the exact k nearest (:43-87)
-  launch_project_uvd(h->cx, h->cy, h->cz, (uint32_t)h->n, h->m_cam, h->camk, h->tx, h->ty, h->tz, h->stream);
-  launch_knn(h->tx, h->ty, h->tz, (uint32_t)h->n, h->det[2].bboxes, nb, k, h->knn_partial, r_depths, knn_d2 ? r_d2 : nullptr, done,
-             h->stream);
+  if ((rc = R.begin(h, (size_t)nb * (1 + (size_t)k) * sizeof(float), done))) return rc;
+  float *r_depths = reinterpret_cast<float *>(R.payload()), *r_d2 = r_depths + nb;
+  const KnnArgs ka = knn_args(h, h->det[2].bboxes, nb, k, r_depths, knn_d2 ? r_d2 : nullptr);
+  launch_project_uvd(ka, h->stream);
+  launch_knn(ka, done, h->stream);
   GV_HIP(hipGetLastError());
-  if ((rc = wait_result(h))) return rc;
+  if ((rc = R.wait(h))) return rc;
   std::memcpy(depths, r_depths, (size_t)nb * sizeof(float));
   if (knn_d2) std::memcpy(knn_d2, r_d2, (size_t)nb * k * sizeof(float));
   return GV_OK;
   GV_CATCH
 }
 
+// segmentGroundPlane(0.04, 50 hypotheses) as computeBBoxPose calls it (grid_vision_node.cpp:215-216)
+constexpr int32_t kPoseRansacIters = 50;
+constexpr uint64_t kPoseRansacSeed = 12345ull;
+
 static int ensure_ransac_buffers(gv_context *h, size_t n, int32_t iterations)
 {
+  gv_context::Pose &P = h->pose;
   int rc;
-  if ((size_t)iterations > h->planes_cap) {
-    h->planes_cap = 0;
-    if ((rc = h->d_planes.reserve(h, (size_t)iterations)) ||
-        (rc = h->d_plane_counts.reserve_zeroed(h, (size_t)iterations * kRansacCountSlices, h->stream)))   // every pass leaves them zero
-      return rc;
-    h->planes_cap = (size_t)iterations;
-  }
-  if ((rc = h->d_rscratch.reserve(h, ransac_scratch_doubles(n)))) return rc;
-  return h->d_rstate.reserve_zeroed(h, 1, h->stream);
+  if ((rc = P.plane_counts.reserve_zeroed(h, (size_t)iterations * kRansacCountSlices, h->stream)) ||   // every pass leaves them zero
+      (rc = P.rscratch.reserve(h, ransac_scratch_doubles(n))))
+    return rc;
+  return P.rstate.reserve_zeroed(h, 1, h->stream);
 }
 
-static size_t pose_block_valid_off(int32_t nb) { return (size_t)nb * sizeof(gv_lshape_pose) + sizeof(RansacState); }
-static size_t pose_block_bytes(int32_t nb) { return pose_block_valid_off(nb) + (size_t)nb; }
+// plane fit and mask pass over the camera-frame cloud (the reference segments transformed_cloud: transformed on the fly);
+// st_copy: where the mask pass hands the final state out
+static RansacArgs ransac_args(const gv_context *h, float thr_f, int32_t iterations, uint64_t seed, RansacState *st_copy = nullptr)
+{
+  const gv_context::Pose &P = h->pose;
+  RansacArgs a{};
+  a.x = h->cx; a.y = h->cy; a.z = h->cz; a.n = (uint32_t)h->n;
+  a.m_cam = h->m_cam;
+  a.thr_f = thr_f; a.iters = iterations; a.seed = seed;
+  a.counts = P.plane_counts; a.scratch = P.rscratch; a.st = P.rstate;
+  a.mask = P.ground; a.st_copy = st_copy;
+  return a;
+}
+
+// poses | RansacState | valid of nb boxes, as k_pca_extent stores them behind `base` (in the result block).  The kernel
+// stores the poses as double2 and the state as 64-bit words: base is 16-byte aligned, and so is then the state.
+struct PoseBlock {
+  static_assert(sizeof(gv_lshape_pose) % 16 == 0 && alignof(RansacState) <= 16 && sizeof(RansacState) % 8 == 0, "PoseBlock alignment");
+  uint8_t *base;
+  int32_t nb;
+  PoseBlock(uint8_t *base_, int32_t nb_) : base(base_), nb(nb_) { assert((reinterpret_cast<uintptr_t>(base) & 15u) == 0); }
+  gv_lshape_pose *poses() const { return reinterpret_cast<gv_lshape_pose *>(base); }
+  RansacState *state() const { return reinterpret_cast<RansacState *>(base + (size_t)nb * sizeof(gv_lshape_pose)); }
+  uint8_t *valid() const { return base + (size_t)nb * sizeof(gv_lshape_pose) + sizeof(RansacState); }
+  static size_t bytes(int32_t nb) { return (size_t)nb * (sizeof(gv_lshape_pose) + 1) + sizeof(RansacState); }
+};
+
+// "empty segmented cloud": no plane, no ground point, or nothing but ground among the n points -> the reference returns {}
+// (cloud_detections.cpp:307-309)
+static bool segmented_cloud_empty(const RansacState &st, size_t n)
+{
+  const uint64_t m = st.best_count ? st.n_inliers : 0;
+  return m == 0 || (size_t)m == n;
+}
+
+// The scratch of enqueue_bbox_pose, group by group; a group has room for what its smallest member has room for.
+// Per point, with n / 8 + 1024 of slack:
+static int reserve_pose_points(gv_context *h, size_t n)
+{
+  gv_context::Pose &P = h->pose;
+  if (n <= std::min({P.nodes.cap(), P.keep.cap(), P.ticket_of.cap()})) return GV_OK;
+  const size_t want = n + n / 8 + 1024;
+  int rc;
+  if ((rc = P.nodes.reserve(h, want)) || (rc = P.keep.reserve(h, want))) return rc;
+  return P.ticket_of.reserve(h, want);
+}
+// per box, with nb / 4 + 64 of slack (every call leaves them zero)
+static int reserve_pose_boxes(gv_context *h, int32_t nb)
+{
+  gv_context::Pose &P = h->pose;
+  if (pca_acc_words(nb) <= P.pca_acc.cap() && pca_ext_words(nb) <= P.pca_ext.cap()) return GV_OK;
+  const int want = nb + nb / 4 + 64;
+  if (int rc = P.pca_acc.reserve_zeroed(h, pca_acc_words(want), h->stream)) return rc;
+  return P.pca_ext.reserve_zeroed(h, pca_ext_words(want), h->stream);
+}
+// cell buckets: a power of two, about one per two points, that only grows (the three arrays stay L2 resident at config-3
+// size; cells that share a bucket only add candidates that fail the id or distance test)
+static int reserve_pose_buckets(gv_context *h, size_t n)
+{
+  gv_context::Pose &P = h->pose;
+  size_t n_buckets = 4096;
+  while (n_buckets < n / 2 && n_buckets < ((size_t)1 << 25)) n_buckets <<= 1;
+  if (n_buckets <= P.buckets().n_buckets) return GV_OK;
+  int rc;
+  if ((rc = P.cellcnt.reserve_zeroed(h, n_buckets, h->stream)) ||   // every call counts them back to zero
+      (rc = P.cellpre.reserve(h, BucketTable::pre_words(n_buckets))))
+    return rc;
+  return P.celloff.reserve_zeroed(h, BucketTable::off_words(n_buckets), h->stream);   // the scan's ticket is in there
+}
+
+// extractCloudPerBBox + RadiusOutlierRemoval(0.4, 10)  (cloud_detections.cpp:250-298, 150-154)
+static RadiusFilterArgs radius_filter_args(const gv_context *h, int32_t nb, bool with_ground, float thr_f)
+{
+  const gv_context::Pose &P = h->pose;
+  const double radius = 0.4;
+  RadiusFilterArgs a{};
+  a.x = h->cx; a.y = h->cy; a.z = h->cz; a.n = (uint32_t)h->n;
+  a.m_cam = h->m_cam; a.cam = h->camk;
+  a.bt = bbox_test_of(h, h->det[2]); a.nb = nb;
+  a.use_plane = with_ground; a.thr_f = thr_f; a.st = P.rstate;
+  a.ids = h->sb[h->last.points].bbox_id;
+  a.tab = P.buckets();
+  a.sorted = P.nodes; a.keep = P.keep; a.ticket_of = P.ticket_of;
+  a.acc = P.pca_acc;
+  a.r2f = host::floor_to_float(radius * radius); a.min_pts = 10;
+  return a;
+}
+
+// centroid + PCA rectangle per bbox from order-independent integer sums over the kept points (:156-247), into `out`
+static PcaRectArgs pca_rect_args(const gv_context *h, int32_t nb, bool with_ground, const PoseBlock &out, gv_lshape_pose *poses_dev)
+{
+  const gv_context::Pose &P = h->pose;
+  PcaRectArgs a{};
+  a.sorted = P.nodes; a.n_sel = P.buckets().n_selected(); a.n = (uint32_t)h->n; a.keep = P.keep;
+  a.acc = P.pca_acc; a.ext = P.pca_ext; a.ticket = P.pca_ticket; a.nb = nb;
+  a.st = P.rstate; a.use_plane = with_ground;
+  a.poses = out.poses(); a.valid = out.valid(); a.st_copy = out.state(); a.poses_dev = poses_dev;
+  return a;
+}
 
 // extractCloudPerBBox -> RadiusOutlierRemoval -> centroid + PCA rectangle, all on the device and all enqueued
 // without a host wait in between; only the nb poses come back.  with_ground: the points of the refined RANSAC
-// plane in *d_rstate are dropped first (computeBBoxPose, cloud_detections.cpp:300-321), and the "empty segmented
+// plane in *rstate are dropped first (computeBBoxPose, cloud_detections.cpp:300-321), and the "empty segmented
 // cloud" outcomes (:307-309) are decided on the device.
 // poses_dev (optional): the camera-frame poses also go to device memory (a NaN length marks "no pose": its
 // corners fail getIndex, so k_rects_from_poses gives it no cells), for a map update enqueued right behind this without a trip to the host.
-static int enqueue_bbox_pose(gv_context *h, int32_t nb, bool with_ground, float thr_f, uint8_t *out, const CallDone &done,
+static int enqueue_bbox_pose(gv_context *h, int32_t nb, bool with_ground, float thr_f, const PoseBlock &out, const CallDone &done,
                              gv_lshape_pose *poses_dev = nullptr)
 {
-  const size_t n = h->n;
+  gv_context::Pose &P = h->pose;
   int rc;
-  if (n > h->pc_cap) {
-    h->pc_cap = 0;
-    const size_t want = n + n / 8 + 1024;
-    if ((rc = h->d_nodes.reserve(h, want)) || (rc = h->d_keep.reserve(h, want)) || (rc = h->d_ticket_of.reserve(h, want))) return rc;
-    h->pc_cap = want;
-  }
-  if ((size_t)nb > h->pca_cap) {
-    h->pca_cap = 0;
-    const size_t want = (size_t)nb + (size_t)nb / 4 + 64;
-    if ((rc = h->d_pca_acc.reserve_zeroed(h, pca_acc_words((int)want), h->stream)) ||   // every call leaves them zero
-        (rc = h->d_pca_ext.reserve_zeroed(h, pca_ext_words((int)want), h->stream)))
-      return rc;
-    h->pca_cap = want;
-  }
-  if ((rc = h->d_pca_ticket.reserve_zeroed(h, 16, h->stream))) return rc;   // 64 bytes
-  // cell buckets: a power of two, about one per two points (the three arrays stay L2 resident at config-3 size;
-  // cells that share a bucket only add candidates that fail the id or distance test)
-  size_t n_buckets = 4096;
-  while (n_buckets < n / 2 && n_buckets < ((size_t)1 << 25)) n_buckets <<= 1;
-  if (n_buckets > h->head_cap) {
-    h->head_cap = 0;
-    if ((rc = h->d_cellcnt.reserve_zeroed(h, n_buckets, h->stream)) ||   // every call counts them back to zero
-        (rc = h->d_cellpre.reserve(h, n_buckets + 4)) ||
-        (rc = h->d_celloff.reserve_zeroed(h, n_buckets / 4096 + 4, h->stream)))   // [n_buckets / 4096 + 2] = the scan's ticket
-      return rc;
-    h->head_cap = n_buckets;
-  }
-  n_buckets = h->head_cap;   // the table only grows
-  if ((rc = h->d_rstate.reserve_zeroed(h, 1, h->stream))) return rc;
-  hipStream_t s = h->stream;
-  // extractCloudPerBBox + RadiusOutlierRemoval(0.4, 10)  (cloud_detections.cpp:250-298, 150-154)
-  const double radius = 0.4;
-  launch_radius_filter(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, h->camk, bbox_test_of(h, h->det[2]), nb, with_ground, thr_f,
-                       h->d_rstate, h->sb[h->last.points].bbox_id, h->d_cellcnt, h->d_cellpre, h->d_celloff,
-                       h->d_celloff + n_buckets / 4096 + 2, h->d_nodes, h->d_keep, h->d_ticket_of, h->d_pca_acc, (uint32_t)n_buckets,
-                       host::floor_to_float(radius * radius), 10, s);
+  if ((rc = reserve_pose_points(h, h->n)) || (rc = reserve_pose_boxes(h, nb)) ||
+      (rc = P.pca_ticket.reserve_zeroed(h, 16, h->stream)) ||   // 64 bytes
+      (rc = reserve_pose_buckets(h, h->n)) || (rc = P.rstate.reserve_zeroed(h, 1, h->stream)))
+    return rc;
+  launch_radius_filter(radius_filter_args(h, nb, with_ground, thr_f), h->stream);
   h->last.bbox_id = true;
-  // centroid + PCA rectangle per bbox from order-independent integer sums over the kept points (:156-247)
-  launch_pca_rect(h->d_nodes, h->d_celloff + n_buckets / 4096, (uint32_t)n, h->d_keep, h->d_pca_acc, h->d_pca_ext, h->d_pca_ticket, nb,
-                  h->d_rstate, with_ground, reinterpret_cast<gv_lshape_pose *>(out), out + pose_block_valid_off(nb),
-                  reinterpret_cast<RansacState *>(out + (size_t)nb * sizeof(gv_lshape_pose)), done, s, poses_dev);
+  launch_pca_rect(pca_rect_args(h, nb, with_ground, out, poses_dev), done, h->stream);
   GV_HIP(hipGetLastError());
   return GV_OK;
 }
@@ -239,34 +324,33 @@ static int compute_bbox_pose_impl(gv_handle h, const gv_bbox *bboxes, int32_t nb
   if (n == 0 || (with_ground && n < 3)) return GV_OK;
   if (nb && (rc = upload_scratch_bboxes(h, bboxes, nb))) return rc;
   const float thr_f = host::ceil_to_float(0.04);   // for a float f: f < thr_f <=> (double)f < 0.04
-  if (with_ground) {   // segmentGroundPlane(0.04, 50 hypotheses) on the camera-frame cloud (grid_vision_node.cpp:215-216)
-    if ((rc = ensure_ransac_buffers(h, n, 50))) return rc;
-    launch_ransac_plane(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, 50, 12345ull, h->d_planes, h->d_plane_counts,
-                        h->d_rscratch, h->d_rstate, h->stream);
+  ResultBlock &R = h->pose.res;
+  CallDone done;
+  if (with_ground) {
+    if ((rc = ensure_ransac_buffers(h, n, kPoseRansacIters))) return rc;
+    launch_ransac_plane(ransac_args(h, thr_f, kPoseRansacIters, kPoseRansacSeed), h->stream);
     GV_HIP(hipGetLastError());
-    h->ground_n = 0;   // the mask itself is not materialised on this path
+    h->pose.ground_n = 0;   // the mask itself is not materialised on this path
   }
   if (nb) {
     // poses | state | flags: stored by the PCA kernel straight into the result block, no copy, no runtime wait
-    CallDone done;
-    if ((rc = begin_result(h, pose_block_bytes(nb), done))) return rc;
-    const uint8_t *blk = h->res_host + kResHeader;
-    if ((rc = enqueue_bbox_pose(h, nb, with_ground, thr_f, h->res_host + kResHeader, done))) return rc;
-    if ((rc = wait_result(h))) return rc;
-    std::memcpy(poses_out, blk, (size_t)nb * sizeof(gv_lshape_pose));
-    std::memcpy(valid, blk + pose_block_valid_off(nb), (size_t)nb);
-    if (st_out) std::memcpy(st_out, blk + (size_t)nb * sizeof(gv_lshape_pose), sizeof(RansacState));
+    if ((rc = R.begin(h, PoseBlock::bytes(nb), done))) return rc;
+    const PoseBlock out(R.payload(), nb);
+    if ((rc = enqueue_bbox_pose(h, nb, with_ground, thr_f, out, done))) return rc;
+    if ((rc = R.wait(h))) return rc;
+    std::memcpy(poses_out, out.poses(), (size_t)nb * sizeof(gv_lshape_pose));
+    std::memcpy(valid, out.valid(), (size_t)nb);
+    if (st_out) std::memcpy(st_out, out.state(), sizeof(RansacState));
     return GV_OK;
   }
   if (with_ground) {   // no boxes: the ground count still decides the return value
-    if ((rc = h->d_ground.reserve(h, n))) return rc;
-    CallDone done;
-    if ((rc = begin_result(h, sizeof(RansacState), done))) return rc;
-    launch_ransac_mask(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, h->d_rstate, h->d_ground,
-                       reinterpret_cast<RansacState *>(h->res_host + kResHeader), done, h->stream);
+    if ((rc = h->pose.ground.reserve(h, n))) return rc;
+    if ((rc = R.begin(h, sizeof(RansacState), done))) return rc;
+    launch_ransac_mask(ransac_args(h, thr_f, kPoseRansacIters, kPoseRansacSeed, reinterpret_cast<RansacState *>(R.payload())), done,
+                       h->stream);
     GV_HIP(hipGetLastError());
-    if ((rc = wait_result(h))) return rc;
-    if (st_out) std::memcpy(st_out, h->res_host + kResHeader, sizeof(RansacState));
+    if ((rc = R.wait(h))) return rc;
+    if (st_out) std::memcpy(st_out, R.payload(), sizeof(RansacState));
     return GV_OK;
   }
   GV_HIP(hipStreamSynchronize(h->stream));
@@ -283,24 +367,22 @@ int gv_compute_bbox_pose(gv_handle h, const gv_bbox *bboxes, int32_t nb, gv_lsha
 static int segment_ground_device(gv_context *h, double threshold, int32_t iterations, uint64_t seed, RansacState &st)
 {
   const size_t n = h->n;
+  ResultBlock &R = h->pose.res;
   st = RansacState{};
-  h->ground_n = 0;
+  h->pose.ground_n = 0;
   if (n < 3) return GV_OK;
   int rc;
   if ((rc = ensure_ransac_buffers(h, n, iterations))) return rc;
-  if ((rc = h->d_ground.reserve(h, n))) return rc;
+  if ((rc = h->pose.ground.reserve(h, n))) return rc;
   const float thr_f = host::ceil_to_float(threshold);
-  // camera-frame cloud (the reference segments transformed_cloud, grid_vision_node.cpp:215-216): transformed on the fly
-  launch_ransac_plane(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, iterations, seed, h->d_planes, h->d_plane_counts,
-                      h->d_rscratch, h->d_rstate, h->stream);
+  launch_ransac_plane(ransac_args(h, thr_f, iterations, seed), h->stream);
   CallDone done;
-  if ((rc = begin_result(h, sizeof(RansacState), done))) return rc;
-  launch_ransac_mask(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, h->d_rstate, h->d_ground,
-                     reinterpret_cast<RansacState *>(h->res_host + kResHeader), done, h->stream);
+  if ((rc = R.begin(h, sizeof(RansacState), done))) return rc;
+  launch_ransac_mask(ransac_args(h, thr_f, iterations, seed, reinterpret_cast<RansacState *>(R.payload())), done, h->stream);
   GV_HIP(hipGetLastError());
-  if ((rc = wait_result(h))) return rc;
-  std::memcpy(&st, h->res_host + kResHeader, sizeof(RansacState));
-  h->ground_n = n;
+  if ((rc = R.wait(h))) return rc;
+  std::memcpy(&st, R.payload(), sizeof(RansacState));
+  h->pose.ground_n = n;
   return GV_OK;
 }
 
@@ -319,7 +401,7 @@ int gv_segment_ground_plane(gv_handle h, double threshold, int32_t iterations, u
   if ((rc = segment_ground_device(h, threshold, iterations, seed, st))) return rc;
   if (!st.best_count) return GV_OK;   // "Could not estimate a planar model" (:122-126)
   if (is_ground) {   // the caller asked for the per-point mask: the only O(N) transfer of this call
-    GV_HIP(hipMemcpyAsync(is_ground, h->d_ground, h->n, hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipMemcpyAsync(is_ground, h->pose.ground, h->n, hipMemcpyDeviceToHost, h->stream));
     GV_HIP(hipStreamSynchronize(h->stream));
   }
   if (coeff) { coeff[0] = st.refined.x; coeff[1] = st.refined.y; coeff[2] = st.refined.z; coeff[3] = st.refined.w; }
@@ -339,8 +421,7 @@ int gv_compute_bbox_pose_ground_removed(gv_handle h, const gv_bbox *bboxes, int3
   RansacState st;
   int rc = compute_bbox_pose_impl(h, bboxes, nb, poses_out, valid, true, &st);
   if (rc) return rc;
-  const uint64_t m = st.best_count ? st.n_inliers : 0;
-  if (m == 0 || (size_t)m == h->n) {   // empty segmented cloud -> the reference returns {} (:307-309)
+  if (segmented_cloud_empty(st, h->n)) {
     for (int32_t b = 0; b < nb; ++b) valid[b] = 0;
     if (n_poses_or_fail) *n_poses_or_fail = -1;
     return GV_OK;
@@ -362,14 +443,13 @@ int gv_test_bbox_pose_nodes(gv_handle h, const gv_bbox *bboxes, int32_t nb, int3
   GV_TRY
   if (nb == 0 || h->n == 0 || (with_ground && h->n < 3)) return GV_OK;   // nothing was launched
   if ((rc = set_device_only(h))) return rc;
-  // the number of selected points sits behind the block offsets of the bucket table (enqueue_bbox_pose)
   uint32_t m = 0;
-  GV_HIP(hipMemcpyAsync(&m, h->d_celloff + h->head_cap / 4096, sizeof(m), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipMemcpyAsync(&m, h->pose.buckets().n_selected(), sizeof(m), hipMemcpyDeviceToHost, h->stream));
   GV_HIP(hipStreamSynchronize(h->stream));
   if ((size_t)m > h->n) { h->err = "more selected points than points"; return GV_ERR_STATE; }
   if (m) {
-    GV_HIP(hipMemcpyAsync(nodes, h->d_nodes, (size_t)m * sizeof(CellNode), hipMemcpyDeviceToHost, h->stream));
-    GV_HIP(hipMemcpyAsync(keep, h->d_keep, (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipMemcpyAsync(nodes, h->pose.nodes, (size_t)m * sizeof(CellNode), hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipMemcpyAsync(keep, h->pose.keep, (size_t)m, hipMemcpyDeviceToHost, h->stream));
     GV_HIP(hipStreamSynchronize(h->stream));
   }
   *n_sel = (int64_t)m;
@@ -427,18 +507,18 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   // result block: depths | poses, state, valid (the PCA call's layout) | VisionOut
   T.off_depth = 0;
   T.off_pose = ((size_t)ns * sizeof(float) + 15) & ~(size_t)15;
-  T.off_vout = (T.off_pose + pose_block_bytes(n_all) + 15) & ~(size_t)15;
+  T.off_vout = (T.off_pose + PoseBlock::bytes(n_all) + 15) & ~(size_t)15;
   CallDone none;   // nothing published: the tick ends with an event on the public stream
-  if ((rc = begin_result(h, T.off_vout + (size_t)nd * sizeof(VisionOut) + 16, none))) return rc;
+  if ((rc = h->pose.res.begin(h, T.off_vout + (size_t)nd * sizeof(VisionOut) + 16, none))) return rc;
   none = CallDone{};
-  uint8_t *blk = h->res_host + kResHeader;
+  uint8_t *blk = h->pose.res.payload();
   // --- static boxes: buildKDTree + computeDepthForBoundingBoxes (:168-184).  Independent of the pose branch: it
   // runs on a lane beside it and joins the public stream before the tick's last event.
   T.knn_ran = ns > 0;
   bool knn_forked = false;
   if (ns > 0) {
     if ((rc = ensure_tbuf(h, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = h->knn_partial.reserve(h, knn_partial_entries(ns, k)))) return rc;
+    if ((rc = h->pose.knn_partial.reserve(h, knn_partial_entries(ns, k)))) return rc;
     hipStream_t sk = s;
     if (h->tune.tick_knn_lane && nd > 0) {
       sk = h->streams[1];
@@ -447,9 +527,9 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
       h->sb[1].lane_clean = false;
       knn_forked = true;
     }
-    launch_project_uvd(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, h->camk, h->tx, h->ty, h->tz, sk);
-    launch_knn(h->tx, h->ty, h->tz, (uint32_t)n, D.bboxes + n_all, ns, k, h->knn_partial,
-               reinterpret_cast<float *>(blk + T.off_depth), nullptr, none, sk);
+    const KnnArgs ka = knn_args(h, D.bboxes + n_all, ns, k, reinterpret_cast<float *>(blk + T.off_depth), nullptr);
+    launch_project_uvd(ka, sk);
+    launch_knn(ka, none, sk);
     GV_HIP(hipGetLastError());
     if (knn_forked) GV_HIP(hipEventRecord(T.join, sk));
   }
@@ -465,11 +545,10 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
     T.vision_ran = true;
   } else if (pca) {   // cloud_detections::computeBBoxPose (:210-231)
     const float thr_f = host::ceil_to_float(0.04);
-    if ((rc = ensure_ransac_buffers(h, n, 50))) return rc;
-    launch_ransac_plane(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, thr_f, 50, 12345ull, h->d_planes, h->d_plane_counts,
-                        h->d_rscratch, h->d_rstate, s);
-    h->ground_n = 0;
-    if ((rc = enqueue_bbox_pose(h, n_all, true, thr_f, blk + T.off_pose, none, D.poses))) return rc;
+    if ((rc = ensure_ransac_buffers(h, n, kPoseRansacIters))) return rc;
+    launch_ransac_plane(ransac_args(h, thr_f, kPoseRansacIters, kPoseRansacSeed), s);
+    h->pose.ground_n = 0;
+    if ((rc = enqueue_bbox_pose(h, n_all, true, thr_f, PoseBlock(blk + T.off_pose, n_all), none, D.poses))) return rc;
     launch_rects_from_poses(D.poses, n_all, h->g, true, h->x_bc, rects, s);
     n_rects = n_all;
     T.pca_ran = true;
@@ -512,7 +591,7 @@ int gv_tick_wait(gv_handle h, gv_tick_result *r)
   if (rc) return rc;
   GV_HIP(hipEventSynchronize(T.done));   // the tick's one host wait
   T.pending = false;
-  const uint8_t *blk = h->res_host + kResHeader;
+  uint8_t *blk = h->pose.res.payload();
   r->n_static = T.n_static;
   r->n_dynamic = T.n_dynamic;
   r->n_poses = 0;
@@ -524,21 +603,15 @@ int gv_tick_wait(gv_handle h, gv_tick_result *r)
     if (r->base_points_xyz) convert_pixels_host(h->Kinv, T.x_bc, T.st_boxes.data(), dep, T.n_static, r->base_points_xyz);   // :180
   }
   if (T.vision_ran) {
-    const VisionOut *vo = reinterpret_cast<const VisionOut *>(blk + T.off_vout);
-    for (int32_t i = 0; i < T.n_dynamic; ++i) {
-      if (!vo[i].valid) continue;   // vision_orientation.cpp:496-499
-      gv_lshape_pose p = pose_of_vision_out(vo[i]);
-      host::transform_pose(T.tf_bc, p);   // transformLShapeObjects (:204)
-      if (r->poses) r->poses[r->n_poses] = p;
-      r->n_poses++;
-    }
+    // transformLShapeObjects (:204)
+    r->n_poses = collect_vision_poses(reinterpret_cast<const VisionOut *>(blk + T.off_vout), T.n_dynamic, &T.tf_bc, r->poses);
   } else if (T.pca_ran) {
-    const gv_lshape_pose *ps = reinterpret_cast<const gv_lshape_pose *>(blk + T.off_pose);
+    const PoseBlock pb(blk + T.off_pose, T.n_all);
+    const gv_lshape_pose *ps = pb.poses();
+    const uint8_t *valid = pb.valid();
     RansacState st;
-    std::memcpy(&st, blk + T.off_pose + (size_t)T.n_all * sizeof(gv_lshape_pose), sizeof(st));
-    const uint8_t *valid = blk + T.off_pose + pose_block_valid_off(T.n_all);
-    const uint64_t m = st.best_count ? st.n_inliers : 0;
-    if (m == 0 || (size_t)m == T.n) r->pca_empty = 1;   // empty segmented cloud: computeBBoxPose returns {} (:307-309)
+    std::memcpy(&st, pb.state(), sizeof(st));
+    if (segmented_cloud_empty(st, T.n)) r->pca_empty = 1;   // T.n: the cloud the tick read, not the handle's now
     else
       for (int32_t b = 0; b < T.n_all; ++b) {
         if (!valid[b]) continue;   // :174-175

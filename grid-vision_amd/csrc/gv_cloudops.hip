@@ -293,12 +293,7 @@ __global__ void __launch_bounds__(kCoThreads) k_ransac_moments(const float *__re
   // XCD by every workgroup (buffer_wbl2): 10 us of this kernel, 15 us of k_pca_extent (profiles/r04/ticket_fence_ab.txt).
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (tid == 0) {
-    const unsigned ticket = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = ticket == gridDim.x - 1u;
-    if (last) __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
-    s_last = last ? 1u : 0u;
-  }
+  if (tid == 0) s_last = take_last_ticket(&st->ticket) ? 1u : 0u;
   __syncthreads();
   if (!s_last) return;
   // levels 2..: groups of 64 partial sums per wavefront.
@@ -421,9 +416,7 @@ __global__ void __launch_bounds__(kCoThreads) k_ransac_mask(const float *__restr
     if (st_copy) {   // the workgroup that finishes last hands the final state out (the count is an agent-scope atomic:
       // no fence, only this thread's atomic acknowledged before its ticket)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned t = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == gridDim.x - 1u) {
-        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (take_last_ticket(&st->ticket)) {
         RansacState o = *st;
         o.n_inliers = __hip_atomic_load(&st->n_inliers, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         o.ticket = 0u;
@@ -440,27 +433,24 @@ size_t ransac_scratch_doubles(size_t n)
   return (size_t)kMom * (nblk + (nblk + 63) / 64 + 2) + 64;
 }
 
-void launch_ransac_plane(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m_cam, float thr_f, int iters,
-                         unsigned long long seed, float4 *planes, unsigned *counts, double *scratch, RansacState *st,
-                         hipStream_t s)
+void launch_ransac_plane(const RansacArgs &a, hipStream_t s)
 {
-  const uint32_t nblk = (uint32_t)(((size_t)n + kCoBlock - 1) / kCoBlock);
-  (void)planes;   // (the hypotheses are no longer materialised: every workgroup makes the ones it needs)
-  for (int h0 = 0; h0 < iters; h0 += 2048) {   // planes + counters of one launch sit in LDS (20 bytes per hypothesis)
-    const int hn = std::min(2048, iters - h0);
-    hipLaunchKernelGGL(k_ransac_count_all, dim3(nblk), dim3(kCoThreads), (size_t)hn * (sizeof(float4) + sizeof(unsigned)), s, x, y, z,
-                       n, m_cam, seed, h0, hn, thr_f, counts + h0, iters);
+  const uint32_t nblk = (uint32_t)(((size_t)a.n + kCoBlock - 1) / kCoBlock);
+  for (int h0 = 0; h0 < a.iters; h0 += 2048) {   // planes + counters of one launch sit in LDS (20 bytes per hypothesis)
+    const int hn = std::min(2048, a.iters - h0);
+    hipLaunchKernelGGL(k_ransac_count_all, dim3(nblk), dim3(kCoThreads), (size_t)hn * (sizeof(float4) + sizeof(unsigned)), s, a.x, a.y,
+                       a.z, a.n, a.m_cam, a.seed, h0, hn, a.thr_f, a.counts + h0, a.iters);
   }
-  double *part_a = scratch, *part_b = scratch + (size_t)kMom * (nblk + 1);
-  hipLaunchKernelGGL(k_ransac_moments, dim3(nblk), dim3(kCoThreads), 0, s, x, y, z, n, m_cam, seed, counts, iters, thr_f, part_a,
-                     part_b, st);
+  double *part_a = a.scratch, *part_b = a.scratch + (size_t)kMom * (nblk + 1);
+  hipLaunchKernelGGL(k_ransac_moments, dim3(nblk), dim3(kCoThreads), 0, s, a.x, a.y, a.z, a.n, a.m_cam, a.seed, a.counts, a.iters,
+                     a.thr_f, part_a, part_b, a.st);
 }
 
-void launch_ransac_mask(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m_cam, float thr_f,
-                        RansacState *st, uint8_t *mask, RansacState *st_copy, const CallDone &done, hipStream_t s)
+void launch_ransac_mask(const RansacArgs &a, const CallDone &done, hipStream_t s)
 {
-  const uint32_t nblk = (uint32_t)(((size_t)n + kCoBlock - 1) / kCoBlock);
-  hipLaunchKernelGGL(k_ransac_mask, dim3(nblk), dim3(kCoThreads), 0, s, x, y, z, n, m_cam, thr_f, st, mask, st_copy, done);
+  const uint32_t nblk = (uint32_t)(((size_t)a.n + kCoBlock - 1) / kCoBlock);
+  hipLaunchKernelGGL(k_ransac_mask, dim3(nblk), dim3(kCoThreads), 0, s, a.x, a.y, a.z, a.n, a.m_cam, a.thr_f, a.st, a.mask, a.st_copy,
+                     done);
 }
 
 // --------------------------------------------- per-bbox clouds: classify + cell hash --
@@ -641,10 +631,7 @@ __global__ void __launch_bounds__(1024) k_cell_scan(uint32_t *__restrict__ cell_
     // (the last workgroup reads only these totals, by agent-scope atomic loads: no fence -- see k_ransac_moments)
     __hip_atomic_store(&blk_off[blockIdx.x], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = tk == gridDim.x - 1u;
-    if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = last ? 1u : 0u;
+    s_last = take_last_ticket(ticket) ? 1u : 0u;
   }
   __syncthreads();
   if (!s_last) return;
@@ -1230,12 +1217,7 @@ __global__ void __launch_bounds__(256) k_pca_extent(const CellNode *__restrict__
   // (profiles/r04/ticket_fence_ab.txt).
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = tk == gridDim.x - 1u;
-    if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = last ? 1u : 0u;
-  }
+  if (threadIdx.x == 0) s_last = take_last_ticket(ticket) ? 1u : 0u;
   __syncthreads();
   if (!s_last) return;
   // computeBBoxPose :307-309: an empty segmented cloud (no plane found, or everything is ground) -> no poses
@@ -1314,39 +1296,38 @@ __global__ void __launch_bounds__(256) k_pca_extent(const CellNode *__restrict__
   }
 }
 
-void launch_radius_filter(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m_cam, const CamK &cam,
-                          const BBoxTest &bt, int nb, bool use_plane, float thr_f, RansacState *st, int16_t *ids,
-                          uint32_t *cell_cnt, uint32_t *pre, uint32_t *blk_off, unsigned *ticket, CellNode *sorted, uint8_t *keep,
-                          uint32_t *ticket_of, long long *acc, uint32_t n_buckets, float r2f, int min_pts, hipStream_t s)
+void launch_radius_filter(const RadiusFilterArgs &a, hipStream_t s)
 {
-  if (!n) return;
-  const uint32_t nblk = (uint32_t)(((size_t)n + kCoBlock - 1) / kCoBlock);
-  const uint32_t hi_mask = n_buckets / 512u - 1u;
+  if (!a.n) return;
+  const BucketTable &t = a.tab;
+  const uint32_t nblk = (uint32_t)(((size_t)a.n + kCoBlock - 1) / kCoBlock);
+  const uint32_t hi_mask = t.n_buckets / 512u - 1u;
   // the bbox test's tables in LDS when they fit (40 boxes, 640 x 480: 10 KB)
-  const size_t tab_bytes = (size_t)((nb + 3) & ~3) * sizeof(float4) + (size_t)bt.tiles_x * bt.tiles_y * bt.mask_words * sizeof(unsigned long long);
+  const size_t tab_bytes = (size_t)((a.nb + 3) & ~3) * sizeof(float4) +
+                           (size_t)a.bt.tiles_x * a.bt.tiles_y * a.bt.mask_words * sizeof(unsigned long long);
   if (tab_bytes <= 48 * 1024)
-    hipLaunchKernelGGL(k_pose_classify<true>, dim3(nblk), dim3(kCoThreads), tab_bytes, s, x, y, z, n, m_cam, cam, bt, nb, use_plane ? 1 : 0,
-                       thr_f, st, ids, cell_cnt, ticket_of, hi_mask);
+    hipLaunchKernelGGL(k_pose_classify<true>, dim3(nblk), dim3(kCoThreads), tab_bytes, s, a.x, a.y, a.z, a.n, a.m_cam, a.cam, a.bt, a.nb,
+                       a.use_plane ? 1 : 0, a.thr_f, a.st, a.ids, t.cnt, a.ticket_of, hi_mask);
   else
-    hipLaunchKernelGGL(k_pose_classify<false>, dim3(nblk), dim3(kCoThreads), 0, s, x, y, z, n, m_cam, cam, bt, nb, use_plane ? 1 : 0,
-                       thr_f, st, ids, cell_cnt, ticket_of, hi_mask);
-  hipLaunchKernelGGL(k_cell_scan, dim3(n_buckets / kScanBlock), dim3(1024), 0, s, cell_cnt, n_buckets, pre, blk_off, ticket);
-  hipLaunchKernelGGL(k_cell_scatter, dim3(nblk), dim3(kCoThreads), 0, s, x, y, z, n, m_cam, ids, ticket_of, pre, blk_off, hi_mask, sorted);
+    hipLaunchKernelGGL(k_pose_classify<false>, dim3(nblk), dim3(kCoThreads), 0, s, a.x, a.y, a.z, a.n, a.m_cam, a.cam, a.bt, a.nb,
+                       a.use_plane ? 1 : 0, a.thr_f, a.st, a.ids, t.cnt, a.ticket_of, hi_mask);
+  hipLaunchKernelGGL(k_cell_scan, dim3(t.n_buckets / kScanBlock), dim3(1024), 0, s, t.cnt, t.n_buckets, t.pre, t.blk_off, t.scan_ticket());
+  hipLaunchKernelGGL(k_cell_scatter, dim3(nblk), dim3(kCoThreads), 0, s, a.x, a.y, a.z, a.n, a.m_cam, a.ids, a.ticket_of, t.pre,
+                     t.blk_off, hi_mask, a.sorted);
   // 32 selected points per wavefront and pass; their number is only known on the device: a fixed grid strides over them
-  const uint32_t rblk = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)n + 4 * kRadPts - 1) / (4 * kRadPts), GV_RAD_GRID));
-  hipLaunchKernelGGL(k_radius_sorted, dim3(rblk), dim3(256), 0, s, sorted, pre, blk_off, n_buckets, hi_mask, r2f, min_pts, keep, acc, nb);
+  const uint32_t rblk = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)a.n + 4 * kRadPts - 1) / (4 * kRadPts), GV_RAD_GRID));
+  hipLaunchKernelGGL(k_radius_sorted, dim3(rblk), dim3(256), 0, s, a.sorted, t.pre, t.blk_off, t.n_buckets, hi_mask, a.r2f, a.min_pts,
+                     a.keep, a.acc, a.nb);
 }
 
-void launch_pca_rect(const CellNode *sorted, const uint32_t *n_sel, uint32_t n, const uint8_t *keep, long long *acc, unsigned *ext,
-                     unsigned *ticket, int nb, const RansacState *st, bool use_plane, gv_lshape_pose *poses, uint8_t *valid,
-                     RansacState *st_copy, const CallDone &done, hipStream_t s, gv_lshape_pose *poses_dev)
+void launch_pca_rect(const PcaRectArgs &a, const CallDone &done, hipStream_t s)
 {
-  if (nb <= 0) return;
+  if (a.nb <= 0) return;
   // few workgroups: every one of them ends with a flush of its table into the boxes' accumulators
-  const uint32_t blk = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)n + 1023) / 1024, 256));
-  hipLaunchKernelGGL(k_pca_cov, dim3(blk), dim3(256), 0, s, sorted, n_sel, keep, acc, nb);
-  hipLaunchKernelGGL(k_pca_extent, dim3(blk), dim3(256), 0, s, sorted, n_sel, keep, acc, ext, ticket, nb, st, use_plane ? 1 : 0, n,
-                     poses, valid, st_copy, done, poses_dev);
+  const uint32_t blk = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)a.n + 1023) / 1024, 256));
+  hipLaunchKernelGGL(k_pca_cov, dim3(blk), dim3(256), 0, s, a.sorted, a.n_sel, a.keep, a.acc, a.nb);
+  hipLaunchKernelGGL(k_pca_extent, dim3(blk), dim3(256), 0, s, a.sorted, a.n_sel, a.keep, a.acc, a.ext, a.ticket, a.nb, a.st,
+                     a.use_plane ? 1 : 0, a.n, a.poses, a.valid, a.st_copy, done, a.poses_dev);
 }
 
 size_t pca_acc_words(int nb) { return (size_t)nb * kAccStride; }

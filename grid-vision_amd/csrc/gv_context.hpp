@@ -20,6 +20,7 @@
 using namespace gv;
 
 struct ncclComm;   // rccl.h is gv_api_shard.hip's alone
+struct gv_context;
 
 namespace gv_internal __attribute__((visibility("hidden"))) {
 
@@ -125,6 +126,21 @@ struct Tuning {
   int32_t ablate = 0;               // GV_ABLATE
   bool bin_dbg = false, timeline = false, sector_dbg = false;   // GV_BIN_DBG / GV_TIMELINE / GV_SECTOR_DBG = 1: the stamp buffers exist
 #endif
+};
+
+// Result block of the synchronous kNN / RANSAC / PCA calls and of the tick: pinned, coherent and device-mapped, written
+// by the call's last kernel; [0] = the sequence number of the last finished call (CallDone, gv_kernels.hpp), payload
+// from byte kHeader (gv_api_pose.hip)
+struct ResultBlock {
+  static constexpr size_t kHeader = 64;
+  static_assert(kHeader % 16 == 0, "the payload keeps the block's alignment (PoseBlock)");
+  PinnedBuf host;
+  DevBuf<unsigned> ticket;
+  unsigned seq = 0;                 // of the last call begun; never 0 ("nothing published yet")
+  uint8_t *payload() const { return host.get() + kHeader; }
+  // room for `bytes` of payload and the CallDone of the call about to be enqueued; refused while a tick is pending
+  int begin(gv_context *h, size_t bytes, CallDone &done);
+  int wait(gv_context *h);          // host side of CallDone: spins until the call begun last has published
 };
 
 }  // namespace gv_internal
@@ -307,23 +323,32 @@ struct __attribute__((visibility("hidden"))) gv_context {
   int32_t bt_tiles_x = 1, bt_tiles_y = 1;   // 16x16-pixel tiles of the image
   int32_t vout_cap = 0;                     // rectangles, vision outputs (all sets) and centre points
   DevBuf<double> d_pts;
-  // kNN depth / PCA pose scratch
-  DevBuf<Cand2> knn_partial;
-  DevBuf<CellNode> d_nodes; DevBuf<uint8_t> d_keep; size_t pc_cap = 0;   // selected points in bucket order; 1 = survives the radius filter
-  DevBuf<uint32_t> d_ticket_of;      // per cloud point: its slot inside its bucket (selected points only)
-  DevBuf<long long> d_pca_acc; DevBuf<unsigned> d_pca_ext; size_t pca_cap = 0;   // per bbox: integer sums / extent keys of the PCA rectangle (zero between calls)
-  DevBuf<unsigned> d_pca_ticket;
-  DevBuf<uint32_t> d_cellcnt, d_cellpre, d_celloff; size_t head_cap = 0;   // cell buckets: counts, prefix, block offsets (+ ticket)
-  DevBuf<float4> d_planes; DevBuf<unsigned> d_plane_counts; size_t planes_cap = 0;
-  DevBuf<uint8_t> d_ground;   // last ground mask (device resident)
-  size_t ground_n = 0;
-  DevBuf<double> d_rscratch;   // tree-sum partials of the plane refinement
-  DevBuf<RansacState> d_rstate;
-  // result block of the synchronous kNN / RANSAC / PCA calls: pinned and device-mapped, written by the call's last
-  // kernel; [0] = the sequence number of the last finished call (CallDone, gv_kernels.hpp), payload from byte 64
-  PinnedBuf res_host;
-  DevBuf<unsigned> d_res_ticket;
-  unsigned res_seq = 0;
+  // kNN depth, RANSAC ground plane, per-box radius filter + PCA rectangle (gv_api_pose.hip).  Every group of buffers is
+  // made by the first call that needs it and grows through one function of gv_api_pose.hip over the buffers' own cap():
+  // a group whose second allocation failed has a member without room, so the next call grows it again.
+  struct Pose {
+    DevBuf<Cand2> knn_partial;        // stage-1 candidate lists of the kNN
+    // per point of the cloud (n + n / 8 + 1024)
+    DevBuf<CellNode> nodes;           // selected points in bucket order
+    DevBuf<uint8_t> keep;             // 1 = survives the radius filter
+    DevBuf<uint32_t> ticket_of;       // per cloud point: its slot inside its bucket (selected points only)
+    // per bbox (nb + nb / 4 + 64): integer sums / extent keys of the PCA rectangle; every call leaves them zero
+    DevBuf<long long> pca_acc;
+    DevBuf<unsigned> pca_ext;
+    DevBuf<unsigned> pca_ticket;
+    // cell buckets: counts, prefix, block offsets (BucketTable, gv_kernels.hpp); the counts and the ticket are zero between calls
+    DevBuf<uint32_t> cellcnt, cellpre, celloff;
+    BucketTable buckets() const
+    {
+      return {cellcnt, cellpre, celloff, (uint32_t)BucketTable::held(cellcnt.cap(), cellpre.cap(), celloff.cap())};
+    }
+    DevBuf<unsigned> plane_counts;    // inlier counts of the hypotheses; every pass leaves them zero
+    DevBuf<uint8_t> ground;           // last ground mask (device resident)
+    size_t ground_n = 0;
+    DevBuf<double> rscratch;          // tree-sum partials of the plane refinement
+    DevBuf<RansacState> rstate;
+    ResultBlock res;
+  } pose;
 
   // the node's tick (gv_tick_enqueue / gv_tick_wait): what the pending tick put where in the result block
   struct Tick {

@@ -291,8 +291,6 @@ struct Cand2 {
   float d2;
   uint32_t idx;
 };
-void launch_project_uvd(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m,
-                        const CamK &cam, float *pu, float *pv, float *pd, hipStream_t s);
 size_t knn_partial_entries(int nb, int k);   // Cand2 entries of the stage-1 lists
 
 // Completion of a synchronous call without a copy command or a runtime wait: the call's last kernel stores its
@@ -323,11 +321,32 @@ __device__ __forceinline__ void call_done(const CallDone &d, unsigned n_wg)
     __hip_atomic_store(d.flag, d.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+// Such a ticket, by one lane of every workgroup once its stores have been acknowledged (s_waitcnt vmcnt(0) at the site):
+// true in the workgroup that arrives last, which leaves the counter zero for the next call
+__device__ __forceinline__ bool take_last_ticket(unsigned *ticket)
+{
+  const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool last = t == gridDim.x - 1u;
+  if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return last;
+}
 #endif
 
-// depths / knn_d2 may be host-mapped (then done.flag is set)
-void launch_knn(const float *pu, const float *pv, const float *pd, uint32_t n, const gv_bbox *bboxes, int nb, int k,
-                Cand2 *partial, float *depths, float *knn_d2, const CallDone &done, hipStream_t s);
+// buildKDTree projection, then the exact k nearest of every box centre and the median depth of each
+struct KnnArgs {
+  const float *x, *y, *z;   // the resident cloud (lidar frame), n each
+  uint32_t n;
+  Mat34f m_cam;             // camera <- lidar
+  CamK cam;
+  float *pu, *pv, *pd;      // n each: (u, v, depth) of every point, NaN where skipped; written by launch_project_uvd
+  const gv_bbox *bboxes;    // nb (device): only the centres are read
+  int nb, k;                // k in [1, 32]
+  Cand2 *partial;           // knn_partial_entries(nb, k)
+  float *depths;            // nb; may be host-mapped (then done.flag is set)
+  float *knn_d2;            // nb * k sorted squared distances behind it, or null
+};
+void launch_project_uvd(const KnnArgs &a, hipStream_t s);
+void launch_knn(const KnnArgs &a, const CallDone &done, hipStream_t s);
 
 // ---- device-resident RANSAC ground plane + per-bbox clouds / radius filter / PCA (gv_cloudops.hip) ----
 struct RansacState {
@@ -343,41 +362,92 @@ size_t ransac_scratch_doubles(size_t n);
 // the selection sums them): every workgroup ends with one atomic per hypothesis, and 245 workgroups on the same
 // 50 words queue up in two L2 channels otherwise.  counts holds kRansacCountSlices * iters words.
 constexpr int kRansacCountSlices = 16;
-// hypotheses, inlier counts of all of them, selection + refinement on stream s; *st stays on the device.
-// counts[kRansacCountSlices * iters] must be zero on entry (the pass leaves it zero); thr_f = smallest float >= the fp64 threshold
-void launch_ransac_plane(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m_cam, float thr_f, int iters,
-                         unsigned long long seed, float4 *planes, unsigned *counts, double *scratch, RansacState *st,
-                         hipStream_t s);
+struct RansacArgs {
+  const float *x, *y, *z;   // the resident cloud (lidar frame), n each: transformed on the fly
+  uint32_t n;
+  Mat34f m_cam;
+  float thr_f;              // smallest float >= the fp64 threshold
+  int iters;                // hypotheses (launch_ransac_plane)
+  unsigned long long seed;
+  unsigned *counts;         // kRansacCountSlices * iters, zero on entry (the pass leaves them zero)
+  double *scratch;          // ransac_scratch_doubles(n): tree-sum partials of the refinement
+  RansacState *st;          // device; stays there
+  uint8_t *mask;            // n: inliers of the refined plane (launch_ransac_mask)
+  RansacState *st_copy;     // optional, may be host-mapped: the final *st, stored by the workgroup that finishes last
+};
+// hypotheses, inlier counts of all of them, selection + refinement into *st
+void launch_ransac_plane(const RansacArgs &a, hipStream_t s);
 // mask[n] of the refined plane's inliers + st->n_inliers
-// st_copy (optional, may be host-mapped): the final *st, stored by the workgroup that finishes last
-void launch_ransac_mask(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m_cam, float thr_f,
-                        RansacState *st, uint8_t *mask, RansacState *st_copy, const CallDone &done, hipStream_t s);
+void launch_ransac_mask(const RansacArgs &a, const CallDone &done, hipStream_t s);
 // one selected point of the radius filter, in bucket order
 struct CellNode {
   float x, y, z;    // camera frame
   int32_t id;       // bbox
 };
 static_assert(sizeof(CellNode) == 16, "one node = one 16-byte access");
-// extractCloudPerBBox + RadiusOutlierRemoval: ids[n] (ground points of st->refined dropped when use_plane), the
-// selected points in bucket order (sorted, their number at pre[n_buckets]), keep[t] = 1 where sorted point t survives
-// the filter, and the kept points' coordinate sums in acc (pca_acc_words(nb) 64-bit words, zero on entry).
-// cell_cnt[n_buckets] must be zero on entry (left zero), pre has n_buckets + 1 entries, blk_off n_buckets / 4096 + 1,
-// *ticket zero on entry; sorted holds n nodes, keep n bytes, ticket_of n words (a selected point's slot inside its
-// bucket).  n_buckets: a power of two >= 4096
-void launch_radius_filter(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m_cam, const CamK &cam,
-                          const BBoxTest &bt, int nb, bool use_plane, float thr_f, RansacState *st, int16_t *ids,
-                          uint32_t *cell_cnt, uint32_t *pre, uint32_t *blk_off, unsigned *ticket, CellNode *sorted, uint8_t *keep,
-                          uint32_t *ticket_of, long long *acc, uint32_t n_buckets, float r2f, int min_pts, hipStream_t s);
+// The bucket table of the radius filter: n_buckets (a power of two >= 4096 that only grows) counting-sort buckets.
+// k_cell_scan writes pre[0 .. n_buckets] and blk_off[0 .. n_buckets / 4096], the last of which is the number of
+// selected points.  The host allocates n_buckets + 4 and n_buckets / 4096 + 4 words: blk_off's slack holds the scan's
+// ticket, two words behind the number of selected points (one zeroed allocation for both); pre's is slack only.
+struct BucketTable {
+  uint32_t *cnt;            // n_buckets, zero on entry (every call counts them back to zero)
+  uint32_t *pre;            // pre_words(n_buckets): a bucket's first slot inside its scan block
+  uint32_t *blk_off;        // off_words(n_buckets), zero when allocated: block offsets | n_selected | - | ticket
+  uint32_t n_buckets;
+  static size_t pre_words(size_t nb) { return nb + 4; }
+  static size_t off_words(size_t nb) { return nb / 4096 + 4; }
+  // the table three allocations of these sizes hold: the smallest of what each has room for
+  static size_t held(size_t cnt_cap, size_t pre_cap, size_t off_cap)
+  {
+    const size_t p = pre_cap < 4 ? 0 : pre_cap - 4, o = off_cap < 4 ? 0 : (off_cap - 4) * 4096;
+    return cnt_cap < p ? (cnt_cap < o ? cnt_cap : o) : (p < o ? p : o);
+  }
+  uint32_t *n_selected() const { return blk_off + n_buckets / 4096; }
+  unsigned *scan_ticket() const { return blk_off + n_buckets / 4096 + 2; }   // zero between calls
+};
+// extractCloudPerBBox + RadiusOutlierRemoval: the first-match box of every point (ground points of st->refined dropped
+// when use_plane), the selected points in bucket order, and which of them survive the filter
+struct RadiusFilterArgs {
+  const float *x, *y, *z;   // the resident cloud (lidar frame), n each
+  uint32_t n;
+  Mat34f m_cam;
+  CamK cam;
+  BBoxTest bt;
+  int nb;
+  bool use_plane;
+  float thr_f;              // ground test (use_plane)
+  RansacState *st;          // device: the plane; n_inliers is counted here when use_plane
+  int16_t *ids;             // n
+  BucketTable tab;
+  CellNode *sorted;         // n nodes: the selected points in bucket order
+  uint8_t *keep;            // n: keep[t] = 1 where sorted point t survives the filter
+  uint32_t *ticket_of;      // n: a selected point's slot inside its bucket
+  long long *acc;           // pca_acc_words(nb), zero on entry: the kept points' coordinate sums
+  float r2f;                // largest float <= radius^2
+  int min_pts;
+};
+void launch_radius_filter(const RadiusFilterArgs &a, hipStream_t s);
 size_t pca_acc_words(int nb);   // 64-bit words of acc
 size_t pca_ext_words(int nb);   // 32-bit words of ext
 // centroid + PCA rectangle of every bbox's kept points (bboxPoseEstimation :156-181, computePCABoundingBox :187-247)
-// from order-independent integer sums: covariance pass, extents pass, poses by the last workgroup.  acc / ext
-// (pca_acc_words / pca_ext_words) / *ticket are zero on entry and left zero.  n_sel: device address of the number of
-// selected points (blk_off[n_buckets / 4096] of the bucket scan).  st_copy (optional): *st is copied there (one read-back
-// block for poses, flags and state); poses_dev (optional, device memory): a second copy of the camera-frame poses with
-// a NaN length where valid[b] == 0 (no pose: its corners fail getIndex, so k_rects_from_poses gives no cells)
-void launch_pca_rect(const CellNode *sorted, const uint32_t *n_sel, uint32_t n, const uint8_t *keep, long long *acc, unsigned *ext,
-                     unsigned *ticket, int nb, const RansacState *st, bool use_plane, gv_lshape_pose *poses, uint8_t *valid,
-                     RansacState *st_copy, const CallDone &done, hipStream_t s, gv_lshape_pose *poses_dev = nullptr);
+// from order-independent integer sums: covariance pass, extents pass, poses by the last workgroup
+struct PcaRectArgs {
+  const CellNode *sorted;   // launch_radius_filter's
+  const uint32_t *n_sel;    // device: the number of selected points (BucketTable::n_selected)
+  uint32_t n;               // points of the cloud
+  const uint8_t *keep;
+  long long *acc;           // pca_acc_words(nb): launch_radius_filter's sums; left zero
+  unsigned *ext;            // pca_ext_words(nb), zero on entry and left zero
+  unsigned *ticket;         // zero on entry and left zero
+  int nb;
+  const RansacState *st;
+  bool use_plane;           // an empty segmented cloud (no plane, or all ground) gives no poses
+  gv_lshape_pose *poses;    // nb, 16-byte aligned (stored as double2); may be host-mapped
+  uint8_t *valid;           // nb
+  RansacState *st_copy;     // optional, 8-byte aligned: *st rides home in the same block (64-bit words)
+  gv_lshape_pose *poses_dev;   // optional, device memory: a second copy with a NaN length where valid[b] == 0 (no pose:
+                               // its corners fail getIndex, so k_rects_from_poses gives no cells)
+};
+void launch_pca_rect(const PcaRectArgs &a, const CallDone &done, hipStream_t s);
 
 }  // namespace gv

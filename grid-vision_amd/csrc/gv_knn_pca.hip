@@ -45,12 +45,11 @@ __global__ void __launch_bounds__(256) k_project_uvd(const float *__restrict__ x
   }
 }
 
-void launch_project_uvd(const float *x, const float *y, const float *z, uint32_t n, const Mat34f &m,
-                        const CamK &cam, float *pu, float *pv, float *pd, hipStream_t s)
+void launch_project_uvd(const KnnArgs &a, hipStream_t s)
 {
-  if (!n) return;
-  const uint32_t blocks = (uint32_t)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(k_project_uvd, dim3(blocks), dim3(256), 0, s, x, y, z, n, m, cam, pu, pv, pd);
+  if (!a.n) return;
+  const uint32_t blocks = (uint32_t)((a.n + 255) / 256 < 4096 ? (a.n + 255) / 256 : 4096);
+  hipLaunchKernelGGL(k_project_uvd, dim3(blocks), dim3(256), 0, s, a.x, a.y, a.z, a.n, a.m_cam, a.cam, a.pu, a.pv, a.pd);
 }
 
 // (d2, index) candidates ordered lexicographically: equal distances resolve to the lower point index (the
@@ -298,17 +297,16 @@ __global__ void __launch_bounds__(64) k_knn_stage2(const KnnKey *__restrict__ pa
 int knn_chunks() { return 64 * kKnnListsPerLane / kKnnWaves / 2; }   // 32 chunks x 4 wavefronts = 128 lists: two per lane
 size_t knn_partial_entries(int nb, int k) { return (size_t)nb * knn_chunks() * kKnnWaves * k; }
 
-void launch_knn(const float *pu, const float *pv, const float *pd, uint32_t n, const gv_bbox *bboxes, int nb, int k,
-                Cand2 *partial, float *depths, float *knn_d2, const CallDone &done, hipStream_t s)
+void launch_knn(const KnnArgs &a, const CallDone &done, hipStream_t s)
 {
-  if (nb <= 0) return;
+  if (a.nb <= 0) return;
   static_assert(sizeof(Cand2) == sizeof(KnnKey), "candidate layout");
   const int nchunks = knn_chunks();
-  hipLaunchKernelGGL(k_knn_stage1, dim3(nchunks, nb), dim3(kKnnThreads), 0, s, pu, pv, pd, n, bboxes, k,
-                     reinterpret_cast<KnnKey *>(partial));
-  const size_t lds2 = ((size_t)nchunks * kKnnWaves * k + kKnnMaxK) * sizeof(KnnKey);   // 128 lists x k <= 32 keys: 32 KB
-  hipLaunchKernelGGL(k_knn_stage2, dim3(nb), dim3(64), lds2, s, reinterpret_cast<const KnnKey *>(partial), nchunks * kKnnWaves, k,
-                     pd, depths, knn_d2, done);
+  hipLaunchKernelGGL(k_knn_stage1, dim3(nchunks, a.nb), dim3(kKnnThreads), 0, s, a.pu, a.pv, a.pd, a.n, a.bboxes, a.k,
+                     reinterpret_cast<KnnKey *>(a.partial));
+  const size_t lds2 = ((size_t)nchunks * kKnnWaves * a.k + kKnnMaxK) * sizeof(KnnKey);   // 128 lists x k <= 32 keys: 32 KB
+  hipLaunchKernelGGL(k_knn_stage2, dim3(a.nb), dim3(64), lds2, s, reinterpret_cast<const KnnKey *>(a.partial), nchunks * kKnnWaves,
+                     a.k, a.pd, a.depths, a.knn_d2, done);
 }
 
 }  // namespace gv

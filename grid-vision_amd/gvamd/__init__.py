@@ -210,6 +210,15 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _boxes(bboxes):
+    return np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
+
+
+def _pose_outputs(b):
+    """(poses, valid) for the boxes b: one entry at least, so that an empty call still hands the library a pointer"""
+    return np.zeros(max(len(b), 1), dtype=LSHAPE_DTYPE), np.zeros(max(len(b), 1), np.uint8)
+
+
 def _pose_batch(poses, device_ptr, K=None, P=None):
     """(src, K, P, flags) of a (K, P, 3) pose batch for the scoring calls.  The asynchronous calls give K and P and their
     array is used where it is (it stays the caller's until completion); otherwise K and P come from the shape and host
@@ -418,7 +427,7 @@ class GridVisionHIP:
         return x, y, z
 
     def extract_cloud_per_bbox(self, bboxes):
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
+        b = _boxes(bboxes)
         ids = np.empty(self.n, np.int32)
         counts = np.zeros(max(len(b), 1), np.int32)
         self._ck(self._lib.gv_extract_cloud_per_bbox(self._h, _ptr(b), C.c_int32(len(b)), _ptr(ids), _ptr(counts)),
@@ -426,7 +435,7 @@ class GridVisionHIP:
         return ids, counts[:len(b)]
 
     def compute_depth_for_bboxes(self, bboxes, k):
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
+        b = _boxes(bboxes)
         depths = np.zeros(len(b), np.float32)
         d2 = np.zeros((len(b), k), np.float32)
         self._ck(self._lib.gv_compute_depth_for_bboxes(self._h, _ptr(b), C.c_int32(len(b)), C.c_int32(k),
@@ -434,7 +443,7 @@ class GridVisionHIP:
         return depths, d2
 
     def convert_pixels_to_3d(self, bboxes, depths):
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
+        b = _boxes(bboxes)
         d = _f32(depths)
         out = np.zeros((len(b), 3), np.float64)
         self._ck(self._lib.gv_convert_pixels_to_3d(self._h, _ptr(b), _ptr(d), C.c_int32(len(b)), _ptr(out)),
@@ -442,9 +451,8 @@ class GridVisionHIP:
         return out
 
     def compute_bbox_pose(self, bboxes):
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
-        poses = np.zeros(max(len(b), 1), dtype=LSHAPE_DTYPE)
-        valid = np.zeros(max(len(b), 1), np.uint8)
+        b = _boxes(bboxes)
+        poses, valid = _pose_outputs(b)
         self._ck(self._lib.gv_compute_bbox_pose(self._h, _ptr(b), C.c_int32(len(b)), _ptr(poses), _ptr(valid)),
                  "compute_bbox_pose")
         return poses[:len(b)], valid[:len(b)]
@@ -459,9 +467,8 @@ class GridVisionHIP:
         return m.value, mask[:self.n], coeff
 
     def compute_bbox_pose_ground_removed(self, bboxes):
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
-        poses = np.zeros(max(len(b), 1), dtype=LSHAPE_DTYPE)
-        valid = np.zeros(max(len(b), 1), np.uint8)
+        b = _boxes(bboxes)
+        poses, valid = _pose_outputs(b)
         npz = C.c_int32(0)
         self._ck(self._lib.gv_compute_bbox_pose_ground_removed(self._h, _ptr(b), C.c_int32(len(b)), _ptr(poses),
                                                                _ptr(valid), C.byref(npz)), "compute_bbox_pose_gr")
@@ -469,8 +476,8 @@ class GridVisionHIP:
 
     def vision_post_process(self, orient, conf, dims, bboxes):
         o, c, d = _f32(orient), _f32(conf), _f32(dims)
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
-        poses = np.zeros(max(len(b), 1), dtype=LSHAPE_DTYPE)
+        b = _boxes(bboxes)
+        poses, _ = _pose_outputs(b)
         m = C.c_int32(0)
         self._ck(self._lib.gv_vision_post_process(self._h, _ptr(o), _ptr(c), _ptr(d), _ptr(b), C.c_int32(len(b)),
                                                   _ptr(poses), C.byref(m)), "vision_post_process")
@@ -480,7 +487,7 @@ class GridVisionHIP:
         """test hook (csrc/gv_test_hooks.h): (nb, 64, 4) loc0, loc1, loc2, err of every constraint set of k_vision, and
         the (nb,) winner, 64 = none"""
         o, c, d = _f32(orient), _f32(conf), _f32(dims)
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
+        b = _boxes(bboxes)
         sets = np.zeros((len(b), 64, 4), np.float32)
         winner = np.zeros(len(b), np.int32)
         self._ck(self._lib.gv_test_vision_sets(self._h, _ptr(o), _ptr(c), _ptr(d), _ptr(b), C.c_int32(len(b)),
@@ -491,9 +498,8 @@ class GridVisionHIP:
         """test hook (csrc/gv_test_hooks.h): compute_bbox_pose (or compute_bbox_pose_ground_removed) and what it left on
         the device: (poses, valid, nodes, keep) -- nodes: the selected points in bucket order as a structured array
         (x, y, z float32 in the camera frame, id int32), keep: their radius-filter flags"""
-        b = np.ascontiguousarray(bboxes, dtype=BBOX_DTYPE)
-        poses = np.zeros(max(len(b), 1), dtype=LSHAPE_DTYPE)
-        valid = np.zeros(max(len(b), 1), np.uint8)
+        b = _boxes(bboxes)
+        poses, valid = _pose_outputs(b)
         nodes = np.zeros(max(self.n, 1), dtype=NODE_DTYPE)
         keep = np.zeros(max(self.n, 1), np.uint8)
         npz, m = C.c_int32(0), C.c_int64(0)

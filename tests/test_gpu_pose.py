@@ -169,3 +169,74 @@ def test_nothing_stale_after_a_large_call(gvamd):
         for s in (big, small["selected-1"], small["nb-300"], small["nb-1"], big, small["selected-0"], small["cloud-1"],
                   small["nb-129"], P.family("degenerate")[0], big):
             _check(h, s)
+
+
+def _result_bytes(r):
+    """a call's outputs (a tuple, or a tick's dict) as a list of byte strings"""
+    vals = [r[k] for k in sorted(r)] if isinstance(r, dict) else list(r)
+    return [np.asarray(v).tobytes() for v in vals]
+
+
+def test_calls_share_one_result_block(gvamd):
+    """kNN depth, the two pose calls, the ground plane and both ticks take turns on ONE handle: they share the result
+    block (regrown by the 300-box pose, 300 * 81 + 56 bytes, with earlier calls' sequence numbers behind it), the
+    sequence counter and the pose scratch.  Every step's outputs equal, byte for byte, those of the same call on a fresh
+    handle given the same cloud.  Between the PCA tick's enqueue and its wait the calls that would reuse the block are
+    refused with GV_ERR_STATE and leave the tick's result as it is."""
+    from gvamd import synth
+    sizes = {s.tag: s for s in P.family("sizes")}
+    one, many, plane = sizes["nb-1"], sizes["nb-300"], P.with_plane(sizes["nb-129"])
+    for s in (one, many, plane):
+        assert len(s.x) <= 8192                       # a fresh handle's 4096 buckets
+    assert 300 * 81 + 56 > 16384 - 64                 # the first block does not hold the 300-box pose
+    static = P.grid_boxes(4, 3, 3)
+    static["label"] = 5                               # gv_filter_bboxes: static
+    mixed = np.concatenate([plane.boxes[:40], static])   # the dynamic boxes first: first match wins
+    net = synth.network_outputs(40)
+    refused = {}
+
+    def knn(h):
+        return h.compute_depth_for_bboxes(static, 4)
+
+    def ground(h):
+        m, mask, coeff = h.segment_ground_plane()
+        return np.int64(m), mask, coeff
+
+    def pca_tick_with_refusals(h):
+        h.tick_enqueue(mixed, k_near=4)
+        for name, call in (("depth", lambda: knn(h)), ("pose", lambda: h.compute_bbox_pose(one.boxes)),
+                           ("ground", lambda: h.segment_ground_plane()),
+                           ("pose_ground_removed", lambda: h.compute_bbox_pose_ground_removed(plane.boxes))):
+            with pytest.raises(gvamd.GVError) as e:
+                call()
+            refused[name] = (e.value.code, str(e.value))
+        return h.tick_wait()
+
+    steps = [("knn", plane, knn, knn),
+             ("pose nb-1", one, lambda h: h.compute_bbox_pose(one.boxes), None),
+             ("pose nb-300", many, lambda h: h.compute_bbox_pose(many.boxes), None),
+             ("ground plane", plane, ground, None),
+             ("pose ground removed", plane, lambda h: h.compute_bbox_pose_ground_removed(plane.boxes), None),
+             ("vision tick", plane, lambda h: h.tick(mixed, k_near=4, vision=True, net=net), None),
+             ("pca tick", plane, pca_tick_with_refusals, lambda h: h.tick(mixed, k_near=4)),
+             ("knn again", plane, knn, None),
+             ("pose nb-1 again", one, lambda h: h.compute_bbox_pose(one.boxes), None)]
+    got = {}
+    with _handle(gvamd) as shared:
+        for tag, s, call, alone in steps:
+            shared.upload_xyz(s.x, s.y, s.z)
+            got[tag] = call(shared)
+            with _handle(gvamd) as fresh:
+                fresh.upload_xyz(s.x, s.y, s.z)
+                want = (alone or call)(fresh)
+            assert _result_bytes(got[tag]) == _result_bytes(want), tag
+    for name, (code, msg) in refused.items():
+        assert code == 5 and "a tick is pending: call gv_tick_wait first" in msg, (name, code, msg)
+    assert len(refused) == 4
+    # the steps computed something: depths, 300 boxes' worth of poses, a plane, poses from both ticks
+    assert (got["knn"][0] > 0).all()
+    for tag, s in (("pose nb-1", one), ("pose nb-300", many)):
+        assert np.array_equal(got[tag][1], P.reference(s)[1].valid) and got[tag][1].any(), tag
+    assert 5000 <= int(got["ground plane"][0]) < len(plane.x) and got["pose ground removed"][2] >= 20
+    assert got["vision tick"]["n_static"] == 3 and got["vision tick"]["n_dynamic"] == 40
+    assert not got["pca tick"]["pca_empty"] and len(got["pca tick"]["poses"]) > 0 and len(got["pca tick"]["depths"]) == 3

@@ -4,8 +4,12 @@ build (GV_LIB_AB) under HIP API tracing and compare the ordered lists of API nam
 GV_QUEUE_PROBE=0: the probe's round count depends on timing.  Every step is followed by a synchronize.
 python3 tools/api_order.py planner  runs the planner calls instead: inflate, score_trajectories, nav_field, score_nav with
 host and device poses and pinned and pageable destinations.
-python3 tools/api_order.py compare a_hip_api_trace.csv b_hip_api_trace.csv [--no-alloc]  prints the first differences;
---no-alloc leaves hipMalloc and hipFree out of both lists (a change of who owns which buffer moves only those)."""
+python3 tools/api_order.py pose  runs the pose family on a fresh handle: kNN depth, poses of 1 and of 300 boxes (the second
+regrows the result block), the ground plane with and without its mask, the ground-removed pose with and without boxes,
+the vision post-process, a vision tick, a PCA tick with static and dynamic boxes, kNN depth again.
+python3 tools/api_order.py compare a_hip_api_trace.csv b_hip_api_trace.csv [--no-alloc] [--no-query]  prints the first
+differences; --no-alloc leaves hipMalloc and hipFree out of both lists (a change of who owns which buffer moves only
+those), --no-query hipStreamQuery (the result block's wait asks the stream once per 4096 spins: how often is timing)."""
 import csv, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -82,21 +86,57 @@ def run_planner():
     h.close()
 
 
-def names(path, no_alloc=False):
+def run_pose():
+    sys.path.insert(0, os.path.join(ROOT, "grid-vision_amd"))
+    import ctypes as C
+    import gvamd
+    from gvamd import synth
+    g = synth.CONFIGS[1]["grid"]
+    tfs = synth.transforms(True)
+    x, y, z, _ = synth.cloud_uniform(1)
+    bb, many = synth.detections(1, 12), synth.detections(1, 300)
+    st, dy = gvamd.filter_bboxes(bb)
+    assert len(st) and len(dy)
+    net = synth.network_outputs(len(dy))
+    h = gvamd.GridVisionHIP(g.grid_x, g.grid_y, g.resolution)
+    h.set_transforms(tfs["cam_lidar"], tfs["base_cam"], tfs["base_lidar"])
+    steps = [lambda: h.upload_xyz(x, y, z),
+             lambda: h.compute_depth_for_bboxes(st, 4),
+             lambda: h.compute_bbox_pose(bb[:1]),
+             lambda: h.compute_bbox_pose(many),
+             lambda: h.segment_ground_plane(),
+             lambda: h._ck(h._lib.gv_segment_ground_plane(h._h, C.c_double(0.04), C.c_int32(50), C.c_uint64(12345), None, None, None),
+                           "segment_ground_plane"),
+             lambda: h.compute_bbox_pose_ground_removed(bb),
+             lambda: h.compute_bbox_pose_ground_removed(bb[:0]),
+             lambda: h.vision_post_process(*net, dy),
+             lambda: h.tick(bb, k_near=4, vision=True, net=net),
+             lambda: h.tick(bb, k_near=4),
+             lambda: h.compute_depth_for_bboxes(st, 4)]
+    for step in steps:
+        h.synchronize()
+        step()
+    h.synchronize()
+    h.close()
+
+
+def names(path, skip=()):
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    return [r["Function"] for r in rows if not (no_alloc and r["Function"] in ("hipMalloc", "hipFree"))]
+    return [r["Function"] for r in rows if r["Function"] not in skip]
 
 
 if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "compare":
-        no_alloc = "--no-alloc" in sys.argv[4:]
-        a, b = names(sys.argv[2], no_alloc), names(sys.argv[3], no_alloc)
+        skip = ("hipMalloc", "hipFree") * ("--no-alloc" in sys.argv[4:]) + ("hipStreamQuery",) * ("--no-query" in sys.argv[4:])
+        a, b = names(sys.argv[2], skip), names(sys.argv[3], skip)
         diff = [(i, p, q) for i, (p, q) in enumerate(zip(a, b)) if p != q]
         print(f"{len(a)} and {len(b)} HIP API calls, {len(diff)} positions differ" + ("" if diff or len(a) != len(b) else ": identical order"))
         for i, p, q in diff[:20]:
             print(f"  #{i}: {p}  |  {q}")
     elif sys.argv[1:] == ["planner"]:
         run_planner()
+    elif sys.argv[1:] == ["pose"]:
+        run_pose()
     else:
         run()
