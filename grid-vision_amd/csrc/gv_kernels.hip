@@ -692,7 +692,8 @@ __global__ void __launch_bounds__(256) k_ray_march(const uint32_t *__restrict__ 
       const int num = half + i * minor;
       int q = (int)((double)num * rcp);
       const int rem = num - q * major;        // exact integer quotient after one correction
-      if (rem >= major) ++q;
+      if (major == 0) q = 0;                  // a clipped end in the origin cell itself: the line is that one cell
+      else if (rem >= major) ++q;
       else if (rem < 0) --q;
       const int cx = o.cx + sx * (xmaj ? i : q);
       const int cy = o.cy + sy * (xmaj ? q : i);
