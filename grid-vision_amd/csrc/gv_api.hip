@@ -45,7 +45,7 @@ int drain(gv_context *h)
   h->cloud_wait = false;
   for (auto &c : h->cloud) { c.seen = ~0u; c.release_slot = -1; }   // every upload landed, every reader finished
   for (auto &d : h->det) { d.seen = ~0u; d.release_slot = -1; d.readers = 0; }
-  for (auto &b : h->sb) b.sh_counts_slot = -1;
+  h->sh.forget_frames();
   return GV_OK;
 }
 
@@ -69,8 +69,14 @@ int use_device(gv_context *h)
 // plain grid update (A7 / A8 / A10): rectangles already in fs[0].rects
 int enqueue_plain_update(gv_context *h, int32_t n_rects)
 {
-  if (sector_path(h))   // the frame's grid pass without the hit/miss rule, over every row
-    return enqueue_grid_pass(h, 0, h->fs[0].rects, n_rects, false, 0, h->g.ny, h->stream, nullptr, nullptr, nullptr, false, false);
+  if (sector_path(h)) {   // the frame's grid pass without the hit/miss rule, over every row
+    GridPassJob grid;   // buffer set 0, no hit / miss rule
+    grid.rects = h->fs[0].rects; grid.n_rects = n_rects;
+    grid.y1 = h->g.ny;
+    grid.stream = h->stream;
+    grid.of_frame = false;
+    return enqueue_grid_pass(h, grid);
+  }
   launch_finalize(finalize_args(h, n_rects), h->stream);
   GV_HIP(hipGetLastError());
   return GV_OK;
@@ -172,6 +178,9 @@ namespace {
     if ((call) != 0) return GV_ERR_HIP;                      \
   } while (0)
 
+// bitmaps are padded to whole binning tiles, so that every word belongs to exactly one tile
+int32_t pad_to_tiles(int32_t n) { return kBinTile * ((n + kBinTile - 1) / kBinTile); }
+
 // every knob of the handle, from the environment
 void read_tuning(Tuning &t)
 {
@@ -232,9 +241,8 @@ bool set_geometry(gv_context *h, uint8_t grid_x, uint8_t grid_y, double resoluti
   h->bt_tiles_y = std::max(1, (cam->orig_h + 15) / 16);
   // packed (a,b) fields hold 13 bits each; vector stores need nx % 4 == 0
   h->tile_path = (g.nx % 4 == 0) && g.nx <= 8000 && g.ny <= 8000;
-  // bitmaps: padded to whole binning tiles, so that every word belongs to exactly one tile
-  h->nx_pad = kBinTile * ((g.nx + kBinTile - 1) / kBinTile);
-  h->ny_pad = kBinTile * ((g.ny + kBinTile - 1) / kBinTile);
+  h->nx_pad = pad_to_tiles(g.nx);
+  h->ny_pad = pad_to_tiles(g.ny);
   h->nxw = h->nx_pad / 32;
   h->nyw = h->ny_pad / 32;
   h->tiles_x = h->nx_pad / kBinTile;
@@ -350,7 +358,7 @@ int alloc_grid(gv_context *h)
     h->bmT_words = (size_t)h->nx_pad * h->nyw;
     h->ends_words = 2 * (h->bmN_words + h->bmT_words);
     for (FrameSet &f : h->fs) {
-      // + slack: the sharded exchange pads the buffer to `world` equal slices
+      // + slack: the sharded exchange pads the buffer to `world` equal slices (host::ShardPlan::slice)
       GV_C(f.ends.reserve_zeroed(h, h->ends_words + 1024, h->stream));
       f.hitN = f.ends;
       f.clipN = f.hitN + h->bmN_words;
@@ -412,6 +420,7 @@ int gv_create(gv_handle *out, uint8_t grid_x, uint8_t grid_y, double resolution,
   if (h->tune.queue_probe && (rc = probe_upload_queue(h))) return fail(rc);
   if ((rc = create_events(h))) return fail(rc);
   if ((rc = alloc_grid(h))) return fail(rc);
+  h->sh.plan = shard_plan(h, 1);
   *out = h;
   rc = gv_reset(h);
   if (rc != GV_OK) { *out = nullptr; return fail(rc); }
@@ -611,6 +620,40 @@ int gv_filter_bboxes(const gv_bbox *in, int32_t n, gv_bbox *static_out, int32_t 
   return GV_OK;
 }
 
+// host only, no handle: the sharded frame's bands and slices (host::ShardPlan, gv_host_math.hpp)
+int gv_shard_band_rows(int32_t rank, int32_t world, int32_t ny, int32_t *y0, int32_t *y1)
+{
+  if (world < 1 || rank < 0 || rank >= world || ny < 1 || !y0 || !y1) return GV_ERR_BAD_ARG;
+  host::shard_band_rows(rank, world, ny, pad_to_tiles(ny), *y0, *y1);
+  return GV_OK;
+}
+
+int64_t gv_shard_slice_words(int64_t words, int32_t world)
+{
+  if (words < 0 || world < 1) return -1;
+  return (int64_t)host::shard_slice_words((size_t)words, world);
+}
+
+// test hook (gv_test_hooks.h): the plan a handle over an nx x ny grid (tile path) keeps for a communicator of `world` ranks
+int gv_test_shard_plan(int32_t nx, int32_t ny, int32_t world, int64_t *slice, int64_t *chunk, int32_t *equal_bands,
+                       int64_t *cnt0, int32_t *rows)
+{
+  if (nx < 1 || ny < 1 || world < 1 || !slice || !chunk || !equal_bands || !cnt0 || !rows) return GV_ERR_BAD_ARG;
+  const int32_t nx_pad = pad_to_tiles(nx), ny_pad = pad_to_tiles(ny);
+  const size_t ends_words = 2 * ((size_t)ny_pad * (size_t)(nx_pad / 32) + (size_t)nx_pad * (size_t)(ny_pad / 32));   // alloc_grid's
+  try {
+    const host::ShardPlan P(nx, ny, nx_pad, ny_pad, nx_pad / 32, ends_words, world);
+    *slice = (int64_t)P.slice;
+    *chunk = (int64_t)P.chunk;
+    *equal_bands = P.equal_bands ? 1 : 0;
+    *cnt0 = (int64_t)P.cnt0;
+    for (int r = 0; r < world; ++r) { rows[2 * r] = P.bands[(size_t)r].y0; rows[2 * r + 1] = P.bands[(size_t)r].y1; }
+  } catch (...) {
+    return GV_ERR_HIP;
+  }
+  return GV_OK;
+}
+
 int gv_get_intrinsics(gv_handle h, double K[9], double K_inv[9])
 {
   if (!h) return GV_ERR_BAD_ARG;
@@ -638,7 +681,11 @@ int gv_update_map_poses(gv_handle h, const gv_lshape_pose *poses, int32_t n)
   int rc = use_device(h);
   if (rc) return rc;
   DetSet &d = h->det[2];
-  if ((rc = upload_det(h, d, nullptr, 0, poses, n, nullptr, nullptr, nullptr, h->stream, false))) return rc;
+  DetUpload u;
+  u.poses = poses; u.n_poses = n;
+  u.stream = h->stream;
+  u.masks = false;
+  if ((rc = upload_det(h, d, u))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
   if (n) launch_rects_from_poses(d.poses, n, h->g, false, h->x_bc, h->fs[0].rects, h->stream);
   if ((rc = enqueue_plain_update(h, n))) return rc;

@@ -301,12 +301,11 @@ void note_frame_readers(gv_context *h, int slot, int p, CloudSet &CS, DetSet &D,
 // n_net >= 0: the network outputs cover n_net boxes (default: nb).  nb_test >= 0: the bbox test -- thresholds, tile
 // masks, d.nb -- covers the first nb_test boxes only; what follows them in the block is read by other kernels (the
 // tick keeps [all | static | dynamic] boxes in one block: one copy).
-int upload_det(gv_context *h, DetSet &d, const gv_bbox *bboxes, int32_t nb, const gv_lshape_pose *poses,
-               int32_t n_poses, const float *orient, const float *conf, const float *dims, hipStream_t s, bool masks,
-               int32_t n_net, int32_t nb_test, bool fused)
+int upload_det(gv_context *h, DetSet &d, const DetUpload &u)
 {
-  if (n_net < 0) n_net = nb;
-  if (nb_test < 0) nb_test = nb;
+  const int32_t nb = u.nb, n_poses = u.n_poses;
+  const int32_t n_net = u.n_net < 0 ? nb : u.n_net, nb_test = u.nb_test < 0 ? nb : u.nb_test;
+  hipStream_t s = u.stream;
   int rc = ensure_det(h, d, std::max(nb, n_poses));
   if (rc) return rc;
   if ((rc = ensure_det_shared(h, std::max(nb, n_poses)))) return rc;
@@ -318,20 +317,20 @@ int upload_det(gv_context *h, DetSet &d, const gv_bbox *bboxes, int32_t nb, cons
     std::memcpy(d.stage + off, src, bytes);
     used = std::max(used, off + bytes);
   };
-  put(L.bboxes, bboxes, (size_t)nb * sizeof(gv_bbox));
-  put(L.poses, poses, (size_t)n_poses * sizeof(gv_lshape_pose));
-  if (orient) put(L.orient, orient, (size_t)n_net * 4 * sizeof(float));
-  if (conf) put(L.conf, conf, (size_t)n_net * 2 * sizeof(float));
-  if (dims) put(L.dims, dims, (size_t)n_net * 3 * sizeof(float));
+  put(L.bboxes, u.bboxes, (size_t)nb * sizeof(gv_bbox));
+  put(L.poses, u.poses, (size_t)n_poses * sizeof(gv_lshape_pose));
+  if (u.orient) put(L.orient, u.orient, (size_t)n_net * 4 * sizeof(float));
+  if (u.conf) put(L.conf, u.conf, (size_t)n_net * 2 * sizeof(float));
+  if (u.dims) put(L.dims, u.dims, (size_t)n_net * 3 * sizeof(float));
   d.mask_words = std::max(1, (nb_test + 63) / 64);
-  if (fused && used) {
+  if (u.fused && used) {
     // fused: ONE kernel reads the pinned staging (device visible) -- copies the block and builds the tables from the
     // staged boxes -- instead of a copy command (7 us as a blit kernel) + the table kernel behind it
-    launch_bbox_prepare(reinterpret_cast<const gv_bbox *>(d.stage + L.bboxes), masks ? nb_test : 0, h->bt_tiles_x, h->bt_tiles_y,
+    launch_bbox_prepare(reinterpret_cast<const gv_bbox *>(d.stage + L.bboxes), u.masks ? nb_test : 0, h->bt_tiles_x, h->bt_tiles_y,
                         d.mask_words, d.bbox_f, d.tile_mask, s, d.stage, d.block, used);
   } else {
     if (used) GV_HIP(hipMemcpyAsync(d.block, d.stage, used, hipMemcpyHostToDevice, s));
-    if (masks) launch_bbox_prepare(d.bboxes, nb_test, h->bt_tiles_x, h->bt_tiles_y, d.mask_words, d.bbox_f, d.tile_mask, s);
+    if (u.masks) launch_bbox_prepare(d.bboxes, nb_test, h->bt_tiles_x, h->bt_tiles_y, d.mask_words, d.bbox_f, d.tile_mask, s);
   }
   GV_HIP(hipGetLastError());
   d.nb = nb_test;
@@ -346,7 +345,12 @@ int upload_scratch_bboxes(gv_context *h, const gv_bbox *b, int32_t nb, bool mask
   if (h->tick.pending) { h->err = "a tick is pending: call gv_tick_wait first"; return GV_ERR_STATE; }
   DetSet &d = h->det[2];
   // (fused: the table kernel reads the pinned staging itself -- one launch instead of a copy command + a kernel: 6 us)
-  int rc = upload_det(h, d, b, nb, nullptr, 0, nullptr, nullptr, nullptr, h->stream, masks, -1, -1, true);
+  DetUpload u;
+  u.bboxes = b; u.nb = nb;
+  u.stream = h->stream;
+  u.masks = masks;
+  u.fused = true;
+  int rc = upload_det(h, d, u);
   if (rc) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
   return GV_OK;
@@ -355,7 +359,7 @@ int upload_scratch_bboxes(gv_context *h, const gv_bbox *b, int32_t nb, bool mask
 // poses / network outputs of detection set D -> index rectangles on stream s
 int32_t enqueue_rects(gv_context *h, const DetSet &D, Rect *rects, VisionOut *vout, hipStream_t s)
 {
-  const bool vision = D.flags & GV_FRAME_VISION_ORIENT;
+  const bool vision = frame_flags(D.flags).vision;
   if (vision && D.nb > 0) {
     launch_vision(D.orient, D.conf, D.dims, D.bboxes, D.nb, h->cam, vout, D.poses, nullptr, s);
     launch_rects_from_poses(D.poses, D.nb, h->g, true, h->x_bc, rects, s);
@@ -370,11 +374,11 @@ int32_t enqueue_rects(gv_context *h, const DetSet &D, Rect *rects, VisionOut *vo
 
 int check_frame_flags(const gv_context *h, uint32_t fl)
 {
-  const bool do_bin = fl & GV_FRAME_BIN, do_ray = fl & GV_FRAME_RAYMARCH, do_bbox = fl & GV_FRAME_BBOX_TEST;
-  if (do_ray && !do_bin) return GV_ERR_BAD_ARG;
-  if (do_bin && !h->has_bl) return GV_ERR_TF;
-  if (do_bbox && !h->has_cl) return GV_ERR_TF;
-  if ((fl & GV_FRAME_VISION_ORIENT) && !h->has_bc) return GV_ERR_TF;
+  const FrameFlags f = frame_flags(fl);
+  if (f.ray && !f.bin) return GV_ERR_BAD_ARG;
+  if (f.bin && !h->has_bl) return GV_ERR_TF;
+  if (f.bbox && !h->has_cl) return GV_ERR_TF;
+  if (f.vision && !h->has_bc) return GV_ERR_TF;
   return GV_OK;
 }
 
@@ -383,11 +387,14 @@ int check_frame_flags(const gv_context *h, uint32_t fl)
 
 // partition + tile histogram of points [lo, lo + n) of the current cloud on stream k: that stream's hits[]
 // (or not), per-point outputs and binning scratch; the end bitmaps of buffer set p; zeroes the set's
-// free-cell bitmaps.  ev_* are stage-timing events or null.
-int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, size_t n, bool keep_cell, bool do_ray,
-                    bool do_bbox, bool write_hits, hipEvent_t ev_points, Rect *fold_rects, bool timed,
-                    bool any_order)
+// free-cell bitmaps.  (BinningJob, gv_context.hpp, says what each field asks for.)
+int enqueue_binning(gv_context *h, const BinningJob &job)
 {
+  const DetSet &D = job.det;
+  const int p = job.set, k = job.stream;
+  const size_t lo = job.lo, n = job.n;
+  Rect *const fold_rects = job.fold_rects;
+  const bool timed = job.timed;
   hipStream_t s = h->streams[k];
   const uint32_t chunk = bin_chunk_for(n);
   const uint32_t n_wg = (uint32_t)((n + chunk - 1) / chunk);
@@ -411,11 +418,11 @@ int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, siz
   a.nb = D.nb;
   a.nb_pad = (D.nb + 3) & ~3;
   a.bbox_id = h->sb[k].bbox_id + lo;
-  a.cell_idx = keep_cell ? h->sb[k].cell_idx + lo : nullptr;
-  a.do_ray = do_ray;
+  a.cell_idx = job.keep_cell ? h->sb[k].cell_idx + lo : nullptr;
+  a.do_ray = job.do_ray;
   // the fused bbox test keeps its tables in LDS; a detection set too large for that (hundreds of boxes, or a
   // large image: one mask word per 16x16-pixel tile) runs the test as a pass of its own over the cloud
-  const bool bbox_fused = do_bbox && bin_bbox_fits(D.nb, a.bt);
+  const bool bbox_fused = job.do_bbox && bin_bbox_fits(D.nb, a.bt);
   a.do_bbox = bbox_fused;
   a.chunk = chunk;
   a.n_wg = n_wg;
@@ -433,11 +440,11 @@ int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, siz
   a.dbg = h->d_bin_dbg[0];
   a.tl = h->tl_slot(0);
 #endif
-  launch_bin_partition(a, s, timed ? h->kt[0][0] : nullptr, timed ? h->kt[0][1] : nullptr, any_order);
+  launch_bin_partition(a, s, timed ? h->kt[0][0] : nullptr, timed ? h->kt[0][1] : nullptr, job.any_order);
   h->sb[k].lane_clean = false;
   if (timed) h->kt_used[0] = n > 0 || fold_rects;
-  if (do_bbox && !bbox_fused) launch_points(bbox_points_args(h, D, lo, n, a.bbox_id), s);
-  if (ev_points) GV_HIP(hipEventRecord(ev_points, s));
+  if (job.do_bbox && !bbox_fused) launch_points(bbox_points_args(h, D, lo, n, a.bbox_id), s);
+  if (job.ev_points) GV_HIP(hipEventRecord(job.ev_points, s));
   BinTileArgs t{};
   t.nx = h->g.nx; t.ny = h->g.ny;
   t.tiles_x = h->tiles_x; t.tiles_y = h->tiles_y; t.n_tiles = h->n_tiles;
@@ -451,7 +458,7 @@ int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, siz
   t.scratch = h->sb[k].bin_scratch;
   t.split_keys = kBinSplitKeys;
   t.max_slots = (uint32_t)h->bin_slots;
-  t.hits = write_hits ? h->sb[k].hits : nullptr;
+  t.hits = job.write_hits ? h->sb[k].hits : nullptr;
   t.hitN = h->fs[p].hitN; t.clipN = h->fs[p].clipN; t.hitT = h->fs[p].hitT; t.clipT = h->fs[p].clipT;
   t.freeN = h->fs[p].freeN; t.freeT = h->fs[p].freeT;
   t.nxw = h->nxw; t.nyw = h->nyw; t.nx_pad = h->nx_pad; t.ny_pad = h->ny_pad;
@@ -466,56 +473,54 @@ int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, siz
   return GV_OK;
 }
 
-// sector ray stage over the end bitmaps of set p into its free-cell bitmaps; workgroups first,
+// sector ray stage over the end bitmaps of set job.set into its free-cell bitmaps; workgroups first,
 // first + stride, ... of the dispatch order (one GPU: 0, 1)
-int enqueue_sectors(gv_context *h, int p, int first, int stride, hipStream_t s, hipEvent_t done,
-                    bool *done_attached, hipEvent_t t0)
+int enqueue_sectors(gv_context *h, SectorsJob &job)
 {
-  if (done_attached) *done_attached = false;
+  job.done_attached = false;
   if (!h->org.valid) return GV_OK;
   SectorArgs sa{};
-  int rc = fill_sector_args(h, sa, p);
+  int rc = fill_sector_args(h, sa, job.set);
   if (rc) return rc;
-  sa.wg_first = first;
-  sa.wg_stride = stride;
-  const bool launched = launch_ray_sectors(sa, s, done, t0);
-  if (done_attached) *done_attached = launched && done;
+  sa.wg_first = job.first;
+  sa.wg_stride = job.stride;
+  const bool launched = launch_ray_sectors(sa, job.stream, job.done, job.t0);
+  job.done_attached = launched && job.done;
   GV_HIP(hipGetLastError());
   return GV_OK;
 }
 
-// The tile grid pass over rows [y0, y1) with the bitmaps of set p.  of_frame = false: a plain map update (diagnostic
-// build: the timeline stamps stay with the frames).
-int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, bool counts, int32_t y0, int32_t y1,
-                      hipStream_t s, hipEvent_t done, hipEvent_t t0, bool *launched, bool sharded, bool of_frame)
+// The tile grid pass over rows [job.y0, job.y1) with the bitmaps of set job.set.
+int enqueue_grid_pass(gv_context *h, GridPassJob &job)
 {
+  const int p = job.set;
+  const int32_t y0 = job.y0, y1 = job.y1;
   // a sharded pass writes this rank's band whole and leaves the layers out of step (gv_context::layers_in_step)
-  const bool dense = sharded || h->grid_pass_dense();
+  const bool dense = job.sharded || h->grid_pass_dense();
   FinalizeTileArgs t{};
   t.g = h->g;
   t.log_odds = h->log_odds;
   t.occupancy = h->occupancy;
   t.occ_i8 = h->occ_i8;
-  t.rects = rects;
-  t.n_rects = n_rects;
+  t.rects = job.rects;
+  t.n_rects = job.n_rects;
   t.hitN = h->fs[p].hitN;
   t.freeN = h->fs[p].freeN;
   t.freeT = h->fs[p].freeT;
   t.nx_pad = h->nx_pad;
   t.ny_pad = h->ny_pad;
-  t.counts = counts;
+  t.counts = job.counts;
   t.dense = dense;
   t.y_begin = y0;
   t.y_end = y1;
 #ifdef GV_DIAG
-  if (of_frame) t.tl = h->tl_slot(3);
+  if (job.of_frame) t.tl = h->tl_slot(3);
 #endif
-  (void)of_frame;
-  const bool ran = launch_finalize_tiles(t, s, done, t0);
-  if (sharded) h->layers_in_step = false;
+  const bool ran = launch_finalize_tiles(t, job.stream, job.done, job.t0);
+  if (job.sharded) h->layers_in_step = false;
   else if (ran && dense && y0 <= 0 && y1 >= h->g.ny) h->layers_in_step = true;
-  if (launched) *launched = ran;
-  if (!ran && done) GV_HIP(hipEventRecord(done, s));
+  job.launched = ran;
+  if (!ran && job.done) GV_HIP(hipEventRecord(job.done, job.stream));
   GV_HIP(hipGetLastError());
   return GV_OK;
 }
@@ -550,10 +555,8 @@ namespace {
 int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
 {
   DetSet &D = h->det[h->det_cur];
-  const uint32_t fl = D.flags;
-  const bool do_bin = fl & GV_FRAME_BIN, do_ray = fl & GV_FRAME_RAYMARCH, do_bbox = fl & GV_FRAME_BBOX_TEST;
-  const bool keep_cell = fl & GV_FRAME_KEEP_CELL_IDX;
-  int rc = check_frame_flags(h, fl);
+  const FrameFlags f = frame_flags(D.flags);
+  int rc = check_frame_flags(h, D.flags);
   if (rc) return rc;
   const int p = pipelined ? 1 + (int)(h->lane_frames % (uint64_t)(2 * h->tune.n_lanes)) : 0;
   const int k = pipelined ? 1 + (int)(h->lane_frames % (uint64_t)h->lanes_now()) : 0;
@@ -581,7 +584,7 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
   // --- detections -> rectangles.  Base-frame poses of a binning frame ride the partition launch (one
   // extra workgroup) instead of a launch of their own; network outputs go through the vision kernels.
   Rect *rects = h->fs[p].rects;
-  const bool fold_rects = do_bin && !(fl & GV_FRAME_VISION_ORIENT) && D.n_poses > 0;
+  const bool fold_rects = f.bin && !f.vision && D.n_poses > 0;
   mark(s);
   if (!fold_rects) h->sb[k].lane_clean = false;   // (the rectangle / vision kernels go on the lane)
   const int32_t n_rects = fold_rects ? D.n_poses : enqueue_rects(h, D, rects, h->sb[k].vout, s);
@@ -594,14 +597,20 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
 
   // --- points: partition by tile (+ ray ends, bbox test), then the tile histogram: hits[] + end bitmaps
   mark(s);
-  if (do_bin) {
-    if ((rc = enqueue_binning(h, D, p, k, 0, h->n, keep_cell, do_ray, do_bbox, true,
-                              stage_events ? h->ev[kStagePoints + 1] : nullptr, fold_rects ? rects : nullptr, stage_events,
-                              part_any_order)))
-      return rc;
+  if (f.bin) {
+    BinningJob bin{D};
+    bin.set = p; bin.stream = k;
+    bin.n = h->n;
+    bin.keep_cell = f.keep_cell; bin.do_ray = f.ray; bin.do_bbox = f.bbox;
+    bin.write_hits = true;
+    bin.fold_rects = fold_rects ? rects : nullptr;
+    bin.ev_points = stage_events ? h->ev[kStagePoints + 1] : nullptr;
+    bin.timed = stage_events;
+    bin.any_order = part_any_order;
+    if ((rc = enqueue_binning(h, bin))) return rc;
   } else {
     h->sb[k].lane_clean = false;
-    if (do_bbox) launch_points(bbox_points_args(h, D, 0, h->n, h->sb[k].bbox_id), s);
+    if (f.bbox) launch_points(bbox_points_args(h, D, 0, h->n, h->sb[k].bbox_id), s);
     if (stage_events) GV_HIP(hipEventRecord(h->ev[kStagePoints + 1], s));
   }
   mark(s);
@@ -610,14 +619,16 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
 
   // --- free-space ray stage.  On a lane its completion event rides the kernel's own dispatch packet.
   const int slot = (int)(h->frame_no % (uint64_t)gv_context::kRing);
-  bool sec_event = false;
+  SectorsJob sec;
+  sec.set = p; sec.stream = s;
+  sec.done = pipelined ? h->ev_sec[slot] : (stage_events ? h->kt[2][1] : nullptr);
+  sec.t0 = stage_events ? h->kt[2][0] : nullptr;
   mark(s);
-  if (do_ray && (rc = enqueue_sectors(h, p, 0, 1, s, pipelined ? h->ev_sec[slot] : (stage_events ? h->kt[2][1] : nullptr), &sec_event,
-                                      stage_events ? h->kt[2][0] : nullptr)))
-    return rc;
+  if (f.ray && (rc = enqueue_sectors(h, sec))) return rc;
+  const bool sec_event = sec.done_attached;
   if (stage_events) h->kt_used[2] = sec_event;
   // the lane now ends in a sector kernel that carries its own completion event: nothing behind it
-  h->sb[k].lane_clean = pipelined && do_bin && do_ray && sec_event;
+  h->sb[k].lane_clean = pipelined && f.bin && f.ray && sec_event;
   mark(s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageRayMarch + 1], s));
 
@@ -631,19 +642,26 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
 
   mark(s);
   // ev_fin[slot] completes with the grid pass: this frame done => every earlier frame done
-  if (stage_events) {   // stage timing: the kernel carries its own start / end events, ev_fin follows as a marker
-    bool ran = false;
-    if ((rc = enqueue_grid_pass(h, p, rects, n_rects, do_bin, 0, h->g.ny, s, h->kt[3][1], h->kt[3][0], &ran))) return rc;
-    h->kt_used[3] = ran;
+  // (stage timing: the kernel carries its own start / end events, ev_fin follows as a marker)
+  GridPassJob grid;
+  grid.set = p; grid.stream = s;
+  grid.rects = rects; grid.n_rects = n_rects;
+  grid.counts = f.bin;
+  grid.y1 = h->g.ny;
+  grid.done = stage_events ? h->kt[3][1] : h->ev_fin[slot];
+  grid.t0 = stage_events ? h->kt[3][0] : nullptr;
+  if ((rc = enqueue_grid_pass(h, grid))) return rc;
+  if (stage_events) {
+    h->kt_used[3] = grid.launched;
     GV_HIP(hipEventRecord(h->ev_fin[slot], s));
-  } else if ((rc = enqueue_grid_pass(h, p, rects, n_rects, do_bin, 0, h->g.ny, s, h->ev_fin[slot]))) return rc;
+  }
   mark(s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageFinalize + 1], s));
   // cloud, detection set and buffer set remember their last user: this frame, which read D on its own stream only
   note_frame_readers(h, slot, p, CS, D, 1u << k, pipelined, true);
   // the tile pass writes every cell of hits[], and the free-cell bitmaps of set p stay until the set's next frame: a
   // BIN frame has both whether or not it kept anything
-  set_last_frame(h, p, k, k, do_bin, do_bin, do_bin && keep_cell, do_bbox);
+  set_last_frame(h, p, k, k, f.bin, f.bin, f.bin && f.keep_cell, f.bbox);
   return GV_OK;
 }
 
@@ -652,10 +670,8 @@ int enqueue_frame_tiles(gv_context *h, bool pipelined, bool stage_events)
 int enqueue_frame_generic(gv_context *h, bool stage_events)
 {
   DetSet &D = h->det[h->det_cur];
-  const uint32_t fl = D.flags;
-  const bool do_bin = fl & GV_FRAME_BIN, do_ray = fl & GV_FRAME_RAYMARCH, do_bbox = fl & GV_FRAME_BBOX_TEST;
-  const bool keep_cell = fl & GV_FRAME_KEEP_CELL_IDX, keep_counts = fl & GV_FRAME_KEEP_COUNTS;
-  int rc = check_frame_flags(h, fl);
+  const FrameFlags f = frame_flags(D.flags);
+  int rc = check_frame_flags(h, D.flags);
   if (rc) return rc;
   if (h->counts_dirty && (rc = clear_counts(h))) return rc;
   hipStream_t s = h->stream;
@@ -665,19 +681,19 @@ int enqueue_frame_generic(gv_context *h, bool stage_events)
   const int32_t n_rects = enqueue_rects(h, D, h->fs[0].rects, h->sb[0].vout, s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageDetections + 1], s));
   int32_t *const hits = h->sb[0].hits;
-  if (do_bin || do_bbox) {
+  if (f.bin || f.bbox) {
     PointsArgs a = bbox_points_args(h, D, 0, h->n, h->sb[0].bbox_id);
     a.m_base = h->m_base;
     a.org = h->org;
     a.hits = hits;
     a.clip_end = h->clip_end;
-    a.cell_idx = keep_cell ? h->sb[0].cell_idx.get() : nullptr;
-    a.do_bin = do_bin; a.do_ray = do_ray; a.do_bbox = do_bbox;
+    a.cell_idx = f.keep_cell ? h->sb[0].cell_idx.get() : nullptr;
+    a.do_bin = f.bin; a.do_ray = f.ray; a.do_bbox = f.bbox;
     a.band = h->band;
     launch_points(a, s);
   }
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStagePoints + 1], s));
-  if (do_ray && h->org.valid) {
+  if (f.ray && h->org.valid) {
     GV_HIP(hipMemsetAsync(h->ray_count, 0, sizeof(uint32_t), s));
     GV_HIP(hipMemsetAsync(h->fs[0].stats, 0, 2 * sizeof(unsigned long long), s));
     h->last.stat_slots = 1;
@@ -689,20 +705,20 @@ int enqueue_frame_generic(gv_context *h, bool stage_events)
     GV_HIP(hipEventRecord(h->ev[kStageRayCompact + 1], s));
     GV_HIP(hipEventRecord(h->ev[kStageRayMarch + 1], s));
   }
-  FinalizeArgs f = finalize_args(h, n_rects);
-  f.hits = do_bin ? hits : nullptr;
-  f.miss = h->miss8;
-  f.clip_end = h->clip_end;
-  f.zero_counts = do_bin && !keep_counts;
-  launch_finalize(f, s);
+  FinalizeArgs fin = finalize_args(h, n_rects);
+  fin.hits = f.bin ? hits : nullptr;
+  fin.miss = h->miss8;
+  fin.clip_end = h->clip_end;
+  fin.zero_counts = f.bin && !f.keep_counts;
+  launch_finalize(fin, s);
   if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageFinalize + 1], s));
   GV_HIP(hipGetLastError());
   const int slot = (int)(h->frame_no % (uint64_t)gv_context::kRing);
   GV_HIP(hipEventRecord(h->ev_fin[slot], s));   // cloud and detection set remember their last reader
   note_frame_readers(h, slot, 0, CS, D, 1u, false, false);   // everything on the public stream
-  h->counts_dirty = do_bin && keep_counts;
+  h->counts_dirty = f.bin && f.keep_counts;
   // the grid pass zeroes the count grids for the next frame unless the caller asked to keep them
-  set_last_frame(h, 0, 0, 0, do_bin && keep_counts, do_bin && keep_counts, do_bin && keep_cell, do_bbox);
+  set_last_frame(h, 0, 0, 0, f.bin && f.keep_counts, f.bin && f.keep_counts, f.bin && f.keep_cell, f.bbox);
   return GV_OK;
 }
 
@@ -830,9 +846,12 @@ int set_detections(gv_context *h, const gv_frame_desc *d)
   h->sb[k].lane_clean = false;   // the upload and the table kernels go on this stream, in front of the frame's partition pass
   if (D.release_slot >= 0 && D.readers != (1u << k)) GV_HIP(hipStreamWaitEvent(s, h->ev_fin[D.release_slot], 0));
   const bool net = vision && d->n_bboxes;
-  if ((rc = upload_det(h, D, d->bboxes, d->n_bboxes, vision ? nullptr : d->poses, vision ? 0 : d->n_poses,
-                       net ? d->orient : nullptr, net ? d->conf : nullptr, net ? d->dims : nullptr, s)))
-    return rc;
+  DetUpload u;
+  u.bboxes = d->bboxes; u.nb = d->n_bboxes;
+  if (!vision) { u.poses = d->poses; u.n_poses = d->n_poses; }
+  if (net) { u.orient = d->orient; u.conf = d->conf; u.dims = d->dims; }
+  u.stream = s;
+  if ((rc = upload_det(h, D, u))) return rc;
   D.flags = d->flags;
   GV_HIP(hipEventRecord(D.ready, s));
   D.seen = 1u << k;

@@ -23,7 +23,7 @@ int refuse_state(gv_context *h, const char *call, const char *missing, unsigned 
   if (missing) why = missing;
   else if ((needs & kNeedCostmap) && !h->infl.have_cost) why = "no costmap (gv_inflate)";
   else if ((needs & kNeedField) && !h->nav.have_field) why = "no distance field (gv_nav_field)";
-  else if (h->world > 1) why = std::string("ranks own row bands of the grid, ") + sharded;
+  else if (h->sh.world > 1) why = std::string("ranks own row bands of the grid, ") + sharded;
   else return GV_OK;
   h->err = std::string(call) + ": " + why;
   return GV_ERR_STATE;

@@ -37,6 +37,18 @@ static int32_t collect_vision_poses(const VisionOut *vo, int32_t n, const gv_tra
   return m;
 }
 
+// boxes and the network's outputs for them, for kernels that read them raw (no bbox-test tables)
+static DetUpload vision_upload(const gv_bbox *bboxes, int32_t nb, const float *orient, const float *conf, const float *dims,
+                               hipStream_t s)
+{
+  DetUpload u;
+  u.bboxes = bboxes; u.nb = nb;
+  u.orient = orient; u.conf = conf; u.dims = dims;
+  u.stream = s;
+  u.masks = false;
+  return u;
+}
+
 int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, const float *dims,
                            const gv_bbox *bboxes, int32_t nb, gv_lshape_pose *poses_out, int32_t *n_out)
 {
@@ -47,7 +59,7 @@ int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, 
   int rc = use_device(h);
   if (rc) return rc;
   DetSet &d = h->det[2];
-  if ((rc = upload_det(h, d, bboxes, nb, nullptr, 0, orient, conf, dims, h->stream, false))) return rc;
+  if ((rc = upload_det(h, d, vision_upload(bboxes, nb, orient, conf, dims, h->stream)))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
   launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, nullptr, h->stream);
   GV_HIP(hipGetLastError());
@@ -69,7 +81,7 @@ int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, con
   int rc = use_device(h);
   if (rc) return rc;
   DetSet &d = h->det[2];
-  if ((rc = upload_det(h, d, bboxes, nb, nullptr, 0, orient, conf, dims, h->stream, false))) return rc;
+  if ((rc = upload_det(h, d, vision_upload(bboxes, nb, orient, conf, dims, h->stream)))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
   DevBuf<float> dsets;   // nb * 64 * (loc0, loc1, loc2, err), then nb winners
   if ((rc = dsets.reserve(h, (size_t)nb * 257))) return rc;
@@ -499,9 +511,14 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   const bool net = vision && nd > 0 && d->n_net == nd;       // poses only when the network ran for every dynamic box
   DetSet &D = h->det[2];
   if (n_all) {
-    if ((rc = upload_det(h, D, cat.data(), 2 * n_all, nullptr, 0, net ? d->orient : nullptr, net ? d->conf : nullptr,
-                         net ? d->dims : nullptr, s, pca, net ? nd : 0, n_all, true)))
-      return rc;
+    DetUpload u;   // [all | static | dynamic] boxes in one block; the bbox test (the PCA branch's) covers the first n_all
+    u.bboxes = cat.data(); u.nb = 2 * n_all;
+    if (net) { u.orient = d->orient; u.conf = d->conf; u.dims = d->dims; }
+    u.stream = s;
+    u.masks = pca;
+    u.n_net = net ? nd : 0; u.nb_test = n_all;
+    u.fused = true;
+    if ((rc = upload_det(h, D, u))) return rc;
     GV_HIP(hipEventRecord(D.ready, s));
   }
   // result block: depths | poses, state, valid (the PCA call's layout) | VisionOut
@@ -557,9 +574,19 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   // --- map update (:145, :206, :230, :235) + int8 pack (:265-278)
   if (lidar && n > 0) {   // [EXTENSION] the fused frame's kernels, serial on the public stream
     if ((rc = ensure_point_buffers(h, n))) return rc;
-    if ((rc = enqueue_binning(h, D, 0, 0, 0, n, false, lidar_ray, false, true, nullptr))) return rc;
-    if (lidar_ray && (rc = enqueue_sectors(h, 0, 0, 1, s))) return rc;
-    if ((rc = enqueue_grid_pass(h, 0, rects, n_rects, true, 0, h->g.ny, s))) return rc;
+    BinningJob bin{D};   // buffer set 0 and the public stream throughout
+    bin.n = n;
+    bin.do_ray = lidar_ray; bin.write_hits = true;
+    if ((rc = enqueue_binning(h, bin))) return rc;
+    SectorsJob sec;
+    sec.stream = s;
+    if (lidar_ray && (rc = enqueue_sectors(h, sec))) return rc;
+    GridPassJob grid;
+    grid.rects = rects; grid.n_rects = n_rects;
+    grid.counts = true;
+    grid.y1 = h->g.ny;
+    grid.stream = s;
+    if ((rc = enqueue_grid_pass(h, grid))) return rc;
     // a tick writes no per-point output: those of the call before it stay where they are
     set_last_frame(h, 0, 0, h->last.points, true, true, h->last.cell_idx, h->last.bbox_id);
   } else if ((rc = enqueue_plain_update(h, n_rects)))

@@ -88,7 +88,6 @@ struct StreamBufs {
   // bit (hipExtAnyOrderLaunch) and starts while the sector kernel's last workgroups still run.  lane_clean:
   // the last packet on this lane is a sector kernel.  GV_ANYORDER=0 switches it off.
   bool lane_clean = false;
-  int sh_counts_slot = -1;      // ev_fin slot of the lane's last sharded KEEP_COUNTS frame (its x3 reduces hits in place)
 };
 
 // What the last frame left behind, for the getters and the standalone calls that go on from it.  Written in one place,
@@ -100,6 +99,76 @@ struct LastFrame {
   int points = 0;               // sb[points].cell_idx / .bbox_id: per-point outputs (a tick writes none: they stay where they were)
   bool hits = false, miss = false, cell_idx = false, bbox_id = false;   // what the getters may read
   size_t stat_slots = 1;        // ray statistics slots written by the last ray stage
+};
+
+// What a frame descriptor's flag word asks for, decoded once (frame_flags): every frame form reads these.
+struct FrameFlags {
+  bool bin, ray, bbox;          // GV_FRAME_BIN / RAYMARCH / BBOX_TEST
+  bool keep_cell, keep_counts;  // GV_FRAME_KEEP_CELL_IDX / KEEP_COUNTS
+  bool vision;                  // GV_FRAME_VISION_ORIENT: rectangles from the network outputs, not from poses
+};
+inline FrameFlags frame_flags(uint32_t fl)
+{
+  return {(fl & GV_FRAME_BIN) != 0,           (fl & GV_FRAME_RAYMARCH) != 0,    (fl & GV_FRAME_BBOX_TEST) != 0,
+          (fl & GV_FRAME_KEEP_CELL_IDX) != 0, (fl & GV_FRAME_KEEP_COUNTS) != 0, (fl & GV_FRAME_VISION_ORIENT) != 0};
+}
+
+// ---- job blocks of the stage calls that the tile frame, the sharded frame, its emulation and the tick share
+// (gv_api_frame.hip).  A caller names what it sets; everything else keeps the default written here.
+
+// enqueue_binning: partition + tile histogram of points [lo, lo + n) of the current cloud
+struct BinningJob {
+  const DetSet &det;                // detection set: bbox-test tables, and the poses of folded rectangles
+  int set = 0;                      // fs[set]: the end bitmaps written, the free-cell bitmaps zeroed
+  int stream = 0;                   // streams[stream] / sb[stream]: hits[], per-point outputs, binning scratch
+  size_t lo = 0, n = 0;             // the points
+  bool keep_cell = false;           // write cell_idx
+  bool do_ray = false;              // clip the ray ends into the end bitmaps
+  bool do_bbox = false;             // bbox test (fused while its tables fit LDS, else a pass of its own)
+  bool write_hits = false;          // the tile pass writes every cell of hits[]
+  Rect *fold_rects = nullptr;       // non-null: det's poses become rectangles there, on the partition launch
+  hipEvent_t ev_points = nullptr;   // recorded between the partition and the tile pass (stage timing)
+  bool timed = false;               // the kernels carry kt[0] / kt[1]
+  bool any_order = false;           // partition launched without the barrier bit (StreamBufs::lane_clean)
+};
+
+// enqueue_sectors: the sector ray stage over the end bitmaps of a set into its free-cell bitmaps
+struct SectorsJob {
+  int set = 0;                      // fs[set]
+  int first = 0, stride = 1;        // workgroups first, first + stride, ... of the dispatch order (a rank's share)
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;        // rides the kernel's dispatch packet when the kernel is launched
+  hipEvent_t t0 = nullptr;          // the kernel's start (stage timing)
+  bool done_attached = false;       // out: a kernel was launched and carries `done`
+};
+
+// enqueue_grid_pass: the tile grid pass over rows [y0, y1) with the bitmaps of a set
+struct GridPassJob {
+  int set = 0;                      // fs[set]
+  const Rect *rects = nullptr;      // index rectangles of the detections
+  int32_t n_rects = 0;
+  bool counts = false;              // apply the hit / miss rule (false: a plain map update)
+  int32_t y0 = 0, y1 = 0;           // rows
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;        // rides the kernel's packet, or is recorded behind a pass that launched nothing
+  hipEvent_t t0 = nullptr;          // the kernel's start (stage timing)
+  bool sharded = false;             // a rank's band: written whole, leaves the layers out of step
+  bool of_frame = true;             // false: a plain update (diagnostic build: the timeline stamps stay with the frames)
+  bool launched = false;            // out: a kernel ran
+};
+
+// upload_det: the caller's arrays into a detection set, in one copy, and the bbox-test tables derived there
+struct DetUpload {
+  const gv_bbox *bboxes = nullptr;
+  int32_t nb = 0;
+  const gv_lshape_pose *poses = nullptr;
+  int32_t n_poses = 0;
+  const float *orient = nullptr, *conf = nullptr, *dims = nullptr;   // network outputs of n_net boxes, or null
+  hipStream_t stream = nullptr;
+  bool masks = true;                // false: only kernels that read the raw boxes / poses follow; no bbox-test tables
+  int32_t n_net = -1;               // boxes the network outputs cover (-1: nb)
+  int32_t nb_test = -1;             // the bbox test covers the first nb_test boxes only (-1: nb)
+  bool fused = false;               // one kernel reads the pinned staging: copy + tables, no copy command
 };
 
 // Experiment and sweep knobs: read from the environment by read_tuning (gv_api.hip), once, at gv_create.
@@ -182,10 +251,26 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // (the streams come before every buffer and event: members go in reverse order, the streams last)
   Stream stream, stream_copy;       // public, uploads
   Stream lane[kLanesMax];           // lane[2] exists only with GV_LANE3_OWN_STREAM
-  Stream stream_x;                  // the exchanges of the sharded frame (created by gv_comm_init)
+  // Multi-GPU: one large frame sharded by points (gv_api_shard.hip).  Here, with the streams, because it owns one: its
+  // buffer and events go before it, and it goes behind every other buffer and event of the handle.
+  struct Shard {
+    ncclComm *comm = nullptr;       // (ncclComm_t)
+    int32_t rank = 0, world = 1;
+    host::ShardPlan plan;           // of this grid and `world`: gv_create (world 1), gv_comm_init, gv_comm_destroy
+    Stream stream_x;                // the exchanges (RCCL) of the sharded frame
+    DevBuf<uint32_t> xchg;          // exchange scratch, plan.scratch_words(): received slices / packed and received bands
+    Event ev[kRing][5];             // per frame slot: binning, exchange 1, sectors + packing, exchange 2, grid pass done
+    Event t[7];                     // stage timing of the sharded frame (gv_time_frame_sharded_stages)
+    // per stream: ev_fin slot of its last sharded KEEP_COUNTS frame in flight (its last exchange reduces hits in place)
+    int counts_slot[kStreams];
+    Shard() { forget_frames(); }
+    bool active() const { return comm != nullptr; }
+    void forget_frames() { for (int &c : counts_slot) c = -1; }   // every frame in flight has finished (drain)
+    int create(gv_context *h);      // the exchange stream and the events, once (gv_comm_init)
+  } sh;
   hipStream_t streams[kStreams]{};  // what the frame code indexes: {stream, lane[0], lane[1], lane[2] or else stream_copy}
   // every stream the handle owns, in the order drain waits for them (null: not created)
-  std::array<hipStream_t, 3 + kLanesMax> own_streams() const { return {stream_copy, stream, lane[0], lane[1], lane[2], stream_x}; }
+  std::array<hipStream_t, 3 + kLanesMax> own_streams() const { return {stream_copy, stream, lane[0], lane[1], lane[2], sh.stream_x}; }
   Event ev_sec[kRing];              // lane: partition, tile pass, sector stage of frame (slot) done
   Event ev_fin[kRing];              // public stream: grid pass of frame (slot) done => that frame and every earlier one are done
   Event ev_join;                    // copy stream -> public stream (gv_frame_fence)
@@ -369,13 +454,6 @@ struct __attribute__((visibility("hidden"))) gv_context {
 
   bool counts_dirty = false;   // generic path: hits/miss/clip_end hold a kept frame
 
-  // multi-GPU (one large frame sharded by points)
-  ncclComm *comm = nullptr;       // (ncclComm_t)
-  int32_t rank = 0, world = 1;
-  DevBuf<uint32_t> sh_xchg;       // exchange scratch: `world` received slices / packed bands
-  Event ev_sh[kRing][5];          // per frame slot: binning, exchange 1, sectors + packing, exchange 2, grid pass done
-  Event sh_t[7];                  // stage timing of the sharded frame (gv_time_frame_sharded_stages)
-
   Event ev[kNumStages + 1];
   // stage timing (gv_time_frame_stages): start / end of the partition, tile-pass, sector and grid-pass kernels,
   // taken from their own dispatch packets; kt_used: the kernel was launched in the frame just timed
@@ -443,23 +521,17 @@ BBoxTest bbox_test_of(const gv_context *h, const DetSet &d);
 PointsArgs bbox_points_args(const gv_context *h, const DetSet &D, size_t lo, size_t n, int16_t *ids);
 void set_last_frame(gv_context *h, int set, int stream, int points, bool hits, bool miss, bool cell_idx, bool bbox_id);
 void note_frame_readers(gv_context *h, int slot, int p, CloudSet &CS, DetSet &D, uint32_t readers, bool on_lane, bool quiet);
-int upload_det(gv_context *h, DetSet &d, const gv_bbox *bboxes, int32_t nb, const gv_lshape_pose *poses,
-               int32_t n_poses, const float *orient, const float *conf, const float *dims, hipStream_t s, bool masks = true,
-               int32_t n_net = -1, int32_t nb_test = -1, bool fused = false);
+int upload_det(gv_context *h, DetSet &d, const DetUpload &u);
 int upload_scratch_bboxes(gv_context *h, const gv_bbox *b, int32_t nb, bool masks = true);
 int32_t enqueue_rects(gv_context *h, const DetSet &D, Rect *rects, VisionOut *vout, hipStream_t s);
 int check_frame_flags(const gv_context *h, uint32_t fl);
-int enqueue_binning(gv_context *h, const DetSet &D, int p, int k, size_t lo, size_t n, bool keep_cell, bool do_ray,
-                    bool do_bbox, bool write_hits, hipEvent_t ev_points, Rect *fold_rects = nullptr, bool timed = false,
-                    bool any_order = false);
-int enqueue_sectors(gv_context *h, int p, int first, int stride, hipStream_t s, hipEvent_t done = nullptr,
-                    bool *done_attached = nullptr, hipEvent_t t0 = nullptr);
-int enqueue_grid_pass(gv_context *h, int p, const Rect *rects, int32_t n_rects, bool counts, int32_t y0, int32_t y1,
-                      hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr, bool *launched = nullptr,
-                      bool sharded = false, bool of_frame = true);
+int enqueue_binning(gv_context *h, const BinningJob &job);
+int enqueue_sectors(gv_context *h, SectorsJob &job);
+int enqueue_grid_pass(gv_context *h, GridPassJob &job);
 int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k);
 // gv_api_shard.hip
 void comm_destroy(gv_context *h);
+host::ShardPlan shard_plan(const gv_context *h, int world);
 // gv_api_planner.hip
 enum : unsigned { kNeedCostmap = 1u, kNeedField = 2u };
 int refuse_state(gv_context *h, const char *call, const char *missing, unsigned needs, const char *sharded);

@@ -426,5 +426,59 @@ inline bool inflation_table(const gv_inflation &c, double res, InflationTable &o
   return true;
 }
 
+// [EXTENSION] SURVEY 8(e)-2 the frame sharded by points over `world` GPUs: who owns which rows of the grid and how large
+// the two exchanges are.  THE band rule: rank q finalises the whole 64-row blocks [blk(q), blk(q + 1)) of the padded grid,
+// blk(q) = q * (ny_pad / 64) / world, clipped to ny.  (Device twin: band_block in gv_shard.hip, which packs by that rule.)
+inline int shard_band_block(int q, int nblk, int world) { return (int)((long long)q * nblk / world); }
+inline void shard_band_rows(int rank, int world, int ny, int ny_pad, int32_t &y0, int32_t &y1)
+{
+  y0 = std::min(ny, 64 * shard_band_block(rank, ny_pad / 64, world));
+  y1 = std::min(ny, 64 * shard_band_block(rank + 1, ny_pad / 64, world));
+}
+
+// words of one of `world` equal slices that cover `words` bitmap words: a multiple of 4 (16-byte vectors)
+inline size_t shard_slice_words(size_t words, int world)
+{
+  return (((words + (size_t)world - 1) / (size_t)world) + 3) & ~(size_t)3;
+}
+
+struct ShardPlan {
+  struct Band {
+    int32_t y0 = 0, y1 = 0;   // rows [y0, y1)
+    size_t b = 0, e = 0;      // cells [b, e) = [y0 * nx, y1 * nx)
+  };
+  int32_t world = 1;
+  int32_t nxw = 0, nx_pad = 0, ny_pad = 0;   // the bitmaps' geometry (the band packing kernels take it)
+  size_t slice = 0;           // exchange 1: words of one rank's slice of the end bitmaps
+  size_t chunk = 0;           // exchange 2: words of one packed free-cell band (the longest one's, a multiple of 4)
+  std::vector<Band> bands;    // per rank
+  // one ncclReduceScatter of cnt0 cells per rank serves the hit counts: every band has cnt0 cells and band r starts at
+  // cell r * cnt0 (otherwise: one ncclReduce per band)
+  bool equal_bands = true;
+  size_t cnt0 = 0;
+
+  ShardPlan() = default;
+  ShardPlan(int32_t nx, int32_t ny, int32_t nx_pad_, int32_t ny_pad_, int32_t nxw_, size_t ends_words, int32_t world_)
+      : world(world_), nxw(nxw_), nx_pad(nx_pad_), ny_pad(ny_pad_), slice(shard_slice_words(ends_words, world_)),
+        bands((size_t)world_)
+  {
+    int32_t rows_max = 0;
+    for (int r = 0; r < world; ++r) {
+      Band &B = bands[(size_t)r];
+      shard_band_rows(r, world, ny, ny_pad, B.y0, B.y1);
+      B.b = (size_t)B.y0 * (size_t)nx;
+      B.e = (size_t)B.y1 * (size_t)nx;
+      if (r == 0) cnt0 = B.e - B.b;
+      equal_bands = equal_bands && B.e - B.b == cnt0 && B.b == (size_t)r * cnt0;
+      // (a packed band holds every row of its blocks, also those of the padding behind ny)
+      rows_max = std::max(rows_max, 64 * (shard_band_block(r + 1, ny_pad / 64, world) - shard_band_block(r, ny_pad / 64, world)));
+    }
+    // (equal bands are never empty: the bands cover [0, ny) and ny >= 1)
+    chunk = ((size_t)nxw * (size_t)rows_max + (size_t)(rows_max / 32) * (size_t)nx_pad + 3) & ~(size_t)3;
+  }
+  // words the exchange scratch holds: `world` received slices, or the packed bands and behind them the received ones
+  size_t scratch_words() const { return std::max(slice * (size_t)world, 2 * chunk * (size_t)world) + 16; }
+};
+
 }  // namespace host
 }  // namespace gv

@@ -278,13 +278,10 @@ void launch_miss_to_i32(const uint32_t *freeN, const uint32_t *freeT, int nx, in
 
 // ---- frame sharded by points over several GPUs: OR-exchange helpers (gv_shard.hip) ----
 void launch_or_slices(const uint32_t *src, uint32_t *dst, size_t count_words, int world, hipStream_t s);
-size_t free_band_chunk_words(int nxw, int nx_pad, int ny_pad, int world);
-void launch_pack_free_bands(const uint32_t *fN, const uint32_t *fT, int nxw, int nx_pad, int ny_pad, int world,
-                            size_t chunk, uint32_t *out, hipStream_t s);
-void launch_unpack_free_band(const uint32_t *in, int world, size_t chunk, int rank, int nxw, int nx_pad, int ny_pad,
-                             uint32_t *fN, uint32_t *fT, hipStream_t s);
-// rows [y0, y1) rank `rank` of `world` finalises: whole 64-row blocks of the padded grid, clipped to ny
-void shard_band_rows(int rank, int world, int ny, int ny_pad, int32_t &y0, int32_t &y1);
+// bands, chunk size and bitmap geometry come from the plan (host::ShardPlan, gv_host_math.hpp)
+namespace host { struct ShardPlan; }
+void launch_pack_free_bands(const uint32_t *fN, const uint32_t *fT, const host::ShardPlan &P, uint32_t *out, hipStream_t s);
+void launch_unpack_free_band(const uint32_t *in, const host::ShardPlan &P, int rank, uint32_t *fN, uint32_t *fT, hipStream_t s);
 
 // ---- kNN depth + radius outlier counts (gv_knn_pca.hip) ----
 struct Cand2 {

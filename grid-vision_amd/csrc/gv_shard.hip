@@ -7,6 +7,8 @@
 
 #include <algorithm>
 
+#include "gv_host_math.hpp"
+
 namespace gv {
 
 // dst[i] = OR over r of src[r * count + i]      (count words, 16-byte vectors)
@@ -36,6 +38,7 @@ void launch_or_slices(const uint32_t *src, uint32_t *dst, size_t count_words, in
 // Row band q of the free-cell bitmaps, packed for peer q.  Bands are whole 64-row blocks of the padded
 // grid: rows [64*blk(q), 64*blk(q+1)), blk(q) = q * (ny_pad/64) / world.  Chunk q of `out` (chunk words
 // each) holds   [wc][y - y0] words of freeN   then   [wr - y0/32][x] words of freeT.
+// (Host twin of the rule: host::shard_band_block, gv_host_math.hpp; host::ShardPlan sizes `chunk` by it.)
 __device__ __forceinline__ int band_block(int q, int nblk, int world) { return (int)((long long)q * nblk / world); }
 
 __global__ void __launch_bounds__(256) k_pack_free_bands(const uint32_t *__restrict__ fN, const uint32_t *__restrict__ fT,
@@ -61,11 +64,10 @@ __global__ void __launch_bounds__(256) k_pack_free_bands(const uint32_t *__restr
   }
 }
 
-void launch_pack_free_bands(const uint32_t *fN, const uint32_t *fT, int nxw, int nx_pad, int ny_pad, int world,
-                            size_t chunk, uint32_t *out, hipStream_t s)
+void launch_pack_free_bands(const uint32_t *fN, const uint32_t *fT, const host::ShardPlan &P, uint32_t *out, hipStream_t s)
 {
-  const uint32_t bx = (uint32_t)std::min<size_t>((chunk + 255) / 256, (size_t)512);
-  hipLaunchKernelGGL(k_pack_free_bands, dim3(bx, world), dim3(256), 0, s, fN, fT, nxw, nx_pad, ny_pad, world, chunk, out);
+  const uint32_t bx = (uint32_t)std::min<size_t>((P.chunk + 255) / 256, (size_t)512);
+  hipLaunchKernelGGL(k_pack_free_bands, dim3(bx, P.world), dim3(256), 0, s, fN, fT, P.nxw, P.nx_pad, P.ny_pad, P.world, P.chunk, out);
 }
 
 // OR of the `world` chunks received for MY band, written back into the bitmap layout at the band's rows
@@ -90,30 +92,10 @@ __global__ void __launch_bounds__(256) k_unpack_free_band(const uint32_t *__rest
   }
 }
 
-void launch_unpack_free_band(const uint32_t *in, int world, size_t chunk, int rank, int nxw, int nx_pad, int ny_pad,
-                             uint32_t *fN, uint32_t *fT, hipStream_t s)
+void launch_unpack_free_band(const uint32_t *in, const host::ShardPlan &P, int rank, uint32_t *fN, uint32_t *fT, hipStream_t s)
 {
-  const uint32_t bx = (uint32_t)std::min<size_t>((chunk + 255) / 256, (size_t)1024);
-  hipLaunchKernelGGL(k_unpack_free_band, dim3(bx), dim3(256), 0, s, in, world, chunk, rank, nxw, nx_pad, ny_pad, fN, fT);
-}
-
-size_t free_band_chunk_words(int nxw, int nx_pad, int ny_pad, int world)
-{
-  const int nblk = ny_pad / 64;
-  int rows_max = 0;
-  for (int q = 0; q < world; ++q) {
-    const int r = 64 * ((int)((long long)(q + 1) * nblk / world) - (int)((long long)q * nblk / world));
-    rows_max = std::max(rows_max, r);
-  }
-  const size_t c = (size_t)nxw * rows_max + (size_t)(rows_max / 32) * nx_pad;
-  return (c + 3) & ~(size_t)3;
-}
-
-void shard_band_rows(int rank, int world, int ny, int ny_pad, int32_t &y0, int32_t &y1)
-{
-  const int nblk = ny_pad / 64;
-  y0 = std::min(ny, 64 * (int)((long long)rank * nblk / world));
-  y1 = std::min(ny, 64 * (int)((long long)(rank + 1) * nblk / world));
+  const uint32_t bx = (uint32_t)std::min<size_t>((P.chunk + 255) / 256, (size_t)1024);
+  hipLaunchKernelGGL(k_unpack_free_band, dim3(bx), dim3(256), 0, s, in, P.world, P.chunk, rank, P.nxw, P.nx_pad, P.ny_pad, fN, fT);
 }
 
 }  // namespace gv

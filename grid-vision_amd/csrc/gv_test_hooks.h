@@ -27,6 +27,13 @@ int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, con
 int gv_test_bbox_pose_nodes(gv_handle h, const gv_bbox *bboxes, int32_t nb, int32_t with_ground, gv_lshape_pose *poses_out,
                             uint8_t *valid, int32_t *n_poses_or_fail, float *nodes /* n*4 */, uint8_t *keep /* n */,
                             int64_t *n_sel);
+/* Host only, no handle and no device: the plan of the sharded frame (host::ShardPlan, csrc/gv_host_math.hpp) that a handle
+ * over an nx x ny grid keeps for a communicator of `world` ranks: words of one end-bitmap slice and of one packed free-cell
+ * band, whether one ncclReduceScatter of *cnt0 cells per rank serves the hit counts (else one ncclReduce per band: the
+ * choice no one-GPU run can take), and rows[2 * r], rows[2 * r + 1] = band [y0, y1) of rank r
+ * (tests/test_oracle_properties.py). */
+int gv_test_shard_plan(int32_t nx, int32_t ny, int32_t world, int64_t *slice, int64_t *chunk, int32_t *equal_bands,
+                       int64_t *cnt0, int32_t *rows /* 2 * world */);
 #ifdef __cplusplus
 }
 #endif

@@ -272,6 +272,19 @@ def shard_band_rows(rank, world, ny):
     return y0.value, y1.value
 
 
+def shard_plan(nx, ny, world):
+    """test hook (csrc/gv_test_hooks.h): the sharded frame's plan for an nx x ny grid and `world` ranks, as a dict of
+    slice, chunk (words), equal_bands, cnt0 (cells) and rows = [(y0, y1)] per rank (host only; needs no GPU)"""
+    sl, ch, cnt0, eq = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+    rows = np.zeros(2 * world, np.int32)
+    rc = load().gv_test_shard_plan(C.c_int32(nx), C.c_int32(ny), C.c_int32(world), C.byref(sl), C.byref(ch), C.byref(eq),
+                                   C.byref(cnt0), _ptr(rows))
+    if rc:
+        raise GVError(rc, "gv_test_shard_plan")
+    return dict(slice=sl.value, chunk=ch.value, equal_bands=bool(eq.value), cnt0=cnt0.value,
+                rows=[(int(rows[2 * r]), int(rows[2 * r + 1])) for r in range(world)])
+
+
 def inflation_cost_table(cfg, resolution):
     """the uint8 cost table (d2max + 1 entries) an Inflation gives at `resolution` (host only; needs no GPU)"""
     table = np.zeros(4096, np.uint8)

@@ -4,8 +4,8 @@ buffers of the call that made it valid.
 Every frame form ends by recording what it left behind (gv_context::LastFrame): the buffer set, the stream whose count
 grid and per-point outputs it wrote, and which of the four outputs exist.  The forms differ on purpose -- the generic
 frame keeps its counts only with KEEP_COUNTS, the sharded frame's emulation has no whole count grid and no whole miss
-grid, the tick writes no per-point output and leaves those of the call before it alone -- and the standalone calls
-change single flags.  The tables below pin that step by step on one handle, so that every step starts from the
+grid, the sharded frame itself keeps its band's count totals only with KEEP_COUNTS and never a miss grid, the tick
+writes no per-point output and leaves those of the call before it alone -- and the standalone calls change single flags.  The tables below pin that step by step on one handle, so that every step starts from the
 history of the steps before it; a getter that is not valid raises GV_ERR_STATE (5), ray_stats() never raises.  The
 values behind a valid getter are held to a fresh handle that ran only the step in question: after a history of other
 calls the last frame ran on another lane and another buffer set than the fresh handle's."""
@@ -162,6 +162,32 @@ def test_three_pipelined_frames(gvamd):
         h.synchronize()
         _expect(gv, h, ("hits", "miss"), "three enqueue_frame(BIN|RAYMARCH) + synchronize")
         _same(_arrays(h, ("hits", "miss")), _fresh(gv, "tile_three"), "three pipelined frames after a history")
+
+
+def test_sharded_frame_one_rank_step_by_step(gvamd):
+    """The product's sharded frame on a real one-rank communicator: its tile pass writes hits[] only with KEEP_COUNTS
+    (one band, a one-rank reduce: the totals are the plain frame's), its free-cell bitmaps are a band's, so miss() is
+    never valid after it; the per-point outputs are the plain frame's.  Leaving the communicator gives the plain frame
+    back."""
+    gv = gvamd
+    cloud, boxes = _inputs(TILE_GRID)
+    rm = gv.FRAME_BIN | gv.FRAME_RAYMARCH
+    fresh = _fresh(gv, "tile_all")
+    with _handle(gv, TILE_GRID, cloud) as h:
+        h.comm_init(gv.GridVisionHIP.comm_unique_id(), 0, 1)
+        h.process_frame_sharded(rm)
+        _expect(gv, h, (), "process_frame_sharded(BIN|RAYMARCH)")
+        h.process_frame_sharded(rm | gv.FRAME_KEEP_COUNTS)
+        _expect(gv, h, ("hits",), "process_frame_sharded(BIN|RAYMARCH|KEEP_COUNTS)")
+        _same(_arrays(h, ("hits",)), {"hits": fresh["hits"]}, "sharded KEEP_COUNTS frame")
+        h.process_frame_sharded(rm | gv.FRAME_KEEP_COUNTS | gv.FRAME_KEEP_CELL_IDX | gv.FRAME_BBOX_TEST, bboxes=boxes)
+        names = ("hits", "cell_idx", "bbox_id")
+        _expect(gv, h, names, "process_frame_sharded(BIN|RAYMARCH|KEEP_COUNTS|KEEP_CELL_IDX|BBOX_TEST)")
+        _same(_arrays(h, names), {n: fresh[n] for n in names}, "sharded frame that keeps everything it can")
+        h.comm_destroy()
+        h.process_frame(rm | gv.FRAME_KEEP_CELL_IDX | gv.FRAME_BBOX_TEST, bboxes=boxes)
+        _expect(gv, h, ALL, "comm_destroy, then the all-four frame")
+        _same(_arrays(h), fresh, "all four after the communicator is gone")
 
 
 def test_serial_tile_path(gvamd, monkeypatch):

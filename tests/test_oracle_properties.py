@@ -294,6 +294,40 @@ def test_shard_band_and_slice_helpers_partition_the_grid():
             assert sl % 4 == 0 and sl * world >= words and (sl - 4) * world < max(words, 1) + 4 * world
 
 
+def test_shard_plan_at_its_edges():
+    """host::ShardPlan through gv_test_shard_plan (host only): what the sharded frame sizes its exchanges by and, with more
+    than one rank, chooses its hit-count reduction by -- one ncclReduceScatter when the bands are equal, one ncclReduce per
+    band otherwise.  No one-GPU run takes that branch; this is its only check.  The expected values are stated here from
+    the rule itself: bands are the whole 64-row blocks [blk(q), blk(q + 1)) of the grid padded to 128 rows,
+    blk(q) = q * (ny_pad / 64) // world, clipped to ny; a packed band holds every row of its blocks."""
+    import gvamd
+    seen = set()
+    for ny in (1, 63, 64, 65, 200, 800, 1000, 2000, 4000, 8000):
+        for nx in (4, 100, 2000):
+            nx_pad, ny_pad = -(-nx // 128) * 128, -(-ny // 128) * 128
+            nxw = nx_pad // 32
+            ends_words = 2 * (ny_pad * nxw + nx_pad * (ny_pad // 32))   # hit + clip bitmaps, along x and transposed
+            for world in (1, 2, 3, 5, 8, 16):
+                p = gvamd.shard_plan(nx, ny, world)
+                what = f"nx {nx} ny {ny} world {world}"
+                assert p["rows"] == [gvamd.shard_band_rows(r, world, ny) for r in range(world)], what
+                blk = [q * (ny_pad // 64) // world for q in range(world + 1)]
+                packed = [nxw * rows + (rows // 32) * nx_pad for rows in (64 * (blk[q + 1] - blk[q]) for q in range(world))]
+                assert p["chunk"] % 4 == 0 and p["chunk"] == (max(packed) + 3) // 4 * 4, what
+                for y0, y1 in p["rows"]:   # ... which is at least what any band's own rows need
+                    assert p["chunk"] >= nxw * (y1 - y0) + ((y1 - y0) // 32) * nx_pad, what
+                assert p["slice"] == gvamd.shard_slice_words(ends_words, world), what
+                cells = [(y0 * nx, y1 * nx) for y0, y1 in p["rows"]]
+                cnt0 = cells[0][1] - cells[0][0]
+                equal = all(e - b == cnt0 and b == r * cnt0 for r, (b, e) in enumerate(cells))
+                assert p["equal_bands"] == equal and p["cnt0"] == cnt0, what
+                assert not equal or cnt0 > 0, what   # the reduce-scatter never moves zero cells
+                if world == 1:
+                    assert equal, what
+                seen.add(equal)
+    assert seen == {True, False}, "the sweep takes one branch only"
+
+
 def test_oracle_reproduces_pca_fixture():
     """tests/golden/pca_small.npz (made by tests/golden/make_pca_fixture.py from the oracle): kNN depths, the RANSAC
     ground plane and the PCA poses of a small seeded scene.  Freezes the oracle's arithmetic on the reference's other

@@ -7,6 +7,10 @@ host and device poses and pinned and pageable destinations.
 python3 tools/api_order.py pose  runs the pose family on a fresh handle: kNN depth, poses of 1 and of 300 boxes (the second
 regrows the result block), the ground plane with and without its mask, the ground-removed pose with and without boxes,
 the vision post-process, a vision tick, a PCA tick with static and dynamic boxes, kNN depth again.
+python3 tools/api_order.py shard  runs the sharded frame on a fresh handle with a one-rank communicator (it sets
+GV_QUEUE_PROBE=0 itself): process_frame_sharded plain, with KEEP_COUNTS, and with everything it can keep plus boxes and
+poses; six frames in flight; the stage timing; the three-rank emulation; comm_destroy and one plain frame.  RCCL's own HIP
+calls are in both builds' traces alike.
 python3 tools/api_order.py compare a_hip_api_trace.csv b_hip_api_trace.csv [--no-alloc] [--no-query]  prints the first
 differences; --no-alloc leaves hipMalloc and hipFree out of both lists (a change of who owns which buffer moves only
 those), --no-query hipStreamQuery (the result block's wait asks the stream once per 4096 spins: how often is timing)."""
@@ -120,6 +124,41 @@ def run_pose():
     h.close()
 
 
+def run_shard():
+    os.environ["GV_QUEUE_PROBE"] = "0"
+    sys.path.insert(0, os.path.join(ROOT, "grid-vision_amd"))
+    import gvamd
+    from gvamd import synth
+    g = synth.CONFIGS[1]["grid"]
+    tfs = synth.transforms(True)
+    x, y, z, _ = synth.cloud_uniform(1)
+    bb, pp = synth.detections(3, 8), synth.lshape_poses(1, 8)
+    rm = gvamd.FRAME_BIN | gvamd.FRAME_RAYMARCH
+    keep_all = rm | gvamd.FRAME_KEEP_COUNTS | gvamd.FRAME_KEEP_CELL_IDX | gvamd.FRAME_BBOX_TEST
+    h = gvamd.GridVisionHIP(g.grid_x, g.grid_y, g.resolution)
+    h.set_transforms(tfs["cam_lidar"], tfs["base_cam"], tfs["base_lidar"])
+
+    def six_in_flight():
+        for _ in range(6):
+            h.enqueue_frame_sharded()
+
+    steps = [lambda: h.upload_xyz(x, y, z),
+             lambda: h.comm_init(gvamd.GridVisionHIP.comm_unique_id(), 0, 1),
+             lambda: h.process_frame_sharded(rm),
+             lambda: h.process_frame_sharded(rm | gvamd.FRAME_KEEP_COUNTS),
+             lambda: h.process_frame_sharded(keep_all, bboxes=bb, poses=pp),
+             six_in_flight,
+             lambda: h.time_frame_sharded_stages(2),
+             lambda: h.frame_sharded_emulated(3, keep_all, bboxes=bb, poses=pp),
+             h.comm_destroy,
+             lambda: h.process_frame(keep_all, bboxes=bb, poses=pp)]
+    for step in steps:
+        h.synchronize()
+        step()
+    h.synchronize()
+    h.close()
+
+
 def names(path, skip=()):
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
@@ -138,5 +177,7 @@ if __name__ == "__main__":
         run_planner()
     elif sys.argv[1:] == ["pose"]:
         run_pose()
+    elif sys.argv[1:] == ["shard"]:
+        run_shard()
     else:
         run()
