@@ -198,25 +198,25 @@ void read_tuning(Tuning &t)
   const char *impl = std::getenv("GV_RAY_IMPL");
   t.force_simple = impl && std::strcmp(impl, "simple") == 0;
   if (num("GV_PIPELINE", v)) t.no_pipeline = v == 0;
-  num("GV_LOG2S", t.log2s);
+  num("GV_LOG2S", t.sec.log2s);
   if (const char *e = std::getenv("GV_LOG2S_OCT")) {
     int k = 0;
     for (const char *q = e; *q && k < 8; ++k) {
-      t.log2s_oct[k] = std::atoi(q);
+      t.sec.log2s_oct[k] = std::atoi(q);
       while (*q && *q != ',') ++q;
       if (*q == ',') ++q;
     }
   }
-  if (num("GV_SECTOR_REORDER", v)) t.reorder = v != 0;
-  if (num("GV_SECTOR_HELPERS", v)) t.helpers = v != 0;
+  if (num("GV_SECTOR_REORDER", v)) t.sec.reorder = v != 0;
+  if (num("GV_SECTOR_HELPERS", v)) t.sec.helpers = v != 0;
   if (num("GV_ANYORDER", v)) t.anyorder = v != 0;
   if (num("GV_GRID_SKIP", v)) t.grid_skip = v != 0;
-  num("GV_CAP", t.cap);
-  if (num("GV_FLAT_K", v)) t.flat_k = std::max(0, v);
-  if (num("GV_FLAT_DIRECT", v)) t.flat_direct = (uint32_t)std::max(0, v);
-  if (num("GV_MARCH_LIMIT", v)) t.march_limit = (uint32_t)std::max(0, v);
-  if (num("GV_LOG2M", v)) t.log2m = std::min(9, std::max(4, v));
-  num("GV_SECTOR_REV", t.sector_rev);
+  num("GV_CAP", t.sec.cap);
+  if (num("GV_FLAT_K", v)) t.sec.flat_k = std::max(0, v);
+  if (num("GV_FLAT_DIRECT", v)) t.sec.flat_direct = (uint32_t)std::max(0, v);
+  if (num("GV_MARCH_LIMIT", v)) t.sec.march_limit = (uint32_t)std::max(0, v);
+  if (num("GV_LOG2M", v)) t.sec.log2m = std::min(9, std::max(4, v));
+  num("GV_SECTOR_REV", t.sec.sector_rev);
   if (num("GV_NAV_PASS_CAP", v)) t.nav_pass_cap = std::max(1, v);
 #ifdef GV_DIAG
   num("GV_ABLATE", t.ablate);
@@ -650,6 +650,33 @@ int gv_test_shard_plan(int32_t nx, int32_t ny, int32_t world, int64_t *slice, in
     for (int r = 0; r < world; ++r) { rows[2 * r] = P.bands[(size_t)r].y0; rows[2 * r + 1] = P.bands[(size_t)r].y1; }
   } catch (...) {
     return GV_ERR_HIP;
+  }
+  return GV_OK;
+}
+
+// test hook (gv_test_hooks.h): the sector plan enqueue_sectors builds for this grid, origin cell and cloud size
+int gv_test_sector_plan(int32_t nx, int32_t ny, int32_t cx, int32_t cy, int64_t n_points, gv_test_sector_plan_t *plan,
+                        int32_t *wg, int64_t wg_cap)
+{
+  if (nx < 1 || ny < 1 || cx < 0 || cx >= nx || cy < 0 || cy >= ny || n_points < 0 || !plan || wg_cap < 0 || (wg_cap && !wg))
+    return GV_ERR_BAD_ARG;
+  Tuning t;
+  read_tuning(t);
+  const host::SectorPlan P(nx, ny, cx, cy, (size_t)n_points, t.sec);
+  gv_test_sector_plan_t &out = *plan;
+  out = gv_test_sector_plan_t{};
+  for (int o = 0; o < 8; ++o) { out.len[o] = P.len[o]; out.log2s_oct[o] = P.log2s_oct[o]; out.rev_oct[o] = P.rev_oct[o]; }
+  for (int k = 0; k < 9; ++k) out.wg_base[k] = P.wg_base[k];
+  out.imax = P.imax; out.cap = P.cap; out.log2m = P.log2m; out.marks_words = P.marks_words;
+  out.oct_perm = P.oct_perm; out.reorder = P.reorder; out.n_helpers = P.n_helpers;
+  out.flat_k = P.flat_k; out.march_limit = P.march_limit; out.flat_direct = P.flat_direct;
+  out.ch = P.ch; out.lds_bytes = (int64_t)P.lds_bytes;
+  out.total_workgroups = P.total_workgroups; out.stat_slots = (int64_t)P.stat_slots;
+  out.violations = P.violations();
+  for (int64_t b = 0; b < std::min<int64_t>(wg_cap, P.total_workgroups); ++b) {
+    const host::SectorPlan::Workgroup w = P.workgroup((int)b);
+    const int32_t row[7] = {w.octant, w.sector, w.helper, w.part, w.nparts, w.stat_slot, w.idle};
+    std::memcpy(wg + 7 * b, row, sizeof(row));
   }
   return GV_OK;
 }

@@ -46,68 +46,22 @@ int clear_counts(gv_context *h)
   return GV_OK;
 }
 
-// sector-kernel launch parameters for the resident cloud and grid, buffer set p
-int fill_sector_args(gv_context *h, SectorArgs &sa, int p)
+// sector-kernel arguments: the plan's fields beside the pointers and geometry of buffer set p
+void fill_sector_args(const gv_context *h, const host::SectorPlan &P, SectorArgs &sa, int p)
 {
   sa.g = h->g;
   sa.org = h->org;
-  const int imax = std::max(std::max(h->org.cx, h->g.nx - 1 - h->org.cx), std::max(h->org.cy, h->g.ny - 1 - h->org.cy));
-  // octant o: xmaj = bit 2, smaj = bit 1; wedge length = distance to the map edge along the major axis
-  int len[8], ord[8];
-  for (int o = 0; o < 8; ++o) {
-    const bool xmaj = (o >> 2) & 1, pos = (o >> 1) & 1;
-    len[o] = xmaj ? (pos ? h->g.nx - 1 - h->org.cx : h->org.cx) : (pos ? h->g.ny - 1 - h->org.cy : h->org.cy);
-    ord[o] = o;
-  }
-  // Sectors per octant: the far end of a wedge about 16 cells wide (len <= 16*S; the kernel needs
-  // <= 32) and an estimated <= 12000 ends per sector (the estimate runs ~2x high; above one LDS chunk
-  // of 4096 ends a wedge is processed in row groups, which measured better on config 5 -- 10 M points,
-  // 160 vs 390 us -- than four times as many, thinner wedges).  Measured on
-  // config 3 (tools/sweep_oct.sh, tools/sweep_sectors.sh): the kernel is bound by per-workgroup
-  // latency chains, so fewer, fatter wedges win as long as those two hold, and an octant whose wedge
-  // is short (origin near that map edge) gets proportionally fewer sectors: 128/64/32 sectors for
-  // wedges of 1660/1000/340 columns instead of 128 everywhere does the same frame in 576 instead of
-  // 1024 workgroups, 84 -> 76 us pipelined.  Wider wedges (S = 16 for 340 columns) lose again.
-  const double dens = std::min((double)h->n, (double)h->g.G) / (double)h->g.G;
-  double est_max = 0.0;
-  for (int o = 0; o < 8; ++o) {
-    int l2 = 3;   // the gap-sector logic wants S >= 8
-    while ((16 << l2) < len[o]) ++l2;
-    double est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2);
-    while (est > 12000.0 && l2 < 12) {
-      ++l2;
-      est *= 0.5;
-    }
-    if (h->tune.log2s > 0) { l2 = h->tune.log2s; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
-    if (h->tune.log2s_oct[o] > 0) { l2 = h->tune.log2s_oct[o]; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
-    sa.log2s_oct[o] = (uint8_t)l2;
-    est_max = std::max(est_max, est);
-  }
-  // Rows of 512 columns, 8 blocks of 64 each, one block per wavefront: a row goes to the wavefronts in ascending or in
-  // descending order, whichever keeps the fullest wavefront lightest (far columns are wider: weight ~ column number),
-  // rows taken from the heaviest (last) one down.  GV_SECTOR_REV=0 / 1: never / always alternate (experiments).
-  for (int o = 0; o < 8; ++o) {
-    const int rows = (len[o] + 511) / 512;
-    double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint16_t mask = 0;
-    const double wbase = (double)(1 << sa.log2s_oct[o]);   // a column's cost: its cells (a / S + 1), times S
-    for (int r = std::min(rows, 16) - 1; r >= 0; --r) {
-      double w[8];
-      for (int b = 0; b < 8; ++b) {
-        const int a0 = 512 * r + 64 * b + 1, a1 = std::min(a0 + 63, len[o]);
-        w[b] = a1 >= a0 ? (double)(a1 - a0 + 1) * (0.5 * (double)(a0 + a1) + wbase) : 0.0;
-      }
-      double up = 0.0, down = 0.0;
-      for (int b = 0; b < 8; ++b) { up = std::max(up, load[b] + w[b]); down = std::max(down, load[b] + w[7 - b]); }
-      bool rev = down < up;
-      if (h->tune.sector_rev == 0) rev = false;
-      if (h->tune.sector_rev == 1) rev = (r & 1) != 0;
-      if (rev) mask |= (uint16_t)(1u << r);
-      for (int b = 0; b < 8; ++b) load[b] += rev ? w[7 - b] : w[b];
-    }
-    sa.rev_oct[o] = mask;
-  }
-  sa.cap = h->tune.cap > 0 ? std::max(2048, h->tune.cap) : ((est_max <= 1700.0 && h->tune.log2s <= 0) ? 2048 : 4096);
+  for (int o = 0; o < 8; ++o) { sa.log2s_oct[o] = P.log2s_oct[o]; sa.rev_oct[o] = P.rev_oct[o]; }
+  for (int k = 0; k < 9; ++k) sa.wg_base[k] = (uint16_t)P.wg_base[k];
+  sa.cap = P.cap;
+  sa.log2m = P.log2m;
+  sa.marks_words = P.marks_words;
+  sa.oct_perm = P.oct_perm;
+  sa.reorder = P.reorder;
+  sa.n_helpers = P.n_helpers;
+  sa.flat_k = P.flat_k;
+  sa.march_limit = P.march_limit;
+  sa.flat_direct = P.flat_direct;
   sa.ablate = 0;
   sa.dbg = nullptr;
 #ifdef GV_DIAG
@@ -115,34 +69,11 @@ int fill_sector_args(gv_context *h, SectorArgs &sa, int p)
   sa.dbg = h->d_dbg;
   sa.tl = h->tl_slot(2);
 #endif
-  sa.flat_k = h->tune.flat_k;
-  sa.march_limit = h->tune.march_limit;
-  sa.flat_direct = h->tune.flat_direct;
-  sa.log2m = h->tune.log2m > 0 ? h->tune.log2m : 9;
-  sa.marks_words = (imax + 3) & ~1;   // one word per wedge column, 0..imax
-  std::stable_sort(ord, ord + 8, [&](int a, int b) { return len[a] > len[b]; });
-  sa.oct_perm = 0;
-  sa.reorder = h->tune.reorder;
-  uint32_t base = 0;
-  for (int k = 0; k < 8; ++k) {
-    sa.oct_perm |= (uint32_t)ord[k] << (3 * k);
-    sa.wg_base[k] = (uint16_t)base;
-    base += 1u << sa.log2s_oct[sa.reorder ? ord[k] : k];
-  }
-  // second workgroups for the axis / diagonal sectors of every octant once the wedges are long enough to have
-  // heavy tails (GV_SECTOR_HELPERS=0 / 1 forces them off / on)
-  sa.n_helpers = (h->tune.helpers >= 0) ? (h->tune.helpers ? 16 : 0) : (imax >= 512 ? 16 : 0);
-  if (base + 16 > kMaxStatSlots || base > 65535u) { h->err = "too many sector workgroups"; return GV_ERR_BAD_ARG; }
-  sa.wg_base[8] = (uint16_t)base;
   sa.hitN = h->fs[p].hitN; sa.clipN = h->fs[p].clipN; sa.hitT = h->fs[p].hitT; sa.clipT = h->fs[p].clipT;
   sa.nxw = h->nxw; sa.nyw = h->nyw; sa.nx_pad = h->nx_pad; sa.ny_pad = h->ny_pad;
   sa.freeN = h->fs[p].freeN;
   sa.freeT = h->fs[p].freeT;
   sa.stats = h->fs[p].stats;
-  sa.wg_first = 0;
-  sa.wg_stride = 1;
-  h->last.stat_slots = (size_t)sa.wg_base[8] + (size_t)sa.n_helpers;
-  return GV_OK;
 }
 
 }  // namespace
@@ -479,12 +410,14 @@ int enqueue_sectors(gv_context *h, SectorsJob &job)
 {
   job.done_attached = false;
   if (!h->org.valid) return GV_OK;
+  const host::SectorPlan P(h->g.nx, h->g.ny, h->org.cx, h->org.cy, h->n, h->tune.sec);
+  if (const uint32_t v = P.violations()) { h->err = host::SectorPlan::violation_name(v); return GV_ERR_BAD_ARG; }
   SectorArgs sa{};
-  int rc = fill_sector_args(h, sa, job.set);
-  if (rc) return rc;
+  fill_sector_args(h, P, sa, job.set);
   sa.wg_first = job.first;
   sa.wg_stride = job.stride;
-  const bool launched = launch_ray_sectors(sa, job.stream, job.done, job.t0);
+  h->last.stat_slots = P.stat_slots;
+  const bool launched = launch_ray_sectors(sa, {P.ch, P.lds_bytes, (int)P.total_workgroups}, job.stream, job.done, job.t0);
   job.done_attached = launched && job.done;
   GV_HIP(hipGetLastError());
   return GV_OK;

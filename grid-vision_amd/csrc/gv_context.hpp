@@ -182,15 +182,8 @@ struct Tuning {
   bool tick_knn_lane = true;        // GV_TICK_KNN_LANE=0: the static boxes' kNN in line on the public stream
   bool grid_skip = true;            // GV_GRID_SKIP=0: every grid pass dense (A/B runs, tests)
   bool anyorder = true;             // GV_ANYORDER=0: no any-order partition launches (StreamBufs::lane_clean)
-  int reorder = 1;                  // GV_SECTOR_REORDER=0: workgroups in natural (octant, sector) order
-  int helpers = -1;                 // GV_SECTOR_HELPERS: -1 automatic, 0 off, 1 on
-  int32_t sector_rev = -1;          // GV_SECTOR_REV (sweeps)
+  host::SectorTuning sec;           // the sector ray stage's knobs: what host::SectorPlan reads (gv_host_math.hpp)
   int32_t nav_pass_cap = kNavPassCap;   // GV_NAV_PASS_CAP: passes of a tile per round of gv_nav_field (tests: the cap's own path)
-  int32_t log2s_oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // GV_LOG2S_OCT="a,b,..." per octant index (sweeps)
-  uint32_t march_limit = 64u * 512u;   // GV_MARCH_LIMIT
-  uint32_t flat_direct = 2048;         // GV_FLAT_DIRECT
-  int32_t flat_k = 8;               // GV_FLAT_K: exact-cell : marched-cell cost ratio (0 = always march)
-  int32_t log2s = 0, cap = 0, log2m = 0;   // GV_LOG2S / GV_CAP / GV_LOG2M (sweeps)
 #ifdef GV_DIAG
   int32_t ablate = 0;               // GV_ABLATE
   bool bin_dbg = false, timeline = false, sector_dbg = false;   // GV_BIN_DBG / GV_TIMELINE / GV_SECTOR_DBG = 1: the stamp buffers exist
@@ -462,7 +455,7 @@ struct __attribute__((visibility("hidden"))) gv_context {
   std::string err;
 };
 
-constexpr size_t kMaxStatSlots = 8u << 12;   // one (rays, visits) slot per sector workgroup
+using host::kMaxStatSlots;
 
 #define GV_HIP(call)                                                                          \
   do {                                                                                        \

@@ -480,5 +480,194 @@ struct ShardPlan {
   size_t scratch_words() const { return std::max(slice * (size_t)world, 2 * chunk * (size_t)world) + 16; }
 };
 
+// [EXTENSION] X2 the sector ray stage (k_ray_sectors, gv_raysector.hip): how the eight wedges around the origin cell are
+// cut into workgroups.  Built per frame from the grid, the origin cell and the cloud's size; the launcher and the
+// argument block (SectorArgs) only copy it.  violations() is THE list of what the kernel relies on.
+constexpr size_t kMaxStatSlots = 8u << 12;        // one (rays, visits) slot per sector workgroup
+constexpr size_t kSectorLdsMax = 160u * 1024u;    // LDS of a gfx950 CU: the most hipFuncAttributeMaxDynamicSharedMemorySize grants
+
+// the knobs of Tuning (gv_context.hpp) the plan reads; read_tuning fills them with the rest
+struct SectorTuning {
+  int32_t log2s = 0, cap = 0, log2m = 0;   // GV_LOG2S / GV_CAP / GV_LOG2M (sweeps)
+  int32_t log2s_oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // GV_LOG2S_OCT="a,b,..." per octant index (sweeps)
+  int32_t sector_rev = -1;                 // GV_SECTOR_REV (sweeps)
+  int reorder = 1;                         // GV_SECTOR_REORDER=0: workgroups in natural (octant, sector) order
+  int helpers = -1;                        // GV_SECTOR_HELPERS: -1 automatic, 0 off, 1 on
+  int32_t flat_k = 8;                      // GV_FLAT_K: exact-cell : marched-cell cost ratio (0 = always march)
+  uint32_t march_limit = 64u * 512u;       // GV_MARCH_LIMIT
+  uint32_t flat_direct = 2048;             // GV_FLAT_DIRECT
+};
+
+struct SectorPlan {
+  // one bit per precondition of k_ray_sectors (line numbers: gv_raysector.hip)
+  enum : uint32_t {
+    kWideColumn = 1u << 0,      // a column of a sector is one 32-bit word of cell bits (w, line 381; wm, lines 396 and 418)
+    kSectorCount = 1u << 1,     // S <= 2^12: S << log2m stays in 32 bits (SM, line 461)
+    kWorkgroups = 1u << 2,      // wg_base[] is 16 bits wide (line 148); one statistics slot per workgroup (line 168)
+    kLog2m = 1u << 3,           // M = 1 << log2m <= 512 slope buckets: eight blocks of 64 (s_blkmax[8], line 195); 4 is the knob's least
+    kCap = 1u << 4,             // cap >= 2048: the ends of one wavefront's 64 columns fit a chunk (line 974); <= 65536: an
+                                // overflow entry holds a 16-bit index into raw (L.over, sector_lds_layout)
+    kMarksWords = 1u << 5,      // marks[]: one word per wedge column 0 .. imax (line 221); even: what follows it stays 8-byte aligned
+    kLds = 1u << 6,             // sector_lds_layout fits the LDS of a CU
+  };
+  struct Workgroup {
+    int32_t octant, sector, helper, part, nparts, stat_slot, idle;
+  };
+
+  int32_t len[8] = {}, imax = 0;   // wedge length of octant o (xmaj = bit 2, smaj = bit 1): cells to the map edge along the major axis
+  uint8_t log2s_oct[8] = {};
+  uint16_t rev_oct[8] = {};
+  int32_t cap = 0, log2m = 0, marks_words = 0;
+  uint32_t oct_perm = 0;
+  int32_t reorder = 0;
+  uint32_t wg_base[9] = {};        // (SectorArgs holds them in 16 bits: kWorkgroups)
+  int32_t n_helpers = 0;
+  int32_t flat_k = 0;              // the tail parameters
+  uint32_t march_limit = 0, flat_direct = 0;
+  int32_t ch = 4;                  // k_ray_sectors<ch>: every wedge column lives in a register slot of one thread, ch * 512 >= imax
+  size_t lds_bytes = 0;
+  uint32_t total_workgroups = 0;   // the dispatch: helpers first, then the octants' sectors
+  size_t stat_slots = 0;
+
+  SectorPlan() = default;
+  SectorPlan(int32_t nx, int32_t ny, int32_t cx, int32_t cy, size_t n_points, const SectorTuning &tune)
+  {
+    imax = std::max(std::max(cx, nx - 1 - cx), std::max(cy, ny - 1 - cy));
+    int ord[8];
+    for (int o = 0; o < 8; ++o) {
+      const bool xmaj = (o >> 2) & 1, pos = (o >> 1) & 1;
+      len[o] = xmaj ? (pos ? nx - 1 - cx : cx) : (pos ? ny - 1 - cy : cy);
+      ord[o] = o;
+    }
+    // Sectors per octant: the far end of a wedge about 16 cells wide (len <= 16*S; the kernel needs
+    // <= 32) and an estimated <= 12000 ends per sector (the estimate runs ~2x high; above one LDS chunk
+    // of 4096 ends a wedge is processed in row groups, which measured better on config 5 -- 10 M points,
+    // 160 vs 390 us -- than four times as many, thinner wedges).  Measured on
+    // config 3 (tools/sweep_oct.sh, tools/sweep_sectors.sh): the kernel is bound by per-workgroup
+    // latency chains, so fewer, fatter wedges win as long as those two hold, and an octant whose wedge
+    // is short (origin near that map edge) gets proportionally fewer sectors: 128/64/32 sectors for
+    // wedges of 1660/1000/340 columns instead of 128 everywhere does the same frame in 576 instead of
+    // 1024 workgroups, 84 -> 76 us pipelined.  Wider wedges (S = 16 for 340 columns) lose again.
+    const double G = (double)nx * (double)ny;
+    const double dens = std::min((double)n_points, G) / G;
+    double est_max = 0.0;
+    for (int o = 0; o < 8; ++o) {
+      int l2 = 3;   // the gap-sector logic wants S >= 8
+      while ((16 << l2) < len[o]) ++l2;
+      double est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2);
+      while (est > 12000.0 && l2 < 12) {
+        ++l2;
+        est *= 0.5;
+      }
+      if (tune.log2s > 0) { l2 = tune.log2s; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
+      if (tune.log2s_oct[o] > 0) { l2 = tune.log2s_oct[o]; est = 1.5 * dens * (double)len[o] * (double)len[o] / (double)(2 << l2); }
+      log2s_oct[o] = (uint8_t)l2;
+      est_max = std::max(est_max, est);
+    }
+    // Rows of 512 columns, 8 blocks of 64 each, one block per wavefront: a row goes to the wavefronts in ascending or in
+    // descending order, whichever keeps the fullest wavefront lightest (far columns are wider: weight ~ column number),
+    // rows taken from the heaviest (last) one down.  GV_SECTOR_REV=0 / 1: never / always alternate (experiments).
+    for (int o = 0; o < 8; ++o) {
+      const int rows = (len[o] + 511) / 512;
+      double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      uint16_t mask = 0;
+      const double wbase = (double)(1 << log2s_oct[o]);   // a column's cost: its cells (a / S + 1), times S
+      for (int r = std::min(rows, 16) - 1; r >= 0; --r) {
+        double w[8];
+        for (int b = 0; b < 8; ++b) {
+          const int a0 = 512 * r + 64 * b + 1, a1 = std::min(a0 + 63, len[o]);
+          w[b] = a1 >= a0 ? (double)(a1 - a0 + 1) * (0.5 * (double)(a0 + a1) + wbase) : 0.0;
+        }
+        double up = 0.0, down = 0.0;
+        for (int b = 0; b < 8; ++b) { up = std::max(up, load[b] + w[b]); down = std::max(down, load[b] + w[7 - b]); }
+        bool rev = down < up;
+        if (tune.sector_rev == 0) rev = false;
+        if (tune.sector_rev == 1) rev = (r & 1) != 0;
+        if (rev) mask |= (uint16_t)(1u << r);
+        for (int b = 0; b < 8; ++b) load[b] += rev ? w[7 - b] : w[b];
+      }
+      rev_oct[o] = mask;
+    }
+    cap = tune.cap > 0 ? std::max(2048, tune.cap) : ((est_max <= 1700.0 && tune.log2s <= 0) ? 2048 : 4096);
+    flat_k = tune.flat_k;
+    march_limit = tune.march_limit;
+    flat_direct = tune.flat_direct;
+    log2m = tune.log2m > 0 ? tune.log2m : 9;
+    marks_words = (imax + 3) & ~1;   // one word per wedge column, 0..imax
+    std::stable_sort(ord, ord + 8, [&](int a, int b) { return len[a] > len[b]; });
+    reorder = tune.reorder;
+    uint32_t base = 0;
+    for (int k = 0; k < 8; ++k) {
+      oct_perm |= (uint32_t)ord[k] << (3 * k);
+      wg_base[k] = base;
+      base += 1u << std::min<int>(log2s_oct[reorder ? ord[k] : k], 28);   // (beyond 2^12: kSectorCount)
+    }
+    wg_base[8] = base;
+    // second workgroups for the axis / diagonal sectors of every octant once the wedges are long enough to have
+    // heavy tails (GV_SECTOR_HELPERS=0 / 1 forces them off / on)
+    n_helpers = (tune.helpers >= 0) ? (tune.helpers ? 16 : 0) : (imax >= 512 ? 16 : 0);
+    ch = imax <= 4 * kSecThreads ? 4 : imax <= 8 * kSecThreads ? 8 : 16;
+    lds_bytes = sector_lds_layout(cap, marks_words, std::min(log2m, 30)).total;
+    total_workgroups = wg_base[8] + (uint32_t)n_helpers;
+    stat_slots = (size_t)total_workgroups;
+  }
+
+  uint32_t violations() const
+  {
+    uint32_t v = 0;
+    for (int o = 0; o < 8; ++o) {
+      // the widest column of a wedge is the last sector's, at column len, in an x-major octant: floor(len / S) + 1
+      // cells (col_bounds: bhi = len, blo = ceil(len * (S - 1) / S)); no other sector or column is wider
+      if (len[o] >= 1 && (len[o] >> std::min<int>(log2s_oct[o], 30)) + 1 > 32) v |= kWideColumn;
+      if (log2s_oct[o] > 12) v |= kSectorCount;
+    }
+    if (wg_base[8] > 65535u || (size_t)total_workgroups > kMaxStatSlots) v |= kWorkgroups;
+    if (log2m < 4 || log2m > 9) v |= kLog2m;
+    if (cap < 2048 || cap > 65536) v |= kCap;
+    if (marks_words < imax + 1 || (marks_words & 1)) v |= kMarksWords;
+    if (lds_bytes > kSectorLdsMax) v |= kLds;
+    return v;
+  }
+  // what the first violated condition is called in an error message
+  static const char *violation_name(uint32_t v)
+  {
+    return (v & kWideColumn)    ? "sector ray stage: a wedge column is wider than 32 cells (GV_LOG2S / GV_LOG2S_OCT too small for this grid)"
+           : (v & kSectorCount) ? "sector ray stage: more than 4096 sectors in an octant"
+           : (v & kWorkgroups)  ? "too many sector workgroups"
+           : (v & kLog2m)       ? "sector ray stage: log2m outside 4 .. 9"
+           : (v & kCap)         ? "sector ray stage: cap outside 2048 .. 65536"
+           : (v & kMarksWords)  ? "sector ray stage: marks_words below imax + 1 or odd"
+           : (v & kLds)         ? "sector ray stage: the LDS layout exceeds 160 KiB"
+                                : "";
+  }
+
+  // Host twin of the kernel's decode of its place in the dispatch order (k_ray_sectors, gv_raysector.hip lines 147-168,
+  // which stays a device copy): helpers first, then the octants with the longest wedges, and inside an octant the
+  // sectors next to the slopes 0, 1/2, 1 first.  idle: the odd helper of a one-sector octant, which returns at once.
+  Workgroup workgroup(int bid_all) const
+  {
+    const bool helper = bid_all < n_helpers;
+    const int bid = helper ? (int)wg_base[bid_all >> 1] : bid_all - n_helpers;   // (helpers: only k_oct is taken from it)
+    int k_oct = 0;
+    for (int k = 1; k < 8; ++k) k_oct += (bid >= (int)wg_base[k]) ? 1 : 0;
+    const int o = reorder ? ((int)(oct_perm >> (3 * k_oct)) & 7) : k_oct;
+    const int S = 1 << log2s_oct[o];
+    int s = bid - (int)wg_base[k_oct];
+    if (reorder && S >= 8) {
+      const int r = s;
+      if (r < 4) s = (r == 0) ? 0 : (r == 1) ? (S >> 1) - 1 : (r == 2) ? S - 1 : (S >> 1);
+      else s = (r - 4 < (S >> 1) - 2) ? r - 3 : r - 1;
+    }
+    bool idle = false;
+    if (helper) {
+      s = (bid_all & 1) ? S - 1 : 0;
+      idle = S < 2 && (bid_all & 1);   // one sector only: it has one helper
+    }
+    // column share: workgroup `part` of `nparts` evaluates the columns i with i % nparts == part
+    const int nparts = (n_helpers > 0 && (s == 0 || s == S - 1)) ? 2 : 1;
+    return {o, s, helper ? 1 : 0, helper ? 1 : 0, nparts, helper ? (int)wg_base[8] + bid_all : bid, idle ? 1 : 0};
+  }
+};
+
 }  // namespace host
 }  // namespace gv

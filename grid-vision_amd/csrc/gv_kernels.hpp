@@ -232,12 +232,13 @@ void launch_bin_tiles(const BinTileArgs &a, uint32_t n_helpers, hipStream_t s, h
 struct SectorArgs {
   GridParams g;
   RayOrigin org;
+  // from log2s_oct to flat_direct: host::SectorPlan's fields (gv_host_math.hpp), whose violations() lists their bounds
   uint8_t log2s_oct[8];   // sectors of octant o = 1 << log2s_oct[o]: short wedges get fewer, fatter sectors
   uint16_t wg_base[9];    // first workgroup of the k-th octant in dispatch order (oct_perm); [8] = grid size
   uint16_t rev_oct[8];    // octant o, bit c: the threads hold row c of the wedge's columns (512 per row) in descending order
-  int32_t cap;            // ends per LDS chunk (>= 2048)
-  int32_t log2m;          // slope buckets per sector = 1 << log2m (<= 9)
-  int32_t marks_words;    // >= max(nx, ny) + 1
+  int32_t cap;            // ends per LDS chunk
+  int32_t log2m;          // slope buckets per sector = 1 << log2m
+  int32_t marks_words;    // LDS words of cell bits, one per wedge column
   uint32_t oct_perm;      // dispatch order of the octants, 3 bits each (longest wedge first); 0 = identity off
   int32_t reorder;        // 1: longest octants and the rational-gap sectors (0, S/2-1, S/2, S-1) first
   const uint32_t *hitN, *clipN, *hitT, *clipT;
@@ -254,8 +255,13 @@ struct SectorArgs {
   unsigned long long *dbg; // diagnostic phase stamps, 16 per workgroup (null in production)
   unsigned long long *tl;  // diagnostic build: launch begin / end (GV_TIMELINE)
 };
-size_t sector_lds_bytes(int cap, int marks_words, int log2m);
-bool launch_ray_sectors(const SectorArgs &a, hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr);
+// what the launch takes from the plan beside the arguments: k_ray_sectors<ch>, dynamic LDS, workgroups of the whole dispatch
+struct SectorLaunch {
+  int ch;
+  size_t lds_bytes;
+  int total_workgroups;
+};
+bool launch_ray_sectors(const SectorArgs &a, const SectorLaunch &l, hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr);
 
 struct FinalizeTileArgs {
   GridParams g;

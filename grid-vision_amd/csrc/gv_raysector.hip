@@ -109,7 +109,6 @@ __device__ __forceinline__ unsigned pack_ab(int a, int b, int incl) { return ((u
 __device__ __forceinline__ int ab_a(unsigned p) { return (int)(p >> 14) & 0x1FFF; }
 __device__ __forceinline__ int ab_b(unsigned p) { return (int)(p >> 1) & 0x1FFF; }
 
-constexpr int kSecThreads = 512;   // 8 wavefronts per sector workgroup
 // Timing experiments (phase ablation, in-kernel clock stamps) exist only in the diagnostic build
 // (-DGV_DIAG, tools/): the production kernel carries none of their branches or stores.
 #ifdef GV_DIAG
@@ -121,39 +120,8 @@ constexpr int kSecThreads = 512;   // 8 wavefronts per sector workgroup
 #define GV_SECTOR_WPE 4             // min waves per SIMD the register allocator must allow
 #endif
 
-// Ends of a slope bucket: the first kSlots in the bucket's own row of a table, in arrival order; what a crowded bucket
-// holds beyond that (the buckets of the few rational slopes many ends share) goes to one overflow list.  No count /
-// prefix / placement passes: an end is placed the moment its bucket is known.
-constexpr int kSlotLog = 3, kSlots = 1 << kSlotLog;
-#ifndef GV_SLOT_TOTAL
-#define GV_SLOT_TOTAL 2048
-#endif
-constexpr int kSlotTotal = GV_SLOT_TOTAL;   // a wedge with more ends than this (4 per bucket: measured, config 3 and config 5) is placed by counting sort instead
-
-// LDS layout of one sector workgroup (bytes), shared by the kernel and the launcher
-struct SectorLds {
-  size_t tab, marks, cnt, bstart, bmax32, lvl, pfx, sfx, raw, over, total;
-};
-__host__ __device__ inline SectorLds sector_lds_layout(int cap, int marks_words, int log2m)
-{
-  const size_t M = (size_t)1 << log2m;
-  SectorLds L;
-  size_t o = 0;
-  L.tab = o;    o += (M * kSlots > (size_t)cap ? M * kSlots : (size_t)cap) * 4;   // [M][kSlots] packed ends (16-byte aligned rows); a crowded group: cap ends grouped by bucket
-  L.raw = o;    o += (size_t)cap * 4;           // packed ends in scan order (staging list; the long-ray pass reads it too)
-  L.over = o;   o += (size_t)(cap > 2 * kSlotTotal ? cap : 2 * kSlotTotal) * 4;   // overflow entries: bucket << 16 | index into raw -- two lists of
-                                                // kSlotTotal (as placed / after the same-slope merge); a crowded group: cap bucket numbers (16 bit)
-  L.marks = o;  o += (size_t)marks_words * 4;
-  L.cnt = o;    o += M * 4;                     // ends per bucket (may exceed kSlots); a crowded group: the end of every bucket's run
-  L.bstart = o; o += M * 4;                     // a crowded group: the start of every bucket's run
-  L.bmax32 = o; o += 2 * M * 4;                 // bucket max reach; dead once the range-max tables are built: then the long-ray list (2M entries)
-  L.lvl = o;
-  L.pfx = L.lvl + 7 * M * 2;                    // in-block (64 buckets) sparse levels 0..6
-  L.sfx = L.pfx + M * 2;
-  o += 9 * M * 2;
-  L.total = (o + 15) & ~(size_t)15;
-  return L;
-}
+// (slope-bucket slots kSlots / kSlotTotal and the LDS layout sector_lds_layout: gv_types.hpp, one text for the kernel and
+// the host's plan)
 
 template <int CH>
 __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(SectorArgs A)
@@ -175,6 +143,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
   // and hundreds of columns are evaluated cell by cell (70 k cycles against a 36 k mean: they set the kernel's
   // makespan).  Each of them is run by TWO workgroups that build the same tables and take every second column
   // of the evaluation.  Helper 2q + e = octant q of the dispatch order, sector e ? S - 1 : 0, odd columns.
+  // (Host twin of this decode, down to stat_slot: host::SectorPlan::workgroup, gv_host_math.hpp.)
   const bool helper = bid_all < A.n_helpers;
   const int bid = helper ? (int)A.wg_base[bid_all >> 1] : bid_all - A.n_helpers;   // (helpers: only k_oct is taken from it)
   int k_oct = 0;
@@ -409,7 +378,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
       int blo, bhi;
       col_bounds(ac, blo, bhi);
       const bool ok = in && blo <= bhi;
-      const int w = ok ? bhi - blo + 1 : 0;   // <= 32 (host guarantees imax <= 30*S)
+      const int w = ok ? bhi - blo + 1 : 0;   // <= 32 (host::SectorPlan::kWideColumn)
       const int major_abs = oc_major + m24(oc.smaj, ac);
       const int m_lo = ok ? ((oc.smin > 0) ? oc_minor + blo : oc_minor - bhi) : 0;
       const int w0 = m_lo >> 5;
@@ -489,7 +458,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
   // evaluated exactly below (cell 1 resp. w-2), like the edge cells themselves.
   int xb0 = 0, xb1 = 0, xt0 = 0, xt1 = 0;   // excluded buckets [xb0, xb1) at the bottom, [xt0, xt1) at the top
   if (S >= 8) {
-    const unsigned SM = (unsigned)S << LM;   // S <= 2^12 (the host), M <= 2^9: 32 bits (a 64-bit division here was ~4 k cycles
+    const unsigned SM = (unsigned)S << LM;   // S <= 2^12, M <= 2^9 (host::SectorPlan::violations): 32 bits (a 64-bit division here was ~4 k cycles
                                              // of these four sectors' -- the heaviest ones' -- chain)
     const int qlo = (s == 0) ? 1 : ((s == (S >> 1)) ? 2 : 0);
     const int qhi = (s == S - 1) ? 1 : ((s == (S >> 1) - 1) ? 2 : 0);
@@ -1089,44 +1058,32 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
   }
 }
 
-size_t sector_lds_bytes(int cap, int marks_words, int log2m)
+// One launch of k_ray_sectors<CH>.  More than 64 KB of dynamic LDS has to be announced per kernel (once per size
+// increase); false: the runtime refused (hipGetLastError tells the caller; the plan keeps lds_bytes within a CU's LDS).
+template <int CH>
+static bool launch_sectors_ch(const SectorArgs &a, int grid, size_t lds, hipStream_t s, hipEvent_t done, hipEvent_t t0)
 {
-  return sector_lds_layout(cap, marks_words, log2m).total;
+  static size_t granted = 0;
+  if (lds > granted && lds > 64u * 1024u) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ray_sectors<CH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return false;
+    granted = lds;
+  }
+  hipExtLaunchKernelGGL(k_ray_sectors<CH>, dim3(grid), dim3(kSecThreads), (uint32_t)lds, s, t0, done, 0, a);
+  return true;
 }
 
 // `done` (optional): an event that completes with this kernel, carried by the kernel's own dispatch packet
 // (hipExtLaunchKernelGGL) -- a hipEventRecord behind it would put a marker packet into the queue and ~7 us
 // between this kernel and the next one of the stream.  Returns false when nothing was launched (the
-// caller then records the event the ordinary way).
-bool launch_ray_sectors(const SectorArgs &a, hipStream_t s, hipEvent_t done, hipEvent_t t0)
+// caller then records the event the ordinary way).  Derives nothing: l is host::SectorPlan's.
+bool launch_ray_sectors(const SectorArgs &a, const SectorLaunch &l, hipStream_t s, hipEvent_t done, hipEvent_t t0)
 {
-  if (!a.org.valid) return false;
-  const size_t lds = sector_lds_bytes(a.cap, a.marks_words, a.log2m);
-  const int imax = std::max(std::max(a.org.cx, a.g.nx - 1 - a.org.cx), std::max(a.org.cy, a.g.ny - 1 - a.org.cy));
-  // every wedge column lives in a register slot of one thread: CH * 512 >= imax
-  const int total = a.wg_base[8] + a.n_helpers;
-  if (a.wg_first >= total) return false;
-  const int grid = (total - a.wg_first + a.wg_stride - 1) / a.wg_stride;
-  // more than 64 KB of dynamic LDS has to be announced per kernel (once per size increase)
-  auto allow_lds = [&](const void *fn, size_t &granted) {
-    if (lds > granted && lds > 64u * 1024u) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-      granted = lds;
-    }
-    return true;
-  };
-  static size_t granted[3] = {0, 0, 0};
-  if (imax <= 4 * kSecThreads) {
-    if (!allow_lds(reinterpret_cast<const void *>(&k_ray_sectors<4>), granted[0])) return false;
-    hipExtLaunchKernelGGL(k_ray_sectors<4>, dim3(grid), dim3(kSecThreads), (uint32_t)lds, s, t0, done, 0, a);
-  } else if (imax <= 8 * kSecThreads) {
-    if (!allow_lds(reinterpret_cast<const void *>(&k_ray_sectors<8>), granted[1])) return false;
-    hipExtLaunchKernelGGL(k_ray_sectors<8>, dim3(grid), dim3(kSecThreads), (uint32_t)lds, s, t0, done, 0, a);
-  } else {
-    if (!allow_lds(reinterpret_cast<const void *>(&k_ray_sectors<16>), granted[2])) return false;
-    hipExtLaunchKernelGGL(k_ray_sectors<16>, dim3(grid), dim3(kSecThreads), (uint32_t)lds, s, t0, done, 0, a);
-  }
-  return true;
+  if (!a.org.valid || a.wg_first >= l.total_workgroups) return false;
+  const int grid = (l.total_workgroups - a.wg_first + a.wg_stride - 1) / a.wg_stride;
+  return l.ch == 4   ? launch_sectors_ch<4>(a, grid, l.lds_bytes, s, done, t0)
+         : l.ch == 8 ? launch_sectors_ch<8>(a, grid, l.lds_bytes, s, done, t0)
+                     : launch_sectors_ch<16>(a, grid, l.lds_bytes, s, done, t0);
 }
 
 // ------------------------------------------------------ tile grid pass -----

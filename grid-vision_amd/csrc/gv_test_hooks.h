@@ -34,6 +34,28 @@ int gv_test_bbox_pose_nodes(gv_handle h, const gv_bbox *bboxes, int32_t nb, int3
  * (tests/test_oracle_properties.py). */
 int gv_test_shard_plan(int32_t nx, int32_t ny, int32_t world, int64_t *slice, int64_t *chunk, int32_t *equal_bands,
                        int64_t *cnt0, int32_t *rows /* 2 * world */);
+/* Host only, no handle and no device: the plan of the sector ray stage (host::SectorPlan, csrc/gv_host_math.hpp) that a
+ * handle over an nx x ny grid builds for origin cell (cx, cy) and a cloud of n_points, with the knobs read from the
+ * environment by the function gv_create reads them with.  wg[7 * b ..] = octant, sector, helper, part, nparts, stat slot,
+ * idle of workgroup b of the dispatch order, for b < min(total_workgroups, wg_cap) (tests/test_sector_plan_host.py). */
+typedef struct gv_test_sector_plan_t {
+  int32_t len[8], imax;
+  int32_t log2s_oct[8], rev_oct[8];
+  int32_t cap, log2m, marks_words;
+  uint32_t oct_perm;
+  int32_t reorder;
+  uint32_t wg_base[9];
+  int32_t n_helpers;
+  int32_t flat_k;
+  uint32_t march_limit, flat_direct;
+  int32_t ch;
+  int64_t lds_bytes;
+  uint32_t total_workgroups;
+  int64_t stat_slots;
+  uint32_t violations;          /* host::SectorPlan::violations(), bits in the order of its enum */
+} gv_test_sector_plan_t;
+int gv_test_sector_plan(int32_t nx, int32_t ny, int32_t cx, int32_t cy, int64_t n_points, gv_test_sector_plan_t *plan,
+                        int32_t *wg /* 7 * wg_cap */, int64_t wg_cap);
 #ifdef __cplusplus
 }
 #endif

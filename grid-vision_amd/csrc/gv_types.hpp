@@ -3,6 +3,7 @@
 // geometry that host and device evaluate from one text (GV_HD, as gv_line.hpp does).
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/gridvision_hip.h"
@@ -85,6 +86,42 @@ struct NavStep {
 GV_HD uint32_t nav_step(NavStep s, uint32_t v)
 {
   return (int32_t)v >= s.obstacle_cost ? 0u : 1u + (uint32_t)s.cost_weight * v;
+}
+
+// ---- sector ray stage (gv_raysector.hip): what the kernel and the host's plan (host::SectorPlan) size LDS by
+constexpr int kSecThreads = 512;   // 8 wavefronts per sector workgroup
+// Ends of a slope bucket: the first kSlots in the bucket's own row of a table, in arrival order; what a crowded bucket
+// holds beyond that (the buckets of the few rational slopes many ends share) goes to one overflow list.  No count /
+// prefix / placement passes: an end is placed the moment its bucket is known.
+constexpr int kSlotLog = 3, kSlots = 1 << kSlotLog;
+#ifndef GV_SLOT_TOTAL
+#define GV_SLOT_TOTAL 2048
+#endif
+constexpr int kSlotTotal = GV_SLOT_TOTAL;   // a wedge with more ends than this (4 per bucket: measured, config 3 and config 5) is placed by counting sort instead
+
+// LDS layout of one sector workgroup (bytes), shared by the kernel and the plan
+struct SectorLds {
+  size_t tab, marks, cnt, bstart, bmax32, lvl, pfx, sfx, raw, over, total;
+};
+GV_HD SectorLds sector_lds_layout(int cap, int marks_words, int log2m)
+{
+  const size_t M = (size_t)1 << log2m;
+  SectorLds L;
+  size_t o = 0;
+  L.tab = o;    o += (M * kSlots > (size_t)cap ? M * kSlots : (size_t)cap) * 4;   // [M][kSlots] packed ends (16-byte aligned rows); a crowded group: cap ends grouped by bucket
+  L.raw = o;    o += (size_t)cap * 4;           // packed ends in scan order (staging list; the long-ray pass reads it too)
+  L.over = o;   o += (size_t)(cap > 2 * kSlotTotal ? cap : 2 * kSlotTotal) * 4;   // overflow entries: bucket << 16 | index into raw -- two lists of
+                                                // kSlotTotal (as placed / after the same-slope merge); a crowded group: cap bucket numbers (16 bit)
+  L.marks = o;  o += (size_t)marks_words * 4;
+  L.cnt = o;    o += M * 4;                     // ends per bucket (may exceed kSlots); a crowded group: the end of every bucket's run
+  L.bstart = o; o += M * 4;                     // a crowded group: the start of every bucket's run
+  L.bmax32 = o; o += 2 * M * 4;                 // bucket max reach; dead once the range-max tables are built: then the long-ray list (2M entries)
+  L.lvl = o;
+  L.pfx = L.lvl + 7 * M * 2;                    // in-block (64 buckets) sparse levels 0..6
+  L.sfx = L.pfx + M * 2;
+  o += 9 * M * 2;
+  L.total = (o + 15) & ~(size_t)15;
+  return L;
 }
 
 // Inclusive index rectangle of one object (updateGridCellsFast block).

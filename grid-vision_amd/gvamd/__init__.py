@@ -285,6 +285,42 @@ def shard_plan(nx, ny, world):
                 rows=[(int(rows[2 * r]), int(rows[2 * r + 1])) for r in range(world)])
 
 
+class _SectorPlan(C.Structure):
+    _fields_ = [("len", C.c_int32 * 8), ("imax", C.c_int32), ("log2s_oct", C.c_int32 * 8), ("rev_oct", C.c_int32 * 8),
+                ("cap", C.c_int32), ("log2m", C.c_int32), ("marks_words", C.c_int32), ("oct_perm", C.c_uint32),
+                ("reorder", C.c_int32), ("wg_base", C.c_uint32 * 9), ("n_helpers", C.c_int32), ("flat_k", C.c_int32),
+                ("march_limit", C.c_uint32), ("flat_direct", C.c_uint32), ("ch", C.c_int32), ("lds_bytes", C.c_int64),
+                ("total_workgroups", C.c_uint32), ("stat_slots", C.c_int64), ("violations", C.c_uint32)]
+
+
+# host::SectorPlan's violation bits (csrc/gv_host_math.hpp), in the order of its enum
+SECTOR_VIOLATIONS = ("wide_column", "sector_count", "workgroups", "log2m", "cap", "marks_words", "lds")
+SECTOR_WG_FIELDS = ("octant", "sector", "helper", "part", "nparts", "stat_slot", "idle")
+
+
+def sector_plan(nx, ny, cx, cy, n, workgroups=True):
+    """test hook (csrc/gv_test_hooks.h): the sector ray stage's plan for an nx x ny grid, origin cell (cx, cy) and a cloud
+    of n points, under the knobs of the environment: a dict of the plan's fields (arrays as lists), `violations` (the bit
+    mask) and `violated` (names from SECTOR_VIOLATIONS), and wg = int32 array (total_workgroups, 7) of SECTOR_WG_FIELDS
+    per workgroup of the dispatch order (host only; needs no GPU)"""
+    P = _SectorPlan()
+    lib = load()
+    rc = lib.gv_test_sector_plan(C.c_int32(nx), C.c_int32(ny), C.c_int32(cx), C.c_int32(cy), C.c_int64(n), C.byref(P), None,
+                                 C.c_int64(0))
+    if rc:
+        raise GVError(rc, "gv_test_sector_plan")
+    d = {k: (list(getattr(P, k)) if hasattr(getattr(P, k), "__len__") else int(getattr(P, k))) for k, _ in _SectorPlan._fields_}
+    d["violated"] = [name for b, name in enumerate(SECTOR_VIOLATIONS) if d["violations"] >> b & 1]
+    if workgroups:
+        wg = np.zeros((max(d["total_workgroups"], 1), 7), np.int32)
+        rc = lib.gv_test_sector_plan(C.c_int32(nx), C.c_int32(ny), C.c_int32(cx), C.c_int32(cy), C.c_int64(n), C.byref(P),
+                                     _ptr(wg), C.c_int64(len(wg)))
+        if rc:
+            raise GVError(rc, "gv_test_sector_plan")
+        d["wg"] = wg[:d["total_workgroups"]]
+    return d
+
+
 def inflation_cost_table(cfg, resolution):
     """the uint8 cost table (d2max + 1 entries) an Inflation gives at `resolution` (host only; needs no GPU)"""
     table = np.zeros(4096, np.uint8)

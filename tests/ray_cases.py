@@ -27,6 +27,21 @@ O5100 = (4990, 25)
 BAND = 24
 SETS = {"g1024_centre": (G1024, O1024_CENTRE), "g1024_off": (G1024, O1024_OFF), "g5100": (G5100, O5100)}
 
+# ------------------------------------------------------------------ the knob sets the GPU suite runs the scenes under
+# (tests/test_gpu_ray_ends.py; tests/test_sector_plan_host.py checks on the CPU that the sector plan accepts each pair run)
+KNOBS = ("GV_RAY_IMPL", "GV_LOG2M", "GV_LOG2S", "GV_SECTOR_HELPERS", "GV_SECTOR_REORDER", "GV_SECTOR_REV", "GV_CAP",
+         "GV_FLAT_DIRECT", "GV_MARCH_LIMIT", "GV_FLAT_K")
+TUNE_BD = {"defaults": {}, "log2m4": {"GV_LOG2M": "4"}, "log2s5": {"GV_LOG2S": "5"}, "log2s6": {"GV_LOG2S": "6"},
+           "helpers0": {"GV_SECTOR_HELPERS": "0"},
+           "helpers1": {"GV_SECTOR_HELPERS": "1"}, "reorder0": {"GV_SECTOR_REORDER": "0"}, "rev0": {"GV_SECTOR_REV": "0"},
+           "rev1": {"GV_SECTOR_REV": "1"}}
+# the five tail settings of test_sector_tail_policies_agree
+TAILS = ({"GV_FLAT_DIRECT": "0"}, {"GV_FLAT_DIRECT": "1000000000"}, {"GV_MARCH_LIMIT": "0"},
+         {"GV_MARCH_LIMIT": "100000000", "GV_FLAT_K": "0"}, {"GV_FLAT_DIRECT": "300", "GV_MARCH_LIMIT": "3000", "GV_FLAT_K": "2"})
+TAILS_B = {"defaults": {}, **{f"tail{i}": t for i, t in enumerate(TAILS)}}
+TUNE_C = {"defaults": {}, "cap2048": {"GV_CAP": "2048"}, **{f"tail{i}": t for i, t in enumerate(TAILS)},
+          "helpers0": {"GV_SECTOR_HELPERS": "0"}, "helpers1": {"GV_SECTOR_HELPERS": "1"}}
+
 Scene = namedtuple("Scene", "name grid origin tf x y z ends")   # ends: int array (n, 3) of (ix, iy, kind), one row per point
 
 

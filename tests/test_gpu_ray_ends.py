@@ -7,31 +7,19 @@ are what they claim to be.
 GV_LOG2S: a column of a sector is one 32-bit word of cell bits, and the last sector of an x-major octant is
 floor(a / S) + 1 cells wide at column a, so a wedge of 512 columns needs S = 32: GV_LOG2S=5 is the smallest value the
 kernel's w <= 32 allows on G1024 (4 would do for 511 columns only; 3 gives 64 cells and more).  5 is also what the host
-picks for 511 / 512 columns, so GV_LOG2S=6 runs beside it: sector boundaries the defaults do not have."""
+picks for 511 / 512 columns, so GV_LOG2S=6 runs beside it: sector boundaries the defaults do not have.  The library's
+own plan says the same: tests/test_sector_plan_host.py::test_gpu_suite_knob_sets asks it, on the CPU, about every (scene
+set, knob set) pair run here and about the two excluded ones; test_wide_column_is_refused runs an excluded pair."""
 import numpy as np
 import pytest
 
 import oracle_lib as ol
 import ray_cases as rc
 from gvamd import synth
-from ray_cases import SETS
+from ray_cases import KNOBS, SETS, TAILS_B, TUNE_BD, TUNE_C
 from test_gpu_parity import check_grid
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("GV_RAY_IMPL", "GV_LOG2M", "GV_LOG2S", "GV_SECTOR_HELPERS", "GV_SECTOR_REORDER", "GV_SECTOR_REV", "GV_CAP",
-         "GV_FLAT_DIRECT", "GV_MARCH_LIMIT", "GV_FLAT_K")
-TUNE_BD = {"defaults": {}, "log2m4": {"GV_LOG2M": "4"}, "log2s5": {"GV_LOG2S": "5"}, "log2s6": {"GV_LOG2S": "6"},
-           "helpers0": {"GV_SECTOR_HELPERS": "0"},
-           "helpers1": {"GV_SECTOR_HELPERS": "1"}, "reorder0": {"GV_SECTOR_REORDER": "0"}, "rev0": {"GV_SECTOR_REV": "0"},
-           "rev1": {"GV_SECTOR_REV": "1"}}
-# the five tail settings of test_sector_tail_policies_agree
-TAILS = ({"GV_FLAT_DIRECT": "0"}, {"GV_FLAT_DIRECT": "1000000000"}, {"GV_MARCH_LIMIT": "0"},
-         {"GV_MARCH_LIMIT": "100000000", "GV_FLAT_K": "0"}, {"GV_FLAT_DIRECT": "300", "GV_MARCH_LIMIT": "3000", "GV_FLAT_K": "2"})
-TAILS_B = {"defaults": {}, **{f"tail{i}": t for i, t in enumerate(TAILS)}}
-TUNE_C = {"defaults": {}, "cap2048": {"GV_CAP": "2048"}, **{f"tail{i}": t for i, t in enumerate(TAILS)},
-          "helpers0": {"GV_SECTOR_HELPERS": "0"}, "helpers1": {"GV_SECTOR_HELPERS": "1"}}
-
 
 @pytest.fixture(scope="module")
 def gvamd():
@@ -183,13 +171,31 @@ def test_single_end_every_cell_simple_impl(gvamd, monkeypatch):
 
 
 # ------------------------------------------------------------------ family B
-# (GV_LOG2S on G1024 only: 32 or 64 sectors cannot hold a wedge of 4990 columns)
+# (GV_LOG2S on G1024 only: 32 or 64 sectors cannot hold a wedge of 4990 columns -- the sector plan's width bit, asserted
+# for exactly these pairs by tests/test_sector_plan_host.py::test_gpu_suite_knob_sets)
 @pytest.mark.parametrize("name,tune", [(n, t) for n in SETS for t in TUNE_BD if not (t.startswith("log2s") and n == "g5100")])
 def test_single_long_ends(gvamd, monkeypatch, cache, name, tune):
     """at most one end per octant and frame, on and beside every boundary a power-of-two sector count can have;
     g5100 runs k_ray_sectors<16> (a wedge of 4990 columns)"""
     ss = scene_set(cache, ("B", name), lambda: (*rc.family_b(*SETS[name])[:2], None), dense=False)
     assert run_scenes(gvamd, monkeypatch, ss, TUNE_BD[tune]) > 200
+
+
+def test_wide_column_is_refused(gvamd, monkeypatch):
+    """G5100 under GV_LOG2S=5: columns 156 cells wide.  The frame is refused on the host (GV_ERR_BAD_ARG, the message
+    names the column width) before any kernel of the ray stage is launched, and the handle closes cleanly"""
+    geo = rc.Geo(*SETS["g5100"])
+    h = make_handle(gvamd, monkeypatch, geo, TUNE_BD["log2s5"])
+    try:
+        x, y = geo.hit_point(geo.origin[0] - 40, geo.origin[1] + 3)
+        h.upload_xyz(np.array([x], np.float32), np.array([y], np.float32), np.zeros(1, np.float32))
+        with pytest.raises(gvamd.GVError) as e:
+            h.process_frame(gvamd.FRAME_BIN | gvamd.FRAME_RAYMARCH)
+        assert e.value.code == 1 and gvamd.STATUS[1] == "GV_ERR_BAD_ARG"
+        assert "column" in str(e.value) and "wider than 32 cells" in str(e.value)
+        h.synchronize()
+    finally:
+        h.close()
 
 
 @pytest.mark.parametrize("tune", list(TAILS_B))
