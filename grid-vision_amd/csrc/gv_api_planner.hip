@@ -2,25 +2,30 @@
 //   [EXTENSION] X6  the inflated costmap layer (gv_set_inflation, gv_inflate, its getters and publisher),
 //   [EXTENSION] X7  footprint scoring of trajectories against it (gv_set_footprint, gv_score_trajectories*),
 //   [EXTENSION] X9  the goal / path distance field over it (gv_set_nav_config, gv_nav_field and its getters) and its
-//                   sampler along trajectories (gv_score_nav*).
-// The kernels are gv_inflate.hip, gv_trajscore.hip and gv_navfield.hip (which also argues why the rounds end at the
-// exact field).  What the two samplers do alike is written once, in front of the entry points.
+//                   sampler along trajectories (gv_score_nav*),
+//   [EXTENSION] X10 the rollout that makes such trajectories on the device and the control step that scores the resident
+//                   rollout with X7 and X9 and selects (gv_set_motion_model, gv_rollout*, gv_control_step*).
+// The kernels are gv_inflate.hip, gv_trajscore.hip, gv_navfield.hip (which also argues why the rounds end at the
+// exact field) and gv_rollout.hip.  What the two samplers do alike is written once, in front of the entry points.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "gv_context.hpp"
+#include "gv_motion.hpp"
 
 namespace gv_internal __attribute__((visibility("hidden"))) {
 
 // What a call refuses with GV_ERR_STATE, checked in this order: `missing` (the call's own configuration is not set:
-// the caller passes the text, or null), a layer in `needs` that no call has made since gv_create / gv_reset, and a
-// communicator of more than one rank (`sharded`: why a row band of the grid will not do).  h->err says which.
+// the caller passes the text, or null), a rollout or a layer in `needs` that no call has made since gv_create (the
+// rollout) or gv_create / gv_reset (the layers), and a communicator of more than one rank (`sharded`: why a row band
+// of the grid will not do).  h->err says which.
 int refuse_state(gv_context *h, const char *call, const char *missing, unsigned needs, const char *sharded)
 {
   std::string why;
   if (missing) why = missing;
+  else if ((needs & kNeedRollout) && !h->roll.have) why = "no rollout (gv_rollout)";
   else if ((needs & kNeedCostmap) && !h->infl.have_cost) why = "no costmap (gv_inflate)";
   else if ((needs & kNeedField) && !h->nav.have_field) why = "no distance field (gv_nav_field)";
   else if (h->sh.world > 1) why = std::string("ranks own row bands of the grid, ") + sharded;
@@ -79,6 +84,25 @@ int wait_scored(gv_context *h, int rc, int32_t K)
   if (rc || K == 0) return rc;
   GV_HIP(hipStreamSynchronize(h->stream));
   return GV_OK;
+}
+
+// ---- X10: what the device calls and their host twins check alike
+bool motion_model_valid(const gv_motion_model &m)
+{
+  return (m.model == GV_MOTION_DIFF || m.model == GV_MOTION_OMNI) && std::isfinite(m.dt) && m.dt > 0.0 && m.flags == 0u;
+}
+
+// a rollout's batch: a finite start, K * P * C controls (K * C with GV_ROLLOUT_CONSTANT), flags within `allowed`
+bool rollout_ok(const double *start, const float *controls, int32_t K, int32_t P, uint32_t flags, uint32_t allowed)
+{
+  return start && controls && std::isfinite(start[0]) && std::isfinite(start[1]) && std::isfinite(start[2]) && P >= 1 &&
+         P <= 4096 && K >= 0 && K <= (1 << 20) && (int64_t)K * (int64_t)P <= (int64_t)(1 << 24) && (flags & ~allowed) == 0;
+}
+
+bool critic_weights_valid(const gv_critic_weights &w)
+{
+  return w.w_cost_sum <= 65535u && w.w_max_cost <= 65535u && w.w_nav_last <= 65535u && w.w_nav_sum <= 65535u &&
+         w.w_nav_best <= 65535u && w.flags == 0u;
 }
 
 }  // namespace
@@ -423,6 +447,187 @@ int gv_score_nav_async(gv_handle h, const float *poses, int32_t K, int32_t P, ui
 int gv_score_nav(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_nav_score *scores)
 {
   return wait_scored(h, gv_score_nav_async(h, poses, K, P, flags, scores), K);
+}
+
+// ---- [EXTENSION] X10: rollout and control step ----
+// handle configuration only; every rollout copies h->roll.model into its kernel arguments
+int gv_set_motion_model(gv_handle h, const gv_motion_model *m)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  if (!m) {
+    h->roll.set = false;
+    return GV_OK;
+  }
+  if (!motion_model_valid(*m)) return GV_ERR_BAD_ARG;
+  h->roll.model = *m;
+  h->roll.set = true;
+  return GV_OK;
+}
+
+// A copy of the controls (host controls only) and one kernel on the public stream.  The pose buffer grows by
+// DevBuf::reserve (hipFree waits for the device: no kernel in flight loses the block it reads); the rollout it held is
+// gone then, and this call writes the next one.
+int gv_rollout_async(gv_handle h, const double start[3], const float *controls, int32_t K, int32_t P, uint32_t flags)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!rollout_ok(start, controls, K, P, flags, GV_ROLLOUT_DEVICE_CONTROLS | GV_ROLLOUT_CONSTANT)) return GV_ERR_BAD_ARG;
+  gv_context::Rollout &r = h->roll;
+  if (!r.set) {
+    h->err = "gv_rollout: no motion model set (gv_set_motion_model)";
+    return GV_ERR_STATE;
+  }
+  int rc = GV_OK;
+  if (K == 0 || (rc = set_device_only(h))) return rc;
+  RolloutArgs a{};
+  a.model = r.model.model;
+  a.dt = r.model.dt;
+  for (int i = 0; i < 3; ++i) a.start[i] = start[i];
+  a.K = K; a.P = P;
+  a.constant = (flags & GV_ROLLOUT_CONSTANT) != 0;
+  const size_t n_poses = (size_t)K * (size_t)P;
+  const size_t n_controls = (a.constant ? (size_t)K : n_poses) * (size_t)motion_controls(a.model);
+  if (n_poses * 3 > r.poses.cap()) r.have = false;   // the buffer is about to move
+  if ((rc = r.poses.reserve(h, n_poses * 3))) return rc;
+  a.controls = controls;
+  if (!(flags & GV_ROLLOUT_DEVICE_CONTROLS)) {
+    if ((rc = r.d_controls.reserve(h, n_controls))) return rc;
+    GV_HIP(hipMemcpyAsync(r.d_controls, controls, n_controls * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    a.controls = r.d_controls;
+  }
+  a.poses = r.poses;
+  launch_rollout(a, h->stream);
+  GV_HIP(hipGetLastError());
+  r.K = K; r.P = P;
+  r.have = true;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_rollout(gv_handle h, const double start[3], const float *controls, int32_t K, int32_t P, uint32_t flags)
+{
+  return wait_scored(h, gv_rollout_async(h, start, controls, K, P, flags), K);
+}
+
+int gv_device_rollout(gv_handle h, float **poses, int32_t *K, int32_t *P)
+{
+  if (!h || !poses) return GV_ERR_BAD_ARG;
+  if (!h->roll.have) return GV_ERR_STATE;
+  *poses = h->roll.poses.get();
+  if (K) *K = h->roll.K;
+  if (P) *P = h->roll.P;
+  return GV_OK;
+}
+
+int gv_get_rollout(gv_handle h, float *poses_out)
+{
+  if (!h || !poses_out) return GV_ERR_BAD_ARG;
+  if (!h->roll.have) return GV_ERR_STATE;
+  return copy_out(h, poses_out, h->roll.poses, (size_t)h->roll.K * (size_t)h->roll.P * 3 * sizeof(float));
+}
+
+// host only: motion_step (gv_motion.hpp), one trajectory after the other, one step after the other
+int gv_rollout_poses(const gv_motion_model *m, const double start[3], const float *controls, int32_t K, int32_t P,
+                     uint32_t flags, float *poses_out)
+{
+  if (!m || !poses_out || !motion_model_valid(*m) || !rollout_ok(start, controls, K, P, flags, GV_ROLLOUT_CONSTANT))
+    return GV_ERR_BAD_ARG;
+  const MotionModel mm{m->model, m->dt};
+  const size_t C = (size_t)motion_controls(m->model);
+  const bool constant = (flags & GV_ROLLOUT_CONSTANT) != 0;
+  for (size_t k = 0; k < (size_t)K; ++k) {
+    double X = start[0], Y = start[1], T = start[2];
+    for (size_t p = 0; p < (size_t)P; ++p) {
+      const float *u = controls + (constant ? k : k * (size_t)P + p) * C;
+      motion_step(mm, u, X, Y, T);
+      float *q = poses_out + (k * (size_t)P + p) * 3;
+      q[0] = (float)X; q[1] = (float)Y; q[2] = (float)T;
+    }
+  }
+  return GV_OK;
+}
+
+// The two samplers over the resident rollout into their device record buffers, then the selection, all on the public
+// stream; the existing launchers and argument blocks, as gv_score_trajectories_async / gv_score_nav_async fill them.
+int gv_control_step_async(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result,
+                          uint64_t *totals)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  const bool keep = (flags & GV_CONTROL_KEEP_TOTALS) != 0;
+  if (!w || !result || !critic_weights_valid(*w) || (flags & ~(uint32_t)GV_CONTROL_KEEP_TOTALS) != 0 || (keep && !totals))
+    return GV_ERR_BAD_ARG;
+  const bool nav_used = critic_nav_used(*w);
+  gv_context::Rollout &r = h->roll;
+  int rc = refuse_state(h, "gv_control_step", h->traj.set ? nullptr : "no footprint set (gv_set_footprint)",
+                        kNeedRollout | kNeedCostmap | (nav_used ? kNeedField : 0u), "there is no whole costmap");
+  if (rc || (rc = set_device_only(h))) return rc;
+  const int32_t K = r.K, P = r.P;
+  if ((rc = h->traj.d_scores.reserve(h, (size_t)K)) || (nav_used && (rc = h->nav.d_scores.reserve(h, (size_t)K)))) return rc;
+  ResultDest<gv_control_result> to_result;
+  ResultDest<uint64_t> to_totals;   // stays closed (null, no copy) without GV_CONTROL_KEEP_TOTALS
+  if ((rc = to_result.open(h, result, 1, 16, r.d_result)) || (keep && (rc = to_totals.open(h, totals, (size_t)K, 8, r.d_totals))))
+    return rc;
+  TrajArgs t{};
+  t.g = h->g;
+  t.fp = h->traj.fp;
+  t.poses = r.poses;
+  t.K = K; t.P = P;
+  t.cost = h->infl.cost;
+  t.scores = h->traj.d_scores;
+  t.pose_cost = nullptr;
+  launch_score_trajectories(t, h->stream);
+  if (nav_used) {
+    NavScoreArgs n{};
+    n.g = h->g;
+    n.poses = r.poses;
+    n.K = K; n.P = P;
+    n.field = h->nav.field;
+    n.scores = h->nav.d_scores;
+    launch_score_nav(n, h->stream);
+  }
+  ControlSelectArgs s{};
+  s.w = *w;
+  s.traj = h->traj.d_scores;
+  s.nav = nav_used ? h->nav.d_scores.get() : nullptr;
+  s.K = K;
+  s.result = to_result.dev;
+  s.totals = to_totals.dev;
+  launch_control_select(s, h->stream);
+  GV_HIP(hipGetLastError());
+  if ((rc = to_result.copy_back(h)) || (rc = to_totals.copy_back(h))) return rc;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_control_step(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result, uint64_t *totals)
+{
+  return wait_scored(h, gv_control_step_async(h, w, flags, result, totals), 1);
+}
+
+// host only: control_total / control_take (gv_motion.hpp) in a loop
+int gv_control_select(const gv_critic_weights *w, const gv_traj_score *traj, const gv_nav_score *nav, int32_t K,
+                      gv_control_result *result, uint64_t *totals)
+{
+  if (!w || !traj || !result || !critic_weights_valid(*w) || K < 0 || K > (1 << 20)) return GV_ERR_BAD_ARG;
+  const bool nav_used = critic_nav_used(*w);
+  if (nav_used && !nav) return GV_ERR_BAD_ARG;
+  uint64_t best_total = UINT64_MAX;
+  int32_t best_k = -1, n = 0;
+  for (int32_t k = 0; k < K; ++k) {
+    uint64_t total = UINT64_MAX;
+    const bool ok = control_total(*w, nav_used, traj[k], nav_used ? nav + k : nullptr, total);
+    if (!ok) total = UINT64_MAX;
+    if (totals) totals[k] = total;
+    if (ok) {
+      ++n;
+      control_take(total, k, best_total, best_k);
+    }
+  }
+  result->best = best_k;
+  result->n_valid = n;
+  result->best_total = best_k < 0 ? UINT64_MAX : best_total;
+  return GV_OK;
 }
 
 }  // extern "C"

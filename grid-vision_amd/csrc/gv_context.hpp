@@ -368,6 +368,24 @@ struct __attribute__((visibility("hidden"))) gv_context {
     Event done;                             // public stream: a batch's counters have landed
     DevBuf<gv_nav_score> d_scores;          // the sampler: the landing place of records bound for pageable memory
   } nav;
+  // [EXTENSION] X10 rollout and control step (gv_set_motion_model / gv_rollout* / gv_control_step*).  The motion model is
+  // handle configuration, copied into the kernel arguments of every rollout at enqueue.  `poses` is the resident
+  // rollout, a buffer of its own (d_poses below is the staging copy of host poses, which every scoring call
+  // overwrites); it does not depend on the map, so gv_reset keeps it, and it moves only when a larger rollout grows it.
+  // The control step's samplers write their records into traj.d_scores and nav.d_scores, which are also the landing
+  // buffers of the asynchronous scoring calls: every user enqueues on the public stream only, so a control step's
+  // kernels run behind the copy command that empties a landing buffer, and a later scoring call's kernel behind
+  // k_control_select.  d_result / d_totals are the landing places of a result bound for memory the kernel cannot write.
+  struct Rollout {
+    bool set = false;                       // a motion model is in force
+    gv_motion_model model{};
+    DevBuf<float> poses;                    // K * P * 3
+    int32_t K = 0, P = 0;                   // of the last rollout
+    bool have = false;                      // a rollout since gv_create
+    DevBuf<float> d_controls;               // the device copy of host controls
+    DevBuf<gv_control_result> d_result;
+    DevBuf<uint64_t> d_totals;
+  } roll;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
   // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in
@@ -526,6 +544,6 @@ int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k);
 void comm_destroy(gv_context *h);
 host::ShardPlan shard_plan(const gv_context *h, int world);
 // gv_api_planner.hip
-enum : unsigned { kNeedCostmap = 1u, kNeedField = 2u };
+enum : unsigned { kNeedCostmap = 1u, kNeedField = 2u, kNeedRollout = 4u };
 int refuse_state(gv_context *h, const char *call, const char *missing, unsigned needs, const char *sharded);
 }  // namespace gv_internal

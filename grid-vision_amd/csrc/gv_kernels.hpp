@@ -165,6 +165,27 @@ struct NavScoreArgs {
   gv_nav_score *scores;         // K records (device memory, or the device view of pinned host memory; 8-byte aligned)
 };
 void launch_score_nav(const NavScoreArgs &a, hipStream_t s);
+// [EXTENSION] X10 rollout and control step (gv_rollout.hip; the arithmetic is gv_motion.hpp's).  The motion model, the
+// start and the weights travel by value: a call already enqueued keeps what it was enqueued with.
+struct RolloutArgs {
+  int32_t model;                // GV_MOTION_DIFF / GV_MOTION_OMNI
+  double dt;
+  double start[3];              // X, Y, T
+  const float *controls;        // K * P * C floats, or K * C with `constant` (device)
+  int32_t K, P;
+  bool constant;
+  float *poses;                 // K * P * 3 (device)
+};
+void launch_rollout(const RolloutArgs &a, hipStream_t s);
+struct ControlSelectArgs {
+  gv_critic_weights w;
+  const gv_traj_score *traj;    // K records (device)
+  const gv_nav_score *nav;      // K records (device), or null when no nav weight is set
+  int32_t K;
+  gv_control_result *result;    // one record (device memory, or the device view of pinned host memory; 16-byte aligned)
+  uint64_t *totals;             // K, or null (device memory, or the device view of pinned host memory)
+};
+void launch_control_select(const ControlSelectArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

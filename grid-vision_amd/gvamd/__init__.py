@@ -43,6 +43,13 @@ NAV_UNREACHABLE = 0xFFFFFFFE
 NAV_SCORE_DTYPE = np.dtype([("sum", np.uint64), ("last", np.uint32), ("best", np.uint32), ("best_pose", np.int32),
                             ("n_bad", np.int32)])   # gv_nav_score
 
+MOTION_DIFF = 0
+MOTION_OMNI = 1
+ROLLOUT_DEVICE_CONTROLS = 1 << 0
+ROLLOUT_CONSTANT = 1 << 1
+CONTROL_KEEP_TOTALS = 1 << 0
+CONTROL_RESULT_DTYPE = np.dtype([("best", np.int32), ("n_valid", np.int32), ("best_total", np.uint64)])   # gv_control_result
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -69,6 +76,8 @@ ABI_SYMBOLS = [
     "gv_set_footprint", "gv_score_trajectories_async", "gv_score_trajectories", "gv_footprint_cells",
     "gv_nav_step_table", "gv_set_nav_config", "gv_nav_field", "gv_get_nav_field", "gv_device_nav_field",
     "gv_score_nav_async", "gv_score_nav",
+    "gv_set_motion_model", "gv_rollout_async", "gv_rollout", "gv_device_rollout", "gv_get_rollout", "gv_rollout_poses",
+    "gv_control_step_async", "gv_control_step", "gv_control_select",
 ]
 
 
@@ -130,6 +139,22 @@ class NavConfig(C.Structure):
 class NavInfo(C.Structure):
     """gv_nav_info: what one gv_nav_field did"""
     _fields_ = [("n_seeds_used", C.c_int32), ("rounds", C.c_int32)]
+
+
+class MotionModel(C.Structure):
+    """gv_motion_model: MOTION_DIFF (controls v, w) or MOTION_OMNI (vx, vy, w), the step dt in seconds"""
+    _fields_ = [("model", C.c_int32), ("dt", C.c_double), ("flags", C.c_uint32)]
+
+    @property
+    def n_controls(self):
+        return 3 if self.model == MOTION_OMNI else 2
+
+
+class CriticWeights(C.Structure):
+    """gv_critic_weights: integer weights 0..65535 of the X7 record (cost_sum, max_cost) and of the X9 record (last,
+    sum, best); any nav weight non-zero makes the control step sample the distance field"""
+    _fields_ = [("w_cost_sum", C.c_uint32), ("w_max_cost", C.c_uint32), ("w_nav_last", C.c_uint32),
+                ("w_nav_sum", C.c_uint32), ("w_nav_best", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class FrameDesc(C.Structure):
@@ -357,6 +382,48 @@ def nav_step_table(cfg):
     return table
 
 
+def _motion_model(model, dt=None):
+    """a MotionModel from one, or from (model, dt)"""
+    return model if isinstance(model, MotionModel) else MotionModel(int(model), float(dt), 0)
+
+
+def _control_batch(model, controls, constant):
+    """(float32 array, K, P or None) of a controls array: (K, P, C), or (K, C) when constant"""
+    c = _f32(controls)
+    want = 2 if constant else 3
+    assert c.ndim == want and c.shape[-1] == model.n_controls, "controls is (K, P, C), or (K, C) when constant"
+    return c, int(c.shape[0]), (None if constant else int(c.shape[1]))
+
+
+def rollout_poses(model, start, controls, constant=False, P=None):
+    """the float32 (K, P, 3) poses a MotionModel makes of float32 controls (K, P, C), or (K, C) held for P steps when
+    constant, from start = (x, y, yaw): the library's own arithmetic with the host's sin and cos (host only; needs no
+    GPU)"""
+    c, K, p = _control_batch(model, controls, constant)
+    P = int(P) if constant else p
+    out = np.zeros((K, P, 3), np.float32)
+    s = (C.c_double * 3)(*[float(v) for v in start])
+    rc = load().gv_rollout_poses(C.byref(model), s, _ptr(c), C.c_int32(K), C.c_int32(P),
+                                 C.c_uint32(ROLLOUT_CONSTANT if constant else 0), _ptr(out))
+    if rc:
+        raise GVError(rc, "gv_rollout_poses")
+    return out
+
+
+def control_select(weights, traj, nav=None, keep_totals=False):
+    """combine and select over TRAJ_SCORE_DTYPE / NAV_SCORE_DTYPE records (nav may be None when no nav weight is set):
+    the CONTROL_RESULT_DTYPE record, and with keep_totals also the uint64 totals (host only; needs no GPU)"""
+    traj = np.ascontiguousarray(traj, TRAJ_SCORE_DTYPE)
+    nav = np.ascontiguousarray(nav, NAV_SCORE_DTYPE) if nav is not None else None
+    assert nav is None or len(nav) == len(traj)
+    res = np.zeros(1, CONTROL_RESULT_DTYPE)
+    totals = np.zeros(max(len(traj), 1), np.uint64) if keep_totals else None
+    rc = load().gv_control_select(C.byref(weights), _ptr(traj), _ptr(nav), C.c_int32(len(traj)), _ptr(res), _ptr(totals))
+    if rc:
+        raise GVError(rc, "gv_control_select")
+    return (res[0], totals[:len(traj)]) if keep_totals else res[0]
+
+
 def shard_slice_words(words, world):
     lib = load()
     lib.gv_shard_slice_words.restype = C.c_int64
@@ -406,6 +473,8 @@ class GridVisionHIP:
         self.nx, self.ny, self.pos_x, self.pos_y = nx.value, ny.value, px.value, py.value
         self.G = self.nx * self.ny
         self.n = 0
+        self._motion = None           # the MotionModel in force (set_motion_model)
+        self._pending_controls = []   # host controls of rollout_async calls, kept alive until the stream is waited for
 
     # ---- plumbing
     def _ck(self, rc, where):
@@ -744,6 +813,79 @@ class GridVisionHIP:
                  "gv_score_nav")
         return scores
 
+    # ---- [EXTENSION] rollout and control step over the resident rollout
+    def set_motion_model(self, model, dt=None):
+        """the motion model of the rollout() calls that follow: a MotionModel, or MOTION_DIFF / MOTION_OMNI and dt;
+        set_motion_model(None) turns it off"""
+        if model is None:
+            self._motion = None
+            self._ck(self._lib.gv_set_motion_model(self._h, None), "gv_set_motion_model")
+            return
+        m = _motion_model(model, dt)
+        self._ck(self._lib.gv_set_motion_model(self._h, C.byref(m)), "gv_set_motion_model")
+        self._motion = MotionModel(m.model, m.dt, m.flags)
+
+    def _rollout(self, fn, name, start, controls, constant, device_ptr, P):
+        flags = ROLLOUT_CONSTANT if constant else 0
+        if device_ptr is not None:
+            shape = tuple(controls)            # with device_ptr `controls` is the shape of the device array
+            src, K, flags = C.c_void_p(device_ptr), int(shape[0]), flags | ROLLOUT_DEVICE_CONTROLS
+            P = int(P) if constant else int(shape[1])
+        else:
+            c = _f32(controls)                 # a contiguous float32 array (pinned memory, say) is used where it is
+            assert c.ndim == (2 if constant else 3), "controls is (K, P, C), or (K, C) when constant"
+            assert self._motion is None or c.shape[-1] == self._motion.n_controls, "the motion model takes other controls per step"
+            src, K = _ptr(c), int(c.shape[0])
+            P = int(P) if constant else int(c.shape[1])
+            self._pending_controls.append(c)   # every call in flight keeps its own array (c may be a converted copy)
+        s = (C.c_double * 3)(*[float(v) for v in start])
+        self._ck(fn(self._h, s, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags)), name)
+        if name == "gv_rollout" and K > 0:
+            self._pending_controls.clear()     # the call waited for the stream
+
+    def rollout(self, start, controls, constant=False, device_ptr=None, P=None):
+        """roll float32 controls (K, P, C) -- or (K, C) held for P steps when constant -- out from start = (x, y, yaw)
+        into the handle's resident pose buffer and wait.  device_ptr: the controls are read from that device address
+        and `controls` is their shape."""
+        self._rollout(self._lib.gv_rollout, "gv_rollout", start, controls, constant, device_ptr, P)
+
+    def rollout_async(self, start, controls, constant=False, device_ptr=None, P=None):
+        """rollout() enqueued on stream() without the wait.  The caller leaves host controls unchanged until completion;
+        the handle keeps every such array alive until synchronize() or a synchronous rollout()."""
+        self._rollout(self._lib.gv_rollout_async, "gv_rollout_async", start, controls, constant, device_ptr, P)
+
+    def device_rollout(self):
+        """(device address, K, P) of the resident rollout, for score_trajectories(..., device_ptr=) and score_nav"""
+        p, K, P = C.c_void_p(), C.c_int32(), C.c_int32()
+        self._ck(self._lib.gv_device_rollout(self._h, C.byref(p), C.byref(K), C.byref(P)), "gv_device_rollout")
+        return p.value, K.value, P.value
+
+    def rollout_array(self):
+        """the resident rollout: float32 (K, P, 3)"""
+        _, K, P = self.device_rollout()
+        out = np.empty((K, P, 3), np.float32)
+        self._ck(self._lib.gv_get_rollout(self._h, _ptr(out)), "gv_get_rollout")
+        return out
+
+    def control_step_async(self, weights, result, totals=None):
+        """enqueue on stream(): result a CONTROL_RESULT_DTYPE array of 1, totals None or a uint64 array of K; both
+        complete after synchronize()"""
+        flags = CONTROL_KEEP_TOTALS if totals is not None else 0
+        self._ck(self._lib.gv_control_step_async(self._h, C.byref(weights), C.c_uint32(flags), _ptr(result), _ptr(totals)),
+                 "gv_control_step_async")
+
+    def control_step(self, weights, keep_totals=False):
+        """score the resident rollout against the costmap (and the distance field when a nav weight is set), combine,
+        select.  Returns the CONTROL_RESULT_DTYPE record, and with keep_totals also the uint64 (K,) totals."""
+        res = np.zeros(1, CONTROL_RESULT_DTYPE)
+        totals = None
+        if keep_totals:
+            totals = np.zeros(self.device_rollout()[1], np.uint64)
+        flags = CONTROL_KEEP_TOTALS if keep_totals else 0
+        self._ck(self._lib.gv_control_step(self._h, C.byref(weights), C.c_uint32(flags), _ptr(res), _ptr(totals)),
+                 "gv_control_step")
+        return (res[0], totals) if keep_totals else res[0]
+
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):
         self._keep = []
@@ -788,6 +930,7 @@ class GridVisionHIP:
 
     def synchronize(self):
         self._ck(self._lib.gv_synchronize(self._h), "synchronize")
+        self._pending_controls.clear()
 
     def process_frame(self, flags, bboxes=None, poses=None, net=None):
         d = self._desc(flags, bboxes, poses, net)

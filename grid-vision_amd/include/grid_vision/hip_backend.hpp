@@ -266,6 +266,39 @@ public:
     gv::check(gv_score_nav(ctx_.handle(), poses.data(), K, P, 0u, scores.data()), ctx_.handle(), "gv_score_nav");
     return scores;
   }
+  // [EXTENSION] X10 the controller's loop on the device: configure the motion model once, roll K control sequences out
+  // into the context's resident pose buffer (controls[K * P * C], or [K * C] held for P steps when constant; C = 2 for
+  // GV_MOTION_DIFF, 3 for GV_MOTION_OMNI), then controlStep(): both samplers over the resident rollout, the records
+  // combined with integer weights, the best admissible trajectory selected -- 16 bytes back.  totals, when given,
+  // receives the K totals.  Synchronous; a controller that must not wait calls the _async forms with pinned buffers.
+  void setMotionModel(const gv_motion_model &m) { gv::check(gv_set_motion_model(ctx_.handle(), &m), ctx_.handle(), "gv_set_motion_model"); }
+  void rollout(const double start[3], const std::vector<float> &controls, int32_t K, int32_t P, bool constant = false)
+  {
+    gv::check(gv_rollout(ctx_.handle(), start, controls.data(), K, P, constant ? (uint32_t)GV_ROLLOUT_CONSTANT : 0u), ctx_.handle(),
+              "gv_rollout");
+  }
+  std::vector<float> getRollout()
+  {
+    float *dev = nullptr;
+    int32_t K = 0, P = 0;
+    gv::check(gv_device_rollout(ctx_.handle(), &dev, &K, &P), ctx_.handle(), "gv_device_rollout");
+    std::vector<float> poses((size_t)K * (size_t)P * 3);
+    gv::check(gv_get_rollout(ctx_.handle(), poses.data()), ctx_.handle(), "gv_get_rollout");
+    return poses;
+  }
+  gv_control_result controlStep(const gv_critic_weights &w, std::vector<uint64_t> *totals = nullptr)
+  {
+    gv_control_result r{};
+    if (totals) {
+      float *dev = nullptr;
+      int32_t K = 0;
+      gv::check(gv_device_rollout(ctx_.handle(), &dev, &K, nullptr), ctx_.handle(), "gv_device_rollout");
+      totals->resize((size_t)K);
+    }
+    gv::check(gv_control_step(ctx_.handle(), &w, totals ? (uint32_t)GV_CONTROL_KEEP_TOTALS : 0u, &r, totals ? totals->data() : nullptr),
+              ctx_.handle(), "gv_control_step");
+    return r;
+  }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {

@@ -542,6 +542,117 @@ int gv_device_nav_field(gv_handle h, uint32_t **field);     /* for device-side c
 int gv_score_nav_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_nav_score *scores);
 int gv_score_nav(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_nav_score *scores);
 
+/* ----------------------------------- [EXTENSION] rollout and control step (planner) -- */
+/* X10.  A sampling controller (DWB, MPPI) closes its loop in three steps: roll K control sequences out into K
+ * trajectories of P poses, score them (X7, X9), pick the best.  gv_rollout does the first on the device and keeps the
+ * poses there, where gv_score_trajectories* and gv_score_nav* read them with GV_TRAJ_DEVICE_POSES; gv_control_step does
+ * the other two over the resident rollout and returns 16 bytes.  The reference has no such step; this text is its
+ * definition, modelled on nav2's dwb_plugins::StandardTrajectoryGenerator and MPPI's integrateStateVelocities.
+ *
+ * Motion model (gv_motion_model).  GV_MOTION_DIFF takes the controls (v, w), C = 2 floats per step; GV_MOTION_OMNI takes
+ *   (vx, vy, w), C = 3 floats per step; dt is the step in seconds.  gv_set_motion_model is handle configuration like
+ *   gv_set_footprint: no device work, kept through gv_reset, gv_set_log_odds and gv_grid_move; NULL turns it off (the
+ *   state after gv_create).  Every rollout carries the model in force when it is enqueued; a later gv_set_motion_model
+ *   does not reach it.  GV_ERR_BAD_ARG, configuration unchanged, for a null handle, a model other than the two, dt not
+ *   finite or not > 0, or flags other than 0.
+ * Rollout.  The state (X, Y, T) is fp64 and starts at start[3] (doubles, all finite, else GV_ERR_BAD_ARG).  For step
+ *   p = 0 .. P-1, with the control values widened from float32 to double, every operation one fp64 operation in exactly
+ *   this order, never contracted:
+ *     c = cos(T);  s = sin(T)                       -- the yaw BEFORE the step, as MPPI does
+ *     DIFF:  d = v * dt;                 X = X + d * c;              Y = Y + d * s
+ *     OMNI:  a = vx * dt;  b = vy * dt;  X = X + (a * c - b * s);    Y = Y + (a * s + b * c)
+ *     T = T + w * dt
+ *     pose[p] = ((float)X, (float)Y, (float)T)      -- round to nearest even; pose p is the state AFTER step p
+ *   The yaw is not wrapped.  Non-finite controls are not errors: they propagate by IEEE rules, and the scorers treat
+ *   such poses as off the map.  On the device cos and sin are the device library's fp64 sincos, on the host (
+ *   gv_rollout_poses) the C library's; the two may differ in the last bit, which reaches a float32 pose only when the
+ *   fp64 value lies within about 2^-44 (relative) of a rounding midpoint.  Everything else is the same on both sides.
+ * Controls.  controls[K][P][C] float32, trajectory-major; with GV_ROLLOUT_CONSTANT controls[K][C], one control held for
+ *   all P steps (DWB's generator).  Host memory, copied on the public stream under gv_score_trajectories_async's rules
+ *   for host poses (unchanged until completion; pinned memory makes the copy truly asynchronous); with
+ *   GV_ROLLOUT_DEVICE_CONTROLS device memory that the kernel reads in place, the caller ordering its producer before
+ *   gv_stream(h): the door for a caller that samples its noise on the device.
+ * Limits.  P in 1..4096 and K in 0..2^20 as for X7, and K * P <= 2^24 because the handle owns the pose buffer.  K == 0
+ *   is a successful no-op that leaves the previous rollout in place (once the arguments and the state have passed).
+ *   GV_ERR_BAD_ARG for a null handle, start or controls, a non-finite start, P, K or K * P out of range or unknown flags;
+ *   GV_ERR_STATE without a motion model.
+ * The rollout buffer.  poses[K][P][3] float32, the layout X7 and X9 read, in a buffer of the handle's own (not the
+ *   staging copy of host poses, which every scoring call overwrites).  gv_rollout_async enqueues on gv_stream(h) without
+ *   a host wait (the allocations of a first or larger call aside), ordered like every planner call: behind everything
+ *   enqueued before it, ahead of what follows; allowed between gv_tick_enqueue and gv_tick_wait.  It does not depend on
+ *   the map: gv_reset keeps it.  gv_rollout is the same call followed by the wait for it.
+ *   gv_device_rollout gives the device pointer and the K and P of the last rollout (K, P may be NULL), read-only, for
+ *   GV_TRAJ_DEVICE_POSES; the pointer stays valid until gv_destroy or a larger rollout -- IT MAY CHANGE WHEN THE BUFFER
+ *   GROWS, so ask again after a rollout with a larger K * P.  gv_get_rollout is a synchronous read-back of K * P * 3
+ *   floats.  Both return GV_ERR_STATE before the first rollout, GV_ERR_BAD_ARG for a null handle or pointer.
+ *   gv_rollout_poses is host only and takes no handle: the same arithmetic text compiled for the host, with the C
+ *   library's sin and cos.  Same limits; GV_ERR_BAD_ARG also for a null or invalid model, a null poses_out, or
+ *   GV_ROLLOUT_DEVICE_CONTROLS.
+ *
+ * Control step.  Scores the resident rollout with X7 (the footprint in force) against the costmap of the last
+ *   gv_inflate and, when a nav weight is set, with X9 against the field of the last gv_nav_field, then combines the two
+ *   records of every trajectory and selects.  The records are integers: everything below is exact and does not depend
+ *   on how the work is scheduled.
+ *     nav_used = any of w_nav_last, w_nav_sum, w_nav_best is non-zero.
+ *     Trajectory k is REJECTED iff traj[k].first_collision >= 0, or nav_used and nav[k].n_bad > 0.
+ *     For an admitted trajectory, in uint64 arithmetic (max_cost taken as uint32),
+ *       total = w_cost_sum * cost_sum + w_max_cost * max_cost
+ *               (+ w_nav_last * last + w_nav_sum * sum + w_nav_best * best   when nav_used).
+ *     With n_bad == 0, last and best are field values, so no sentinel is ever multiplied, and with every weight at most
+ *     65535 and P <= 4096 the total stays below 2^61:
+ *       65535 * (4096 * 255 + 255 + (4096 + 2) * 0xFFFFFFFD) = 1.1535e18 < 2^61.
+ *     best = the smallest k that attains the smallest total among the admitted, n_valid = their number, best_total that
+ *     total; best = -1 and best_total = UINT64_MAX when none is admitted.
+ *     With GV_CONTROL_KEEP_TOTALS, totals[K] receives every total, UINT64_MAX for a rejected trajectory.
+ *   gv_control_step_async enqueues three kernels on gv_stream(h) -- the two samplers, then the selection -- without a
+ *   host wait, ordered and allowed like gv_score_trajectories_async.  The samplers' records stay on the device.
+ *   result and totals follow gv_publish_grid_async's rules: pinned result aligned to 16 bytes and pinned totals aligned
+ *   to 8 bytes are written by the kernel, anything else goes through a landing buffer and a copy command; either is
+ *   complete once an event recorded on gv_stream(h) after the call has passed, or after gv_synchronize.
+ *   gv_control_step is the same call followed by the wait.  GV_ERR_BAD_ARG for a null handle, weights or result, a
+ *   weight above 65535, weight flags other than 0, flags other than GV_CONTROL_KEEP_TOTALS, or that flag with null
+ *   totals (ignored without it).  GV_ERR_STATE without a footprint, without a rollout, without a costmap since
+ *   gv_create / gv_reset, without a field when nav_used, and with a communicator of more than one rank.
+ *   gv_control_select is host only and takes no handle: the same combine / select text over K caller records (K in
+ *   0..2^20; nav may be NULL when no nav weight is set, GV_ERR_BAD_ARG when one is; totals may be NULL). */
+enum {
+  GV_MOTION_DIFF = 0,   /* controls (v, w):      C = 2 floats per step */
+  GV_MOTION_OMNI = 1    /* controls (vx, vy, w): C = 3 floats per step */
+};
+typedef struct {
+  int32_t model;    /* GV_MOTION_DIFF or GV_MOTION_OMNI */
+  double dt;        /* s, finite, > 0                    */
+  uint32_t flags;   /* 0                                 */
+} gv_motion_model;
+enum {
+  GV_ROLLOUT_DEVICE_CONTROLS = 1 << 0,   /* controls is device memory, read in place       */
+  GV_ROLLOUT_CONSTANT        = 1 << 1    /* controls[K][C]: one control for all P steps    */
+};
+typedef struct {
+  uint32_t w_cost_sum, w_max_cost, w_nav_last, w_nav_sum, w_nav_best;   /* each 0..65535 */
+  uint32_t flags;                                                       /* 0 */
+} gv_critic_weights;
+typedef struct {
+  int32_t best;          /* the selected trajectory, -1 when none is admitted */
+  int32_t n_valid;       /* admitted trajectories                             */
+  uint64_t best_total;   /* its total, UINT64_MAX when none is admitted       */
+} gv_control_result;     /* 16 bytes */
+enum {
+  GV_CONTROL_KEEP_TOTALS = 1 << 0   /* write totals[K] */
+};
+int gv_set_motion_model(gv_handle h, const gv_motion_model *m);
+int gv_rollout_async(gv_handle h, const double start[3], const float *controls, int32_t K, int32_t P, uint32_t flags);
+int gv_rollout(gv_handle h, const double start[3], const float *controls, int32_t K, int32_t P, uint32_t flags);
+int gv_device_rollout(gv_handle h, float **poses, int32_t *K, int32_t *P);   /* read-only, for GV_TRAJ_DEVICE_POSES */
+int gv_get_rollout(gv_handle h, float *poses_out);                           /* synchronous read-back, K*P*3 floats */
+int gv_rollout_poses(const gv_motion_model *m, const double start[3], const float *controls, int32_t K, int32_t P,
+                     uint32_t flags, float *poses_out);
+int gv_control_step_async(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result,
+                          uint64_t *totals);
+int gv_control_step(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result, uint64_t *totals);
+int gv_control_select(const gv_critic_weights *w, const gv_traj_score *traj, const gv_nav_score *nav, int32_t K,
+                      gv_control_result *result, uint64_t *totals /* may be NULL */);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
@@ -642,8 +753,8 @@ typedef struct {
  * detection set (gv_compute_depth_for_bboxes, gv_compute_bbox_pose*, gv_segment_ground_plane, gv_extract_cloud_per_bbox,
  * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map*,
  * gv_grid_move, gv_set_transforms, gv_set_height_band, gv_set_inflation, gv_inflate, the costmap getters,
- * gv_set_footprint and gv_score_trajectories* may be
- * called; their device work is ordered behind the tick on gv_stream(h), and an upload never
+ * gv_set_footprint, gv_score_trajectories*, gv_set_motion_model, gv_rollout*, the rollout getters and
+ * gv_control_step* may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
  * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
  * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform or height
  * band set in between applies from the next tick on.  (tests/test_gpu_tick.py) */
