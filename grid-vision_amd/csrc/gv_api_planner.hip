@@ -4,9 +4,11 @@
 //   [EXTENSION] X9  the goal / path distance field over it (gv_set_nav_config, gv_nav_field and its getters) and its
 //                   sampler along trajectories (gv_score_nav*),
 //   [EXTENSION] X10 the rollout that makes such trajectories on the device and the control step that scores the resident
-//                   rollout with X7 and X9 and selects (gv_set_motion_model, gv_rollout*, gv_control_step*).
+//                   rollout with X7 and X9 and selects (gv_set_motion_model, gv_rollout*, gv_control_step*),
+//   [EXTENSION] X11 MPPI's two ends around them: sampling the controls and the softmax average (gv_set_mppi, gv_mppi_*).
 // The kernels are gv_inflate.hip, gv_trajscore.hip, gv_navfield.hip (which also argues why the rounds end at the
-// exact field) and gv_rollout.hip.  What the two samplers do alike is written once, in front of the entry points.
+// exact field), gv_rollout.hip and gv_mppi.hip.  What the two samplers do alike, and what a control step and an MPPI
+// update enqueue alike, is written once, in front of the entry points.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -14,6 +16,7 @@
 
 #include "gv_context.hpp"
 #include "gv_motion.hpp"
+#include "gv_mppi.hpp"
 
 namespace gv_internal __attribute__((visibility("hidden"))) {
 
@@ -103,6 +106,158 @@ bool critic_weights_valid(const gv_critic_weights &w)
 {
   return w.w_cost_sum <= 65535u && w.w_max_cost <= 65535u && w.w_nav_last <= 65535u && w.w_nav_sum <= 65535u &&
          w.w_nav_best <= 65535u && w.flags == 0u;
+}
+
+// what gv_control_step_async and gv_mppi_update_async refuse alike
+bool control_args_ok(const gv_critic_weights *w, uint32_t flags, const gv_control_result *result, const uint64_t *totals)
+{
+  return w && result && critic_weights_valid(*w) && (flags & ~(uint32_t)GV_CONTROL_KEEP_TOTALS) == 0 &&
+         (!(flags & GV_CONTROL_KEEP_TOTALS) || totals);
+}
+
+// The two samplers over the resident rollout into their device record buffers, then the selection into `result` and
+// `totals` (null: no totals), on the public stream: what a control step and an MPPI update enqueue alike.
+int enqueue_control_scores(gv_context *h, const gv_critic_weights &w, gv_control_result *result, uint64_t *totals)
+{
+  const bool nav_used = critic_nav_used(w);
+  gv_context::Rollout &r = h->roll;
+  const int32_t K = r.K, P = r.P;
+  int rc = GV_OK;
+  if ((rc = h->traj.d_scores.reserve(h, (size_t)K)) || (nav_used && (rc = h->nav.d_scores.reserve(h, (size_t)K)))) return rc;
+  TrajArgs t{};
+  t.g = h->g;
+  t.fp = h->traj.fp;
+  t.poses = r.poses;
+  t.K = K; t.P = P;
+  t.cost = h->infl.cost;
+  t.scores = h->traj.d_scores;
+  t.pose_cost = nullptr;
+  launch_score_trajectories(t, h->stream);
+  if (nav_used) {
+    NavScoreArgs n{};
+    n.g = h->g;
+    n.poses = r.poses;
+    n.K = K; n.P = P;
+    n.field = h->nav.field;
+    n.scores = h->nav.d_scores;
+    launch_score_nav(n, h->stream);
+  }
+  ControlSelectArgs s{};
+  s.w = w;
+  s.traj = h->traj.d_scores;
+  s.nav = nav_used ? h->nav.d_scores.get() : nullptr;
+  s.K = K;
+  s.result = result;
+  s.totals = totals;
+  launch_control_select(s, h->stream);
+  GV_HIP(hipGetLastError());
+  return GV_OK;
+}
+
+// ---- X11: what the device calls and their host twins check alike
+bool mppi_config_valid(const gv_mppi_config &c, int32_t channels)
+{
+  for (int32_t i = 0; i < channels; ++i)
+    if (!std::isfinite(c.sigma[i]) || !(c.sigma[i] >= 0.0) || std::isnan(c.u_min[i]) || std::isnan(c.u_max[i]) || !(c.u_min[i] <= c.u_max[i]))
+      return false;
+  return std::isfinite(c.lambda) && c.lambda > 0.0 && c.flags == 0u;
+}
+
+bool mppi_shape_ok(int32_t K, int32_t P)
+{
+  return P >= 1 && P <= 4096 && K >= 0 && K <= (1 << 20) && (int64_t)K * (int64_t)P <= (int64_t)(1 << 24);
+}
+
+// What a sampling refuses with GV_ERR_STATE: no configuration, no motion model, no nominal, a nominal of another C.
+int mppi_sample_refused(gv_context *h, const char *call)
+{
+  const gv_context::Mppi &m = h->mppi;
+  const char *why = !m.set ? "no MPPI configuration set (gv_set_mppi)"
+                    : !h->roll.set ? "no motion model set (gv_set_motion_model)"
+                    : !m.have_nominal ? "no nominal sequence (gv_mppi_set_nominal)"
+                    : motion_controls(h->roll.model.model) != m.C ? "the nominal sequence was set under a motion model with other controls per step"
+                                                                  : nullptr;
+  if (!why) return GV_OK;
+  h->err = std::string(call) + ": " + why;
+  return GV_ERR_STATE;
+}
+
+// What an update refuses with GV_ERR_STATE.  `cycle`: the call makes the controls and the rollout itself before it
+// updates, so neither needs to exist yet.
+int mppi_update_refused(gv_context *h, const char *call, const gv_critic_weights &w, bool cycle)
+{
+  const gv_context::Mppi &m = h->mppi;
+  const char *missing = !h->traj.set ? "no footprint set (gv_set_footprint)" : !m.set ? "no MPPI configuration set (gv_set_mppi)" : nullptr;
+  int rc = refuse_state(h, call, missing, (cycle ? 0u : kNeedRollout) | kNeedCostmap | (critic_nav_used(w) ? kNeedField : 0u),
+                        "there is no whole costmap");
+  if (rc) return rc;
+  const char *why = nullptr;
+  if (!m.have_nominal) why = "no nominal sequence (gv_mppi_set_nominal)";
+  else if (!cycle) {
+    if (!m.have_controls) why = "no sampled controls (gv_mppi_sample)";
+    else if (m.cK != h->roll.K || m.cP != h->roll.P) why = "the resident rollout is not of the sampled controls' K and P";
+    else if (m.cP != m.P || m.cC != m.C) why = "the nominal sequence is not of the sampled controls' P and C";
+  }
+  if (!why) return GV_OK;
+  h->err = std::string(call) + ": " + why;
+  return GV_ERR_STATE;
+}
+
+int mppi_enqueue_sample(gv_context *h, int32_t K, uint64_t seed, uint64_t iteration, uint32_t flags)
+{
+  gv_context::Mppi &m = h->mppi;
+  const size_t n = (size_t)K * (size_t)m.P * (size_t)m.C;
+  if (n > m.controls.cap()) m.have_controls = false;   // the buffer is about to move
+  if (int rc = m.controls.reserve(h, n)) return rc;
+  MppiSampleArgs a{};
+  a.cfg = m.cfg;
+  a.C = m.C;
+  a.K = K; a.P = m.P;
+  a.seed = seed; a.iteration = iteration;
+  a.shift = (flags & GV_MPPI_SHIFT) != 0;
+  a.nominal = m.nominal;
+  a.controls = m.controls;
+  launch_mppi_sample(a, h->stream);
+  GV_HIP(hipGetLastError());
+  m.cK = K; m.cP = m.P; m.cC = m.C;
+  m.have_controls = true;
+  return GV_OK;
+}
+
+// the scoring of the resident rollout and the two launches of the average; results a kernel cannot write go by copy
+int mppi_enqueue_update(gv_context *h, const gv_critic_weights &w, uint32_t flags, gv_control_result *result, uint64_t *totals,
+                        float *nominal_out)
+{
+  gv_context::Mppi &m = h->mppi;
+  gv_context::Rollout &r = h->roll;
+  const bool keep = (flags & GV_CONTROL_KEEP_TOTALS) != 0;
+  const int32_t K = r.K;
+  const int64_t J = (int64_t)m.P * (int64_t)m.C;
+  int rc = GV_OK;
+  MppiAverageArgs a{};
+  a.lambda = m.cfg.lambda;
+  a.K = K; a.J = (int32_t)J;
+  a.rows = mppi_chunk_rows(K, J);
+  a.tile = mppi_tile_cols(J);
+  const size_t chunks = (size_t)((K + a.rows - 1) / a.rows);
+  if ((rc = r.d_result.reserve(h, 1)) || (rc = r.d_totals.reserve(h, (size_t)K)) || (rc = m.partial.reserve(h, chunks * ((size_t)J + 1))))
+    return rc;
+  if ((rc = enqueue_control_scores(h, w, r.d_result, r.d_totals))) return rc;
+  a.controls = m.controls;
+  a.totals = r.d_totals;
+  a.result = r.d_result;
+  a.partial = m.partial;
+  a.nominal = m.nominal;
+  a.result_out = static_cast<gv_control_result *>(pinned_device_view(result, 16));
+  a.totals_out = keep ? static_cast<uint64_t *>(pinned_device_view(totals, 8)) : nullptr;
+  a.nominal_out = nominal_out ? static_cast<float *>(pinned_device_view(nominal_out, 8)) : nullptr;
+  launch_mppi_average(a, h->stream);
+  GV_HIP(hipGetLastError());
+  if (!a.result_out) GV_HIP(hipMemcpyAsync(result, r.d_result, sizeof(gv_control_result), hipMemcpyDeviceToHost, h->stream));
+  if (keep && !a.totals_out) GV_HIP(hipMemcpyAsync(totals, r.d_totals, (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  if (nominal_out && !a.nominal_out)
+    GV_HIP(hipMemcpyAsync(nominal_out, m.nominal, (size_t)J * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  return GV_OK;
 }
 
 }  // namespace
@@ -555,46 +710,17 @@ int gv_control_step_async(gv_handle h, const gv_critic_weights *w, uint32_t flag
   if (!h) return GV_ERR_BAD_ARG;
   GV_TRY
   const bool keep = (flags & GV_CONTROL_KEEP_TOTALS) != 0;
-  if (!w || !result || !critic_weights_valid(*w) || (flags & ~(uint32_t)GV_CONTROL_KEEP_TOTALS) != 0 || (keep && !totals))
-    return GV_ERR_BAD_ARG;
+  if (!control_args_ok(w, flags, result, totals)) return GV_ERR_BAD_ARG;
   const bool nav_used = critic_nav_used(*w);
   gv_context::Rollout &r = h->roll;
   int rc = refuse_state(h, "gv_control_step", h->traj.set ? nullptr : "no footprint set (gv_set_footprint)",
                         kNeedRollout | kNeedCostmap | (nav_used ? kNeedField : 0u), "there is no whole costmap");
   if (rc || (rc = set_device_only(h))) return rc;
-  const int32_t K = r.K, P = r.P;
-  if ((rc = h->traj.d_scores.reserve(h, (size_t)K)) || (nav_used && (rc = h->nav.d_scores.reserve(h, (size_t)K)))) return rc;
   ResultDest<gv_control_result> to_result;
   ResultDest<uint64_t> to_totals;   // stays closed (null, no copy) without GV_CONTROL_KEEP_TOTALS
-  if ((rc = to_result.open(h, result, 1, 16, r.d_result)) || (keep && (rc = to_totals.open(h, totals, (size_t)K, 8, r.d_totals))))
+  if ((rc = to_result.open(h, result, 1, 16, r.d_result)) || (keep && (rc = to_totals.open(h, totals, (size_t)r.K, 8, r.d_totals))))
     return rc;
-  TrajArgs t{};
-  t.g = h->g;
-  t.fp = h->traj.fp;
-  t.poses = r.poses;
-  t.K = K; t.P = P;
-  t.cost = h->infl.cost;
-  t.scores = h->traj.d_scores;
-  t.pose_cost = nullptr;
-  launch_score_trajectories(t, h->stream);
-  if (nav_used) {
-    NavScoreArgs n{};
-    n.g = h->g;
-    n.poses = r.poses;
-    n.K = K; n.P = P;
-    n.field = h->nav.field;
-    n.scores = h->nav.d_scores;
-    launch_score_nav(n, h->stream);
-  }
-  ControlSelectArgs s{};
-  s.w = *w;
-  s.traj = h->traj.d_scores;
-  s.nav = nav_used ? h->nav.d_scores.get() : nullptr;
-  s.K = K;
-  s.result = to_result.dev;
-  s.totals = to_totals.dev;
-  launch_control_select(s, h->stream);
-  GV_HIP(hipGetLastError());
+  if ((rc = enqueue_control_scores(h, *w, to_result.dev, to_totals.dev))) return rc;
   if ((rc = to_result.copy_back(h)) || (rc = to_totals.copy_back(h))) return rc;
   return GV_OK;
   GV_CATCH
@@ -628,6 +754,194 @@ int gv_control_select(const gv_critic_weights *w, const gv_traj_score *traj, con
   result->n_valid = n;
   result->best_total = best_k < 0 ? UINT64_MAX : best_total;
   return GV_OK;
+}
+
+// ---- [EXTENSION] X11: MPPI sampling and softmax update ----
+// handle configuration only; every sampling and update copies h->mppi.cfg into its kernel arguments
+int gv_set_mppi(gv_handle h, const gv_mppi_config *cfg)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  if (!cfg) {
+    h->mppi.set = false;
+    return GV_OK;
+  }
+  if (!mppi_config_valid(*cfg, 3)) return GV_ERR_BAD_ARG;
+  h->mppi.cfg = *cfg;
+  h->mppi.set = true;
+  return GV_OK;
+}
+
+// One copy on the public stream and the wait for it: the caller's array is free on return.
+int gv_mppi_set_nominal(gv_handle h, const float *nominal, int32_t P)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!nominal || P < 1 || P > 4096) return GV_ERR_BAD_ARG;
+  if (!h->roll.set) {
+    h->err = "gv_mppi_set_nominal: no motion model set (gv_set_motion_model)";
+    return GV_ERR_STATE;
+  }
+  gv_context::Mppi &m = h->mppi;
+  const int32_t C = motion_controls(h->roll.model.model);
+  const size_t n = (size_t)P * (size_t)C;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(nominal[i])) return GV_ERR_BAD_ARG;
+  int rc = set_device_only(h);
+  if (rc) return rc;
+  if (n > m.nominal.cap()) m.have_nominal = false;
+  if ((rc = m.nominal.reserve(h, n))) return rc;
+  GV_HIP(hipMemcpyAsync(m.nominal, nominal, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  GV_HIP(hipStreamSynchronize(h->stream));
+  m.P = P; m.C = C;
+  m.have_nominal = true;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_get_mppi_nominal(gv_handle h, float *out, int32_t *P)
+{
+  if (!h || (!out && !P)) return GV_ERR_BAD_ARG;
+  if (!h->mppi.have_nominal) return GV_ERR_STATE;
+  if (P) *P = h->mppi.P;
+  return out ? copy_out(h, out, h->mppi.nominal, (size_t)h->mppi.P * (size_t)h->mppi.C * sizeof(float)) : GV_OK;
+}
+
+// One kernel on the public stream.  The controls buffer grows by DevBuf::reserve, like the rollout's.
+int gv_mppi_sample_async(gv_handle h, int32_t K, uint64_t seed, uint64_t iteration, uint32_t flags)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (K < 0 || K > (1 << 20) || (flags & ~(uint32_t)GV_MPPI_SHIFT) != 0) return GV_ERR_BAD_ARG;
+  int rc = mppi_sample_refused(h, "gv_mppi_sample");
+  if (rc) return rc;
+  if (!mppi_shape_ok(K, h->mppi.P)) return GV_ERR_BAD_ARG;
+  if (K == 0 || (rc = set_device_only(h))) return rc;
+  return mppi_enqueue_sample(h, K, seed, iteration, flags);
+  GV_CATCH
+}
+
+int gv_mppi_sample(gv_handle h, int32_t K, uint64_t seed, uint64_t iteration, uint32_t flags)
+{
+  return wait_scored(h, gv_mppi_sample_async(h, K, seed, iteration, flags), K);
+}
+
+int gv_device_controls(gv_handle h, float **controls, int32_t *K, int32_t *P, int32_t *C)
+{
+  if (!h || !controls) return GV_ERR_BAD_ARG;
+  if (!h->mppi.have_controls) return GV_ERR_STATE;
+  *controls = h->mppi.controls.get();
+  if (K) *K = h->mppi.cK;
+  if (P) *P = h->mppi.cP;
+  if (C) *C = h->mppi.cC;
+  return GV_OK;
+}
+
+int gv_get_controls(gv_handle h, float *out)
+{
+  if (!h || !out) return GV_ERR_BAD_ARG;
+  const gv_context::Mppi &m = h->mppi;
+  if (!m.have_controls) return GV_ERR_STATE;
+  return copy_out(h, out, m.controls, (size_t)m.cK * (size_t)m.cP * (size_t)m.cC * sizeof(float));
+}
+
+int gv_mppi_update_async(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result,
+                         uint64_t *totals, float *nominal_out)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!control_args_ok(w, flags, result, totals)) return GV_ERR_BAD_ARG;
+  int rc = mppi_update_refused(h, "gv_mppi_update", *w, false);
+  if (rc || (rc = set_device_only(h))) return rc;
+  return mppi_enqueue_update(h, *w, flags, result, totals, nominal_out);
+  GV_CATCH
+}
+
+int gv_mppi_update(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result, uint64_t *totals,
+                   float *nominal_out)
+{
+  return wait_scored(h, gv_mppi_update_async(h, w, flags, result, totals, nominal_out), 1);
+}
+
+// Every rule of the three calls first, then their enqueues: sample, rollout of the sampled controls, update.
+int gv_mppi_cycle_async(gv_handle h, const double start[3], int32_t K, uint64_t seed, uint64_t iteration,
+                        uint32_t sample_flags, const gv_critic_weights *w, uint32_t flags, gv_control_result *result,
+                        uint64_t *totals, float *nominal_out)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!start || !std::isfinite(start[0]) || !std::isfinite(start[1]) || !std::isfinite(start[2]) || K < 0 || K > (1 << 20) ||
+      (sample_flags & ~(uint32_t)GV_MPPI_SHIFT) != 0 || !control_args_ok(w, flags, result, totals))
+    return GV_ERR_BAD_ARG;
+  int rc = mppi_sample_refused(h, "gv_mppi_cycle");
+  if (rc || (rc = mppi_update_refused(h, "gv_mppi_cycle", *w, true))) return rc;
+  if (!mppi_shape_ok(K, h->mppi.P)) return GV_ERR_BAD_ARG;
+  if (K == 0 || (rc = set_device_only(h))) return rc;
+  if ((rc = mppi_enqueue_sample(h, K, seed, iteration, sample_flags))) return rc;
+  if ((rc = gv_rollout_async(h, start, h->mppi.controls, K, h->mppi.P, GV_ROLLOUT_DEVICE_CONTROLS))) return rc;
+  return mppi_enqueue_update(h, *w, flags, result, totals, nominal_out);
+  GV_CATCH
+}
+
+int gv_mppi_cycle(gv_handle h, const double start[3], int32_t K, uint64_t seed, uint64_t iteration, uint32_t sample_flags,
+                  const gv_critic_weights *w, uint32_t flags, gv_control_result *result, uint64_t *totals, float *nominal_out)
+{
+  return wait_scored(h, gv_mppi_cycle_async(h, start, K, seed, iteration, sample_flags, w, flags, result, totals, nominal_out), K);
+}
+
+// host only: gv_mppi.hpp's text in loops
+int gv_mppi_words(uint64_t seed, uint64_t iteration, uint32_t k, uint32_t p, uint32_t words[4])
+{
+  if (!words) return GV_ERR_BAD_ARG;
+  mppi_words(seed, iteration, k, p, words);
+  return GV_OK;
+}
+
+int gv_mppi_sample_controls(const gv_mppi_config *cfg, int32_t C, const float *nominal, int32_t K, int32_t P, uint64_t seed,
+                            uint64_t iteration, uint32_t flags, float *controls_out)
+{
+  if (!cfg || (C != 2 && C != 3) || !nominal || !controls_out || !mppi_shape_ok(K, P) || !mppi_config_valid(*cfg, C) ||
+      (flags & ~(uint32_t)GV_MPPI_SHIFT) != 0)
+    return GV_ERR_BAD_ARG;
+  for (size_t i = 0; i < (size_t)P * (size_t)C; ++i)
+    if (!std::isfinite(nominal[i])) return GV_ERR_BAD_ARG;
+  const bool shift = (flags & GV_MPPI_SHIFT) != 0;
+  for (size_t k = 0; k < (size_t)K; ++k)
+    for (size_t p = 0; p < (size_t)P; ++p)
+      mppi_sample(*cfg, C, nominal, P, seed, iteration, shift, (uint32_t)k, (uint32_t)p, controls_out + (k * (size_t)P + p) * (size_t)C);
+  return GV_OK;
+}
+
+// the sequential definition: the admitted trajectories in index order, one column after the other
+int gv_mppi_average(const gv_mppi_config *cfg, int32_t C, const float *controls, const uint64_t *totals, int32_t K,
+                    int32_t P, const float *nominal_in, float *nominal_out)
+{
+  gv_context *h = nullptr;
+  if (!cfg || (C != 2 && C != 3) || !controls || !totals || !nominal_in || !nominal_out || !mppi_shape_ok(K, P) ||
+      !mppi_config_valid(*cfg, C))
+    return GV_ERR_BAD_ARG;
+  GV_TRY
+  const size_t J = (size_t)P * (size_t)C;
+  uint64_t best = UINT64_MAX;
+  for (int32_t k = 0; k < K; ++k) best = std::min(best, totals[k]);
+  if (best == UINT64_MAX) {
+    std::memmove(nominal_out, nominal_in, J * sizeof(float));
+    return GV_OK;
+  }
+  std::vector<double> e((size_t)K, -1.0);
+  double S = 0.0;
+  for (int32_t k = 0; k < K; ++k)
+    if (totals[k] != UINT64_MAX) {
+      e[(size_t)k] = mppi_weight(totals[k], best, cfg->lambda);
+      S = S + e[(size_t)k];
+    }
+  for (size_t j = 0; j < J; ++j) {
+    double N = 0.0;
+    for (size_t k = 0; k < (size_t)K; ++k)
+      if (e[k] >= 0.0) N = N + e[k] * (double)controls[k * J + j];
+    nominal_out[j] = (float)(N / S);
+  }
+  return GV_OK;
+  GV_CATCH
 }
 
 }  // extern "C"

@@ -386,6 +386,22 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<gv_control_result> d_result;
     DevBuf<uint64_t> d_totals;
   } roll;
+  // [EXTENSION] X11 MPPI sampling and softmax update (gv_set_mppi / gv_mppi_*).  The configuration is handle state, copied
+  // into the kernel arguments at enqueue.  `nominal` and `controls` are buffers of their own that remember their shape;
+  // neither depends on the map, so gv_reset keeps them, and `controls` moves only when a larger sampling grows it.  An
+  // update has k_control_select write into roll.d_result / roll.d_totals (device memory, the control step's landing
+  // places: every user enqueues on the public stream only) and reads them there; `partial` holds the chunk sums.
+  struct Mppi {
+    bool set = false;                       // a configuration is in force
+    gv_mppi_config cfg{};
+    DevBuf<float> nominal;                  // P * C
+    int32_t P = 0, C = 0;                   // of the nominal
+    bool have_nominal = false;              // a gv_mppi_set_nominal since gv_create
+    DevBuf<float> controls;                 // K * P * C
+    int32_t cK = 0, cP = 0, cC = 0;         // of the last sampling
+    bool have_controls = false;             // a sampling since gv_create
+    DevBuf<double> partial;                 // chunks * (P * C + 1)
+  } mppi;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
   // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in

@@ -186,6 +186,34 @@ struct ControlSelectArgs {
   uint64_t *totals;             // K, or null (device memory, or the device view of pinned host memory)
 };
 void launch_control_select(const ControlSelectArgs &a, hipStream_t s);
+// [EXTENSION] X11 MPPI sampling and softmax average (gv_mppi.hip; the arithmetic is gv_mppi.hpp's).  The configuration,
+// the seed and the iteration travel by value; the nominal is read when the kernel runs.
+struct MppiSampleArgs {
+  gv_mppi_config cfg;
+  int32_t C;                    // floats per step of the motion model in force
+  int32_t K, P;
+  uint64_t seed, iteration;
+  bool shift;                   // GV_MPPI_SHIFT
+  const float *nominal;         // P * C (device)
+  float *controls;              // K * P * C (device)
+};
+void launch_mppi_sample(const MppiSampleArgs &a, hipStream_t s);
+// The two launches of the average.  `result` and `totals` are what k_control_select left in device memory; the *_out
+// pointers are device views of pinned host memory, or null (the caller then enqueues a copy command).
+struct MppiAverageArgs {
+  double lambda;
+  int32_t K, J;                 // trajectories, columns P * C
+  int32_t rows, tile;           // mppi_chunk_rows(K, J), mppi_tile_cols(J)
+  const float *controls;        // K * J (device)
+  const uint64_t *totals;       // K (device)
+  const gv_control_result *result;   // one record (device)
+  double *partial;              // chunks * J sums, then chunks weights: chunks = ceil(K / rows)
+  float *nominal;               // J (device): rewritten unless no trajectory is admitted
+  uint64_t *totals_out;         // K, or null
+  gv_control_result *result_out;   // one record (16-byte aligned), or null
+  float *nominal_out;           // J, or null
+};
+void launch_mppi_average(const MppiAverageArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

@@ -49,6 +49,7 @@ ROLLOUT_DEVICE_CONTROLS = 1 << 0
 ROLLOUT_CONSTANT = 1 << 1
 CONTROL_KEEP_TOTALS = 1 << 0
 CONTROL_RESULT_DTYPE = np.dtype([("best", np.int32), ("n_valid", np.int32), ("best_total", np.uint64)])   # gv_control_result
+MPPI_SHIFT = 1 << 0
 
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
@@ -78,6 +79,9 @@ ABI_SYMBOLS = [
     "gv_score_nav_async", "gv_score_nav",
     "gv_set_motion_model", "gv_rollout_async", "gv_rollout", "gv_device_rollout", "gv_get_rollout", "gv_rollout_poses",
     "gv_control_step_async", "gv_control_step", "gv_control_select",
+    "gv_set_mppi", "gv_mppi_set_nominal", "gv_get_mppi_nominal", "gv_mppi_sample_async", "gv_mppi_sample",
+    "gv_device_controls", "gv_get_controls", "gv_mppi_update_async", "gv_mppi_update", "gv_mppi_cycle_async",
+    "gv_mppi_cycle", "gv_mppi_words", "gv_mppi_sample_controls", "gv_mppi_average",
 ]
 
 
@@ -155,6 +159,27 @@ class CriticWeights(C.Structure):
     sum, best); any nav weight non-zero makes the control step sample the distance field"""
     _fields_ = [("w_cost_sum", C.c_uint32), ("w_max_cost", C.c_uint32), ("w_nav_last", C.c_uint32),
                 ("w_nav_sum", C.c_uint32), ("w_nav_best", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MppiConfig(C.Structure):
+    """gv_mppi_config: per-channel noise sigma and clamp [u_min, u_max], the softmax temperature lambda in units of a
+    total"""
+    _fields_ = [("sigma", C.c_double * 3), ("u_min", C.c_float * 3), ("u_max", C.c_float * 3), ("lambda_", C.c_double),
+                ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, sigma, u_min=None, u_max=None, lambda_=1.0, flags=0):
+        """sigma, u_min, u_max: up to three values each (missing clamps are -inf / +inf, missing sigmas 0)"""
+        c = cls()
+        sigma = list(sigma)
+        lo = list(u_min) if u_min is not None else [-np.inf] * len(sigma)
+        hi = list(u_max) if u_max is not None else [np.inf] * len(sigma)
+        for i in range(3):
+            c.sigma[i] = float(sigma[i]) if i < len(sigma) else 0.0
+            c.u_min[i] = float(lo[i]) if i < len(lo) else -np.inf
+            c.u_max[i] = float(hi[i]) if i < len(hi) else np.inf
+        c.lambda_, c.flags = float(lambda_), int(flags)
+        return c
 
 
 class FrameDesc(C.Structure):
@@ -424,6 +449,43 @@ def control_select(weights, traj, nav=None, keep_totals=False):
     return (res[0], totals[:len(traj)]) if keep_totals else res[0]
 
 
+def mppi_words(seed, iteration, k, p):
+    """the four Philox4x32-10 words of pose (k, p): uint32 (4,) (host only; needs no GPU)"""
+    w = np.zeros(4, np.uint32)
+    rc = load().gv_mppi_words(C.c_uint64(seed), C.c_uint64(iteration), C.c_uint32(k), C.c_uint32(p), _ptr(w))
+    if rc:
+        raise GVError(rc, "gv_mppi_words")
+    return w
+
+
+def mppi_sample_controls(cfg, nominal, K, seed, iteration, shift=False):
+    """the float32 (K, P, C) controls an MppiConfig samples around the float32 (P, C) nominal: the library's own arithmetic
+    with the host's log, sin and cos (host only; needs no GPU)"""
+    nom = _f32(nominal)
+    assert nom.ndim == 2
+    P, Cn = nom.shape
+    out = np.zeros((K, P, Cn), np.float32)
+    rc = load().gv_mppi_sample_controls(C.byref(cfg), C.c_int32(Cn), _ptr(nom), C.c_int32(K), C.c_int32(P), C.c_uint64(seed),
+                                        C.c_uint64(iteration), C.c_uint32(MPPI_SHIFT if shift else 0), _ptr(out))
+    if rc:
+        raise GVError(rc, "gv_mppi_sample_controls")
+    return out
+
+
+def mppi_average(cfg, controls, totals, nominal):
+    """the float32 (P, C) softmax average of float32 (K, P, C) controls over uint64 (K,) totals (UINT64_MAX: rejected),
+    `nominal` when every trajectory is rejected: the sequential fp64 sums (host only; needs no GPU)"""
+    u, nom = _f32(controls), _f32(nominal)
+    t = np.ascontiguousarray(totals, np.uint64)
+    assert u.ndim == 3 and nom.shape == u.shape[1:] and len(t) == len(u)
+    out = np.zeros_like(nom)
+    rc = load().gv_mppi_average(C.byref(cfg), C.c_int32(u.shape[2]), _ptr(u), _ptr(t), C.c_int32(u.shape[0]),
+                                C.c_int32(u.shape[1]), _ptr(nom), _ptr(out))
+    if rc:
+        raise GVError(rc, "gv_mppi_average")
+    return out
+
+
 def shard_slice_words(words, world):
     lib = load()
     lib.gv_shard_slice_words.restype = C.c_int64
@@ -475,6 +537,7 @@ class GridVisionHIP:
         self.n = 0
         self._motion = None           # the MotionModel in force (set_motion_model)
         self._pending_controls = []   # host controls of rollout_async calls, kept alive until the stream is waited for
+        self._nominal_c = 0           # controls per step of the resident MPPI nominal (mppi_set_nominal)
 
     # ---- plumbing
     def _ck(self, rc, where):
@@ -885,6 +948,82 @@ class GridVisionHIP:
         self._ck(self._lib.gv_control_step(self._h, C.byref(weights), C.c_uint32(flags), _ptr(res), _ptr(totals)),
                  "gv_control_step")
         return (res[0], totals) if keep_totals else res[0]
+
+    # ---- [EXTENSION] MPPI sampling and softmax update
+    def set_mppi(self, cfg):
+        """the MppiConfig of the mppi_* calls that follow; set_mppi(None) turns it off"""
+        self._ck(self._lib.gv_set_mppi(self._h, C.byref(cfg) if cfg is not None else None), "gv_set_mppi")
+
+    def mppi_set_nominal(self, nominal):
+        """the resident nominal sequence: float32 (P, C), C the controls per step of the motion model in force"""
+        nom = _f32(nominal)
+        assert nom.ndim == 2 and (self._motion is None or nom.shape[1] == self._motion.n_controls), "nominal is (P, C)"
+        self._ck(self._lib.gv_mppi_set_nominal(self._h, _ptr(nom), C.c_int32(nom.shape[0])), "gv_mppi_set_nominal")
+        self._nominal_c = int(nom.shape[1])
+
+    def mppi_nominal(self):
+        """the resident nominal sequence: float32 (P, C)"""
+        P = C.c_int32()
+        self._ck(self._lib.gv_get_mppi_nominal(self._h, None, C.byref(P)), "gv_get_mppi_nominal")
+        out = np.empty((P.value, self._nominal_c), np.float32)
+        self._ck(self._lib.gv_get_mppi_nominal(self._h, _ptr(out), None), "gv_get_mppi_nominal")
+        return out
+
+    def mppi_sample(self, K, seed, iteration, shift=False, wait=True):
+        """sample K control sequences around the resident nominal into the handle's controls buffer (wait=False: enqueue
+        on stream() only)"""
+        fn, name = (self._lib.gv_mppi_sample, "gv_mppi_sample") if wait else (self._lib.gv_mppi_sample_async, "gv_mppi_sample_async")
+        self._ck(fn(self._h, C.c_int32(K), C.c_uint64(seed), C.c_uint64(iteration), C.c_uint32(MPPI_SHIFT if shift else 0)), name)
+
+    def device_controls(self):
+        """(device address, K, P, C) of the sampled controls, for rollout(..., device_ptr=)"""
+        p, K, P, Cn = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self._lib.gv_device_controls(self._h, C.byref(p), C.byref(K), C.byref(P), C.byref(Cn)), "gv_device_controls")
+        return p.value, K.value, P.value, Cn.value
+
+    def controls_array(self):
+        """the sampled controls: float32 (K, P, C)"""
+        _, K, P, Cn = self.device_controls()
+        out = np.empty((K, P, Cn), np.float32)
+        self._ck(self._lib.gv_get_controls(self._h, _ptr(out)), "gv_get_controls")
+        return out
+
+    def mppi_update_async(self, weights, result, totals=None, nominal_out=None):
+        """enqueue on stream(): result a CONTROL_RESULT_DTYPE array of 1, totals None or a uint64 array of K, nominal_out
+        None or a float32 array of P * C; all complete after synchronize()"""
+        flags = CONTROL_KEEP_TOTALS if totals is not None else 0
+        self._ck(self._lib.gv_mppi_update_async(self._h, C.byref(weights), C.c_uint32(flags), _ptr(result), _ptr(totals),
+                                                _ptr(nominal_out)), "gv_mppi_update_async")
+
+    def mppi_update(self, weights):
+        """score the resident rollout as control_step does and replace the resident nominal by the softmax average of the
+        sampled controls.  Returns (CONTROL_RESULT_DTYPE record, uint64 (K,) totals, float32 (P, C) new nominal)."""
+        _, K, P, Cn = self.device_controls()
+        res, totals, nom = np.zeros(1, CONTROL_RESULT_DTYPE), np.zeros(max(K, 1), np.uint64), np.zeros((P, Cn), np.float32)
+        self._ck(self._lib.gv_mppi_update(self._h, C.byref(weights), C.c_uint32(CONTROL_KEEP_TOTALS), _ptr(res), _ptr(totals),
+                                          _ptr(nom)), "gv_mppi_update")
+        return res[0], totals[:K], nom
+
+    def mppi_cycle_async(self, start, K, seed, iteration, weights, result, totals=None, nominal_out=None, shift=False):
+        """mppi_sample + rollout of the sampled controls + mppi_update enqueued on stream() without a wait"""
+        s = (C.c_double * 3)(*[float(v) for v in start])
+        flags = CONTROL_KEEP_TOTALS if totals is not None else 0
+        self._ck(self._lib.gv_mppi_cycle_async(self._h, s, C.c_int32(K), C.c_uint64(seed), C.c_uint64(iteration),
+                                               C.c_uint32(MPPI_SHIFT if shift else 0), C.byref(weights), C.c_uint32(flags),
+                                               _ptr(result), _ptr(totals), _ptr(nominal_out)), "gv_mppi_cycle_async")
+
+    def mppi_cycle(self, start, K, seed, iteration, weights, shift=False):
+        """one MPPI iteration from the resident nominal to the next one, and the wait.  Returns (CONTROL_RESULT_DTYPE
+        record, uint64 (K,) totals, float32 (P, C) new nominal)."""
+        P = C.c_int32()
+        self._ck(self._lib.gv_get_mppi_nominal(self._h, None, C.byref(P)), "gv_get_mppi_nominal")
+        res, totals = np.zeros(1, CONTROL_RESULT_DTYPE), np.zeros(max(K, 1), np.uint64)
+        nom = np.zeros((P.value, self._nominal_c), np.float32)
+        s = (C.c_double * 3)(*[float(v) for v in start])
+        self._ck(self._lib.gv_mppi_cycle(self._h, s, C.c_int32(K), C.c_uint64(seed), C.c_uint64(iteration),
+                                         C.c_uint32(MPPI_SHIFT if shift else 0), C.byref(weights), C.c_uint32(CONTROL_KEEP_TOTALS),
+                                         _ptr(res), _ptr(totals), _ptr(nom)), "gv_mppi_cycle")
+        return res[0], totals[:K], nom
 
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):

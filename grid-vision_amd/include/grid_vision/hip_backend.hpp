@@ -299,6 +299,27 @@ public:
               ctx_.handle(), "gv_control_step");
     return r;
   }
+  // [EXTENSION] X11 MPPI with its two ends on the device: configure once, give the first nominal sequence
+  // (nominal[P * C], C of the motion model in force), then one mppiCycle() per iteration: K control sequences sampled
+  // around the resident nominal, rolled out, scored and selected as controlStep() does, and the nominal replaced by
+  // their softmax average, which the call returns.  Synchronous, like controlStep().
+  void setMppi(const gv_mppi_config &c) { gv::check(gv_set_mppi(ctx_.handle(), &c), ctx_.handle(), "gv_set_mppi"); }
+  void setMppiNominal(const std::vector<float> &nominal, int32_t P)
+  {
+    gv::check(gv_mppi_set_nominal(ctx_.handle(), nominal.data(), P), ctx_.handle(), "gv_mppi_set_nominal");
+    nominal_floats_ = nominal.size();
+  }
+  std::vector<float> mppiCycle(const double start[3], int32_t K, uint64_t seed, uint64_t iteration, const gv_critic_weights &w,
+                               gv_control_result *result = nullptr, bool shift = false)
+  {
+    gv_control_result r{};
+    std::vector<float> nominal(nominal_floats_);
+    gv::check(gv_mppi_cycle(ctx_.handle(), start, K, seed, iteration, shift ? (uint32_t)GV_MPPI_SHIFT : 0u, &w, 0u, &r, nullptr,
+                            nominal.data()),
+              ctx_.handle(), "gv_mppi_cycle");
+    if (result) *result = r;
+    return nominal;
+  }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {
@@ -318,6 +339,7 @@ public:
 private:
   GridVisionContext &ctx_;
   size_t cells_ = 0;
+  size_t nominal_floats_ = 0;   // P * C of the nominal given to setMppiNominal
 };
 
 namespace cloud_detections {

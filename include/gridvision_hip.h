@@ -653,6 +653,99 @@ int gv_control_step(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_
 int gv_control_select(const gv_critic_weights *w, const gv_traj_score *traj, const gv_nav_score *nav, int32_t K,
                       gv_control_result *result, uint64_t *totals /* may be NULL */);
 
+/* ------------------------------------- [EXTENSION] MPPI sampling and softmax update (planner) -- */
+/* X11.  The two ends of an MPPI iteration that X10 left with the caller: sampling the K x P x C controls around a
+ * nominal sequence, and the softmax average of them over the totals that becomes the next nominal sequence.  Both run on
+ * the device over buffers of the handle's own, so one iteration takes a seed and 16 bytes in and gives P x C floats
+ * back.  The reference has no such step; this text is its definition, modelled on nav2's mppi::Optimizer (its control-cost
+ * term, coloured noise and acceleration limits are not part of it).
+ *
+ * Configuration (gv_mppi_config).  sigma[c] the standard deviation of channel c, [u_min[c], u_max[c]] its clamp, lambda
+ *   the temperature in units of a total.  gv_set_mppi is handle configuration like gv_set_footprint: no device work,
+ *   kept through gv_reset, gv_set_log_odds and gv_grid_move; NULL turns it off (the state after gv_create); every call
+ *   carries the configuration in force when it is enqueued.  GV_ERR_BAD_ARG, configuration unchanged, for a null handle,
+ *   a sigma that is not finite or < 0, a NaN clamp or u_min > u_max (+-inf allowed), lambda not finite or not > 0, or
+ *   flags other than 0.  gv_set_mppi checks all three channels, the host twins below the first C.
+ * Nominal.  nominal[P][C] float32, C from the motion model in force (X10), in a buffer of the handle's own that remembers
+ *   its P and C.  gv_mppi_set_nominal copies host values (all finite, P in 1..4096, else GV_ERR_BAD_ARG) and returns when
+ *   the caller's array is free; GV_ERR_STATE without a motion model.  gv_get_mppi_nominal is a synchronous read-back of
+ *   P * C floats (out may be NULL to ask for P alone; GV_ERR_STATE before the first gv_mppi_set_nominal).  A later
+ *   sampling or cycle call under a model with another C returns GV_ERR_STATE.  The nominal does not depend on the map:
+ *   gv_reset keeps it.
+ * Sampling.  Per (k, p), every operation one fp64 operation in exactly this order, never contracted:
+ *     r[0..3] = Philox4x32-10(counter = (k, p, iteration_lo, iteration_hi), key = (seed_lo, seed_hi))
+ *                 -- the Random123 function: multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and
+ *                    0xBB67AE85, ten rounds; one call serves one pose, no state is carried
+ *     u_i = ((double)r[i] + 0.5) * 2^-32                       -- never 0 or 1
+ *     R = sqrt(-2.0 * log(u_0));  A = 6.283185307179586 * u_1;  z_0 = R * cos(A);  z_1 = R * sin(A)
+ *     z_2 = the cosine branch of the same text on (u_2, u_3)   -- OMNI only
+ *     pn = p, with GV_MPPI_SHIFT pn = min(p + 1, P - 1)         -- sample around the nominal advanced by one step
+ *     v = (double)nominal[pn][c]                     for k == 0: trajectory 0 is the nominal itself
+ *     v = (double)nominal[pn][c] + sigma[c] * z_c    for k >= 1; DIFF reads z_0, z_1 for (v, w), OMNI z_0, z_1, z_2
+ *     f = (float)v;  f = f < u_min[c] ? u_min[c] : f;  f = f > u_max[c] ? u_max[c] : f;  controls[k][p][c] = f
+ *   On the device log, sin and cos are the device library's, in gv_mppi_sample_controls the C library's; the two may
+ *   differ in the last bit, which reaches a float32 control only near a rounding midpoint, as for X10's sincos.
+ *   gv_mppi_sample_async enqueues one kernel on gv_stream(h) that reads the resident nominal when it runs (behind an
+ *   update enqueued before it) and writes controls[K][P][C], the layout gv_rollout reads with
+ *   GV_ROLLOUT_DEVICE_CONTROLS, into a buffer of the handle's own.  Limits as for the rollout: K in 0..2^20,
+ *   K * P <= 2^24, K == 0 a successful no-op.  GV_ERR_BAD_ARG for a null handle, K out of range or flags other than
+ *   GV_MPPI_SHIFT; GV_ERR_STATE without a configuration, a motion model or a nominal, or when the model's C is not the
+ *   nominal's.  gv_device_controls gives the device pointer and K, P, C of the last sampling (any of the three may be
+ *   NULL); the pointer stays valid until gv_destroy or a larger sampling -- IT MAY CHANGE WHEN THE BUFFER GROWS, like
+ *   gv_device_rollout's.  gv_get_controls is a synchronous read-back of K * P * C floats.  Both return GV_ERR_STATE
+ *   before the first sampling.
+ * Update.  gv_mppi_update_async scores the resident rollout exactly as gv_control_step_async does -- the same samplers,
+ *   record buffers, combine and selection; result and totals are byte for byte what gv_control_step returns on that
+ *   rollout -- and then, over the admitted trajectories k (none admitted: the nominal is unchanged),
+ *     x_k = (double)(total_k - best_total)        -- an exact uint64 difference
+ *     e_k = exp(-(x_k / lambda));   S = sum e_k;   N[p][c] = sum e_k * (double)controls[k][p][c]
+ *     nominal[p][c] = (float)(N[p][c] / S)        -- S >= 1: the best trajectory contributes e = 1
+ *   The sums are fp64, in an order fixed by (K, P, C) alone: no floating-point atomics, the same call on the same bytes
+ *   gives the same bytes.  gv_mppi_average adds in index order, so the device may differ from it by the reordering of a
+ *   K-term fp64 sum.  nominal_out (P * C floats, may be NULL) follows the rules of result and totals: pinned memory
+ *   (nominal_out and totals aligned to 8 bytes, result to 16) is written by a kernel, anything else by a copy command
+ *   behind it.  GV_ERR_BAD_ARG as for gv_control_step_async.  GV_ERR_STATE without a configuration, a footprint, a
+ *   costmap, a field when a nav weight is set, a rollout, sampled controls of the rollout's K and P, a nominal of that P
+ *   and the controls' C, and with a communicator of more than one rank.
+ *   gv_mppi_cycle_async is gv_mppi_sample_async + gv_rollout_async on the sampled controls + gv_mppi_update_async, all on
+ *   gv_stream(h) without a host wait; every argument and state rule is checked before the first of them is enqueued, and
+ *   the results equal the three calls' by bytes.  The synchronous forms add the wait.  All of these are ordered and
+ *   allowed like gv_control_step_async, also between gv_tick_enqueue and gv_tick_wait.
+ *   gv_mppi_words, gv_mppi_sample_controls and gv_mppi_average are host only and take no handle: the same arithmetic
+ *   text compiled for the host (C is 2 or 3; the rollout's limits; in gv_mppi_average a total of UINT64_MAX marks a
+ *   rejected trajectory, and nominal_in is copied to nominal_out when every trajectory is). */
+typedef struct {
+  double sigma[3];             /* per control channel, finite, >= 0; the first C are read */
+  float u_min[3], u_max[3];    /* clamp, u_min <= u_max, +-inf allowed, no NaN            */
+  double lambda;               /* temperature in units of a total, finite, > 0            */
+  uint32_t flags;              /* 0                                                       */
+} gv_mppi_config;
+enum {
+  GV_MPPI_SHIFT = 1 << 0   /* sample around the nominal advanced by one step */
+};
+int gv_set_mppi(gv_handle h, const gv_mppi_config *cfg);
+int gv_mppi_set_nominal(gv_handle h, const float *nominal, int32_t P);
+int gv_get_mppi_nominal(gv_handle h, float *out /* may be NULL */, int32_t *P /* may be NULL */);
+int gv_mppi_sample_async(gv_handle h, int32_t K, uint64_t seed, uint64_t iteration, uint32_t flags);
+int gv_mppi_sample(gv_handle h, int32_t K, uint64_t seed, uint64_t iteration, uint32_t flags);
+int gv_device_controls(gv_handle h, float **controls, int32_t *K, int32_t *P, int32_t *C);
+int gv_get_controls(gv_handle h, float *out);
+int gv_mppi_update_async(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result,
+                         uint64_t *totals, float *nominal_out /* may be NULL */);
+int gv_mppi_update(gv_handle h, const gv_critic_weights *w, uint32_t flags, gv_control_result *result, uint64_t *totals,
+                   float *nominal_out /* may be NULL */);
+int gv_mppi_cycle_async(gv_handle h, const double start[3], int32_t K, uint64_t seed, uint64_t iteration,
+                        uint32_t sample_flags, const gv_critic_weights *w, uint32_t flags, gv_control_result *result,
+                        uint64_t *totals, float *nominal_out /* may be NULL */);
+int gv_mppi_cycle(gv_handle h, const double start[3], int32_t K, uint64_t seed, uint64_t iteration, uint32_t sample_flags,
+                  const gv_critic_weights *w, uint32_t flags, gv_control_result *result, uint64_t *totals,
+                  float *nominal_out /* may be NULL */);
+int gv_mppi_words(uint64_t seed, uint64_t iteration, uint32_t k, uint32_t p, uint32_t words[4]);
+int gv_mppi_sample_controls(const gv_mppi_config *cfg, int32_t C, const float *nominal, int32_t K, int32_t P, uint64_t seed,
+                            uint64_t iteration, uint32_t flags, float *controls_out);
+int gv_mppi_average(const gv_mppi_config *cfg, int32_t C, const float *controls, const uint64_t *totals, int32_t K,
+                    int32_t P, const float *nominal_in, float *nominal_out);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
