@@ -6,6 +6,8 @@
 //   [EXTENSION] X10 the rollout that makes such trajectories on the device and the control step that scores the resident
 //                   rollout with X7 and X9 and selects (gv_set_motion_model, gv_rollout*, gv_control_step*),
 //   [EXTENSION] X11 MPPI's two ends around them: sampling the controls and the softmax average (gv_set_mppi, gv_mppi_*).
+//   [EXTENSION] X12 rate and turning-radius limits on those samples and the control cost in the average
+//                   (gv_set_mppi_limits, gv_mppi_constrain, gv_*mppi_control_costs, gv_mppi_average_cc).
 // The kernels are gv_inflate.hip, gv_trajscore.hip, gv_navfield.hip (which also argues why the rounds end at the
 // exact field), gv_rollout.hip and gv_mppi.hip.  What the two samplers do alike, and what a control step and an MPPI
 // update enqueue alike, is written once, in front of the entry points.
@@ -168,7 +170,16 @@ bool mppi_shape_ok(int32_t K, int32_t P)
   return P >= 1 && P <= 4096 && K >= 0 && K <= (1 << 20) && (int64_t)K * (int64_t)P <= (int64_t)(1 << 24);
 }
 
-// What a sampling refuses with GV_ERR_STATE: no configuration, no motion model, no nominal, a nominal of another C.
+// X12: what gv_set_mppi_limits and the host twins check alike (all three channels)
+bool mppi_limits_valid(const gv_mppi_limits &l)
+{
+  for (int i = 0; i < 3; ++i)
+    if (!(l.rate_up[i] >= 0.0) || !(l.rate_down[i] >= 0.0)) return false;   // NaN lands here
+  return std::isfinite(l.min_turn_radius) && l.min_turn_radius >= 0.0 && std::isfinite(l.gamma) && l.gamma >= 0.0 && l.flags == 0u;
+}
+
+// What a sampling refuses with GV_ERR_STATE: no configuration, no motion model, no nominal, a nominal of another C,
+// a turning radius under a model that is not DIFF.
 int mppi_sample_refused(gv_context *h, const char *call)
 {
   const gv_context::Mppi &m = h->mppi;
@@ -176,7 +187,9 @@ int mppi_sample_refused(gv_context *h, const char *call)
                     : !h->roll.set ? "no motion model set (gv_set_motion_model)"
                     : !m.have_nominal ? "no nominal sequence (gv_mppi_set_nominal)"
                     : motion_controls(h->roll.model.model) != m.C ? "the nominal sequence was set under a motion model with other controls per step"
-                                                                  : nullptr;
+                    : m.lim_set && m.lim.min_turn_radius > 0.0 && h->roll.model.model != GV_MOTION_DIFF
+                        ? "a minimum turning radius (gv_set_mppi_limits) needs GV_MOTION_DIFF"
+                        : nullptr;
   if (!why) return GV_OK;
   h->err = std::string(call) + ": " + why;
   return GV_ERR_STATE;
@@ -218,8 +231,17 @@ int mppi_enqueue_sample(gv_context *h, int32_t K, uint64_t seed, uint64_t iterat
   a.nominal = m.nominal;
   a.controls = m.controls;
   launch_mppi_sample(a, h->stream);
+  if (m.lim_set) {   // X12: the chain over what was just sampled, when it can change a control at all
+    MppiConstrainArgs c{};
+    c.chain = mppi_chain(m.lim, h->roll.model.dt);
+    c.C = m.C;
+    c.K = K; c.P = m.P;
+    c.controls = m.controls;
+    if (mppi_chain_active(c.chain, m.C)) launch_mppi_constrain(c, h->stream);
+  }
   GV_HIP(hipGetLastError());
   m.cK = K; m.cP = m.P; m.cC = m.C;
+  m.c_shift = a.shift;
   m.have_controls = true;
   return GV_OK;
 }
@@ -242,7 +264,30 @@ int mppi_enqueue_update(gv_context *h, const gv_critic_weights &w, uint32_t flag
   const size_t chunks = (size_t)((K + a.rows - 1) / a.rows);
   if ((rc = r.d_result.reserve(h, 1)) || (rc = r.d_totals.reserve(h, (size_t)K)) || (rc = m.partial.reserve(h, chunks * ((size_t)J + 1))))
     return rc;
+  const bool cc = m.lim_set && m.lim.gamma > 0.0;   // X12: the control cost joins the exponent
+  if (cc && ((rc = m.cost.reserve(h, 2 * (size_t)K)) || (rc = m.x_min.reserve(h, 1)))) return rc;
   if ((rc = enqueue_control_scores(h, w, r.d_result, r.d_totals))) return rc;
+  m.have_costs = false;
+  if (cc) {
+    MppiCostArgs c{};
+    for (int i = 0; i < 3; ++i) c.qc[i] = mppi_cost_scale(m.lim.gamma, m.cfg.sigma[i]);
+    c.C = m.C;
+    c.K = K; c.P = m.P;
+    c.shift = m.c_shift;
+    c.nominal = m.nominal;
+    c.controls = m.controls;
+    c.totals = r.d_totals;
+    c.result = r.d_result;
+    c.g = m.cost;
+    c.x = m.cost.get() + K;
+    c.x_min_key = m.x_min;
+    GV_HIP(hipMemsetAsync(m.x_min.get(), 0xFF, sizeof(uint64_t), h->stream));
+    launch_mppi_control_cost(c, h->stream);
+    a.x = c.x;
+    a.x_min_key = c.x_min_key;
+    m.costK = K;
+    m.have_costs = true;
+  }
   a.controls = m.controls;
   a.totals = r.d_totals;
   a.result = r.d_result;
@@ -915,6 +960,78 @@ int gv_mppi_sample_controls(const gv_mppi_config *cfg, int32_t C, const float *n
 int gv_mppi_average(const gv_mppi_config *cfg, int32_t C, const float *controls, const uint64_t *totals, int32_t K,
                     int32_t P, const float *nominal_in, float *nominal_out)
 {
+  return gv_mppi_average_cc(cfg, C, controls, totals, nullptr, K, P, nominal_in, nominal_out);
+}
+
+// ---- [EXTENSION] X12: limits on the samples, control cost ----
+// handle configuration only, like gv_set_mppi
+int gv_set_mppi_limits(gv_handle h, const gv_mppi_limits *lim)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  if (!lim) {
+    h->mppi.lim_set = false;
+    return GV_OK;
+  }
+  if (!mppi_limits_valid(*lim)) return GV_ERR_BAD_ARG;
+  h->mppi.lim = *lim;
+  h->mppi.lim_set = true;
+  return GV_OK;
+}
+
+int gv_get_mppi_control_costs(gv_handle h, double *out)
+{
+  if (!h || !out) return GV_ERR_BAD_ARG;
+  const gv_context::Mppi &m = h->mppi;
+  if (!m.have_costs) return GV_ERR_STATE;
+  return copy_out(h, out, m.cost, (size_t)m.costK * sizeof(double));
+}
+
+// host only: the chain of gv_mppi.hpp, trajectory after trajectory
+int gv_mppi_constrain(const gv_mppi_limits *lim, const gv_motion_model *m, float *controls, int32_t K, int32_t P)
+{
+  if (!lim || !m || !controls || !mppi_shape_ok(K, P) || !mppi_limits_valid(*lim) || !motion_model_valid(*m) ||
+      (lim->min_turn_radius > 0.0 && m->model != GV_MOTION_DIFF))
+    return GV_ERR_BAD_ARG;
+  const int32_t C = motion_controls(m->model);
+  const MppiChain L = mppi_chain(*lim, m->dt);
+  for (size_t k = 0; k < (size_t)K; ++k) {
+    float s[3] = {L.u_prev[0], L.u_prev[1], L.u_prev[2]};
+    float *u = controls + k * (size_t)P * (size_t)C;
+    for (size_t p = 0; p < (size_t)P; ++p) {
+      float q[3] = {0.0f, 0.0f, 0.0f};
+      for (int32_t c = 0; c < C; ++c) q[c] = u[p * (size_t)C + (size_t)c];
+      mppi_constrain_step(L, C, s, q);
+      for (int32_t c = 0; c < C; ++c) u[p * (size_t)C + (size_t)c] = q[c];
+    }
+  }
+  return GV_OK;
+}
+
+// host only: the 64 partial sums and the tree of gv_mppi.hpp
+int gv_mppi_control_costs(const gv_mppi_config *cfg, const gv_mppi_limits *lim, int32_t C, const float *controls,
+                          const float *nominal, int32_t K, int32_t P, uint32_t sample_flags, double *g_out)
+{
+  if (!cfg || !lim || (C != 2 && C != 3) || !controls || !nominal || !g_out || !mppi_shape_ok(K, P) ||
+      !mppi_config_valid(*cfg, C) || !mppi_limits_valid(*lim) || (sample_flags & ~(uint32_t)GV_MPPI_SHIFT) != 0)
+    return GV_ERR_BAD_ARG;
+  double qc[3] = {0.0, 0.0, 0.0};
+  for (int32_t c = 0; c < C; ++c) qc[c] = mppi_cost_scale(lim->gamma, cfg->sigma[c]);
+  const bool shift = (sample_flags & GV_MPPI_SHIFT) != 0;
+  const size_t J = (size_t)P * (size_t)C;
+  for (size_t k = 0; k < (size_t)K; ++k) {
+    double a[kMppiCostLanes];
+    for (int32_t l = 0; l < kMppiCostLanes; ++l) a[l] = mppi_cost_lane(qc, C, nominal, P, shift, controls + k * J, l);
+    for (int32_t w = kMppiCostLanes / 2; w >= 1; w /= 2)
+      for (int32_t l = 0; l < w; ++l) a[l] = a[l] + a[l + w];
+    g_out[k] = a[0];
+  }
+  return GV_OK;
+}
+
+// host only, sums in index order.  control_costs null: x_k is the totals' difference alone, gv_mppi_average.
+int gv_mppi_average_cc(const gv_mppi_config *cfg, int32_t C, const float *controls, const uint64_t *totals,
+                       const double *control_costs, int32_t K, int32_t P, const float *nominal_in, float *nominal_out)
+{
   gv_context *h = nullptr;
   if (!cfg || (C != 2 && C != 3) || !controls || !totals || !nominal_in || !nominal_out || !mppi_shape_ok(K, P) ||
       !mppi_config_valid(*cfg, C))
@@ -929,11 +1046,27 @@ int gv_mppi_average(const gv_mppi_config *cfg, int32_t C, const float *controls,
   }
   std::vector<double> e((size_t)K, -1.0);
   double S = 0.0;
-  for (int32_t k = 0; k < K; ++k)
-    if (totals[k] != UINT64_MAX) {
-      e[(size_t)k] = mppi_weight(totals[k], best, cfg->lambda);
-      S = S + e[(size_t)k];
-    }
+  if (control_costs) {
+    bool first = true;
+    double xm = 0.0;
+    for (int32_t k = 0; k < K; ++k)
+      if (totals[k] != UINT64_MAX) {
+        const double x = mppi_cost_x(totals[k], best, control_costs[k]);
+        if (first || x < xm) xm = x;
+        first = false;
+      }
+    for (int32_t k = 0; k < K; ++k)
+      if (totals[k] != UINT64_MAX) {
+        e[(size_t)k] = mppi_weight_cc(mppi_cost_x(totals[k], best, control_costs[k]), xm, cfg->lambda);
+        S = S + e[(size_t)k];
+      }
+  } else {
+    for (int32_t k = 0; k < K; ++k)
+      if (totals[k] != UINT64_MAX) {
+        e[(size_t)k] = mppi_weight(totals[k], best, cfg->lambda);
+        S = S + e[(size_t)k];
+      }
+  }
   for (size_t j = 0; j < J; ++j) {
     double N = 0.0;
     for (size_t k = 0; k < (size_t)K; ++k)

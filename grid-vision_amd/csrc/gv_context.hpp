@@ -401,6 +401,14 @@ struct __attribute__((visibility("hidden"))) gv_context {
     int32_t cK = 0, cP = 0, cC = 0;         // of the last sampling
     bool have_controls = false;             // a sampling since gv_create
     DevBuf<double> partial;                 // chunks * (P * C + 1)
+    // [EXTENSION] X12 (gv_set_mppi_limits): handle state like cfg, copied into the kernel arguments at enqueue
+    bool lim_set = false;                   // limits are in force
+    gv_mppi_limits lim{};
+    bool c_shift = false;                   // the last sampling's GV_MPPI_SHIFT, next to cK / cP / cC
+    DevBuf<double> cost;                    // g[K], then x[K]
+    DevBuf<uint64_t> x_min;                 // mppi_min_key of the smallest admitted x
+    int32_t costK = 0;                      // of the last update with gamma > 0
+    bool have_costs = false;                // the last update ran with gamma > 0
   } mppi;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;

@@ -212,8 +212,34 @@ struct MppiAverageArgs {
   uint64_t *totals_out;         // K, or null
   gv_control_result *result_out;   // one record (16-byte aligned), or null
   float *nominal_out;           // J, or null
+  const double *x;              // [EXTENSION] X12, with gamma > 0: x_k of the admitted (K, device), else null
+  const uint64_t *x_min_key;    // ... and mppi_min_key of their minimum (device), else null
 };
 void launch_mppi_average(const MppiAverageArgs &a, hipStream_t s);
+// [EXTENSION] X12 the chain over the sampled controls, in place, behind k_mppi_sample (gv_mppi.hip).
+struct MppiConstrainArgs {
+  MppiChain chain;
+  int32_t C;
+  int32_t K, P;
+  float *controls;              // K * P * C (device)
+};
+void launch_mppi_constrain(const MppiConstrainArgs &a, hipStream_t s);
+// [EXTENSION] X12 the control cost of every trajectory and the minimum of x over the admitted, behind k_control_select.
+// The caller clears *x_min_key to all ones on the stream in front of the launch.
+struct MppiCostArgs {
+  double qc[3];                 // mppi_cost_scale per channel
+  int32_t C;
+  int32_t K, P;
+  bool shift;                   // the GV_MPPI_SHIFT of the sampling that made the controls
+  const float *nominal;         // P * C (device)
+  const float *controls;        // K * P * C (device)
+  const uint64_t *totals;       // K (device)
+  const gv_control_result *result;   // one record (device)
+  double *g;                    // K (device)
+  double *x;                    // K (device): written for the admitted
+  uint64_t *x_min_key;          // one (device)
+};
+void launch_mppi_control_cost(const MppiCostArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

@@ -3,7 +3,9 @@
 //   philox4x32_10    the Random123 counter function: four random words of (counter, key), no state;
 //   mppi_sample      one pose's controls: the words of (k, p, iteration | seed), Box-Muller, the nominal step, the clamp;
 //   mppi_weight      one trajectory's softmax weight from its total and the best total;
-//   mppi_chunk_rows, mppi_tile_cols   the fixed shape of the device's two-stage average, a function of (K, P * C) alone.
+//   mppi_chunk_rows, mppi_tile_cols   the fixed shape of the device's two-stage average, a function of (K, P * C) alone;
+//   [EXTENSION] X12: mppi_chain, mppi_constrain_step   the rate and turning-radius limits on a sampled sequence (float32);
+//   mppi_cost_lane, mppi_cost_x, mppi_weight_cc, mppi_min_key   the control cost and the weights with it.
 // Every operation is one fp64 operation in the header's order (include/gridvision_hip.h has the definition); the build
 // never contracts (-ffp-contract=off).  log, sin, cos and exp are the device library's on the device and the C library's
 // on the host.
@@ -76,6 +78,96 @@ GV_HD double mppi_weight(uint64_t total, uint64_t best_total, double lambda)
 {
   const double x = (double)(total - best_total);
   return exp(-(x / lambda));
+}
+
+// ---- [EXTENSION] X12: limits on the sampled controls and the control-cost term (gv_set_mppi_limits).
+// What a sampling makes of a gv_mppi_limits with the model's dt, once per call on the host (MppiChain, gv_types.hpp).
+GV_HD MppiChain mppi_chain(const gv_mppi_limits &lim, double dt)
+{
+  MppiChain L;
+  for (int c = 0; c < 3; ++c) {
+    L.up[c] = (float)(lim.rate_up[c] * dt);
+    L.dn[c] = (float)(lim.rate_down[c] * dt);
+    L.u_prev[c] = lim.u_prev[c];
+  }
+  L.inv_r = lim.min_turn_radius > 0.0 ? (float)(1.0 / lim.min_turn_radius) : 0.0f;
+  return L;
+}
+
+// can the chain change a control of the first C channels at all?  (+inf rates both ways and no radius: it cannot)
+GV_HD bool mppi_chain_active(const MppiChain &L, int32_t C)
+{
+  bool on = L.inv_r > 0.0f;
+  for (int32_t c = 0; c < C; ++c) on = on || L.up[c] < INFINITY || L.dn[c] < INFINITY;
+  return on;
+}
+
+// One step of the chain: q holds f[p][0..C) and leaves as controls[k][p][0..C); s is the step before it (u_prev in
+// front of step 0; NaN: that channel is free) and leaves as q.  Every operation one float32 operation, no library call.
+GV_HD void mppi_constrain_step(const MppiChain &L, int32_t C, float *s, float *q)
+{
+  for (int32_t c = 0; c < 3; ++c) {   // a constant trip count: s and q stay in registers on the device
+    if (c < C) {
+      // "if s[c] is not NaN" needs no branch: from a NaN s both bounds are NaN, both compares false, q stays
+      const float lo = s[c] - L.dn[c];
+      const float hi = s[c] + L.up[c];
+      q[c] = q[c] < lo ? lo : q[c];
+      q[c] = q[c] > hi ? hi : q[c];
+    }
+  }
+  if (L.inv_r > 0.0f) {
+    const float b = fabsf(q[0]) * L.inv_r;
+    q[1] = q[1] < -b ? -b : q[1];
+    q[1] = q[1] > b ? b : q[1];
+  }
+  for (int32_t c = 0; c < 3; ++c)
+    if (c < C) s[c] = q[c];
+}
+
+// The control cost g_k is a sum of J = P * C terms in a fixed order: 64 partial sums a_l over j = l, l + 64, ..
+// (ascending), then the tree a_l += a_(l + w), w = 32 .. 1.  On the device lane l of a wavefront holds a_l.
+constexpr int kMppiCostLanes = 64;
+
+// q_c of the definition: gamma / sigma^2, 0 for a channel without noise
+GV_HD double mppi_cost_scale(double gamma, double sigma) { return sigma > 0.0 ? gamma / (sigma * sigma) : 0.0; }
+
+// term_j of trajectory row u ([P][C]) around the nominal the sampling read
+GV_HD double mppi_cost_term(const double qc[3], int32_t C, const float *nominal, int32_t P, bool shift, const float *u, int32_t j)
+{
+  const int32_t p = j / C, c = j - p * C;
+  int32_t pn = p;
+  if (shift) pn = pn + 1 < P - 1 ? pn + 1 : P - 1;
+  const double n = (double)nominal[(size_t)pn * (size_t)C + (size_t)c];
+  const double q = c == 0 ? qc[0] : c == 1 ? qc[1] : qc[2];
+  return q * (n * ((double)u[j] - n));
+}
+
+// a_l of the definition
+GV_HD double mppi_cost_lane(const double qc[3], int32_t C, const float *nominal, int32_t P, bool shift, const float *u, int32_t l)
+{
+  const int32_t J = P * C;
+  double a = 0.0;
+  for (int32_t j = l; j < J; j += kMppiCostLanes) a = a + mppi_cost_term(qc, C, nominal, P, shift, u, j);
+  return a;
+}
+
+// e_k with the control cost: x_k = (double)(total_k - best_total) + g_k, m the smallest x of the admitted
+GV_HD double mppi_cost_x(uint64_t total, uint64_t best_total, double g) { return (double)(total - best_total) + g; }
+GV_HD double mppi_weight_cc(double x, double m, double lambda) { return exp(-((x - m) / lambda)); }
+
+// An order-preserving 64-bit key of a double (no NaN): a < b as doubles implies key(a) < key(b) as unsigned integers
+// (-0 sorts below +0), so an integer minimum over keys is the minimum over the doubles, in any order.
+GV_HD uint64_t mppi_min_key(double x)
+{
+  union { double d; uint64_t u; } v;
+  v.d = x;
+  return (v.u >> 63) ? ~v.u : v.u | 0x8000000000000000ull;
+}
+GV_HD double mppi_min_unkey(uint64_t key)
+{
+  union { double d; uint64_t u; } v;
+  v.u = (key >> 63) ? key & 0x7FFFFFFFFFFFFFFFull : ~key;
+  return v.d;
 }
 
 // ---- the shape of the device's average (k_mppi_partial / k_mppi_finish), fixed by (K, J = P * C) alone.

@@ -88,6 +88,14 @@ GV_HD uint32_t nav_step(NavStep s, uint32_t v)
   return (int32_t)v >= s.obstacle_cost ? 0u : 1u + (uint32_t)s.cost_weight * v;
 }
 
+// [EXTENSION] X12 limits on MPPI's sampled controls (gv_set_mppi_limits) as the chain reads them: the largest step up
+// and down of a channel (rate * dt), the control in force before step 0 (NaN: free), 1 / min_turn_radius (0: none).
+struct MppiChain {
+  float up[3], dn[3];
+  float u_prev[3];
+  float inv_r;
+};
+
 // ---- sector ray stage (gv_raysector.hip): what the kernel and the host's plan (host::SectorPlan) size LDS by
 constexpr int kSecThreads = 512;   // 8 wavefronts per sector workgroup
 // Ends of a slope bucket: the first kSlots in the bucket's own row of a table, in arrival order; what a crowded bucket

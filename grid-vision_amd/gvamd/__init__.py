@@ -82,6 +82,7 @@ ABI_SYMBOLS = [
     "gv_set_mppi", "gv_mppi_set_nominal", "gv_get_mppi_nominal", "gv_mppi_sample_async", "gv_mppi_sample",
     "gv_device_controls", "gv_get_controls", "gv_mppi_update_async", "gv_mppi_update", "gv_mppi_cycle_async",
     "gv_mppi_cycle", "gv_mppi_words", "gv_mppi_sample_controls", "gv_mppi_average",
+    "gv_set_mppi_limits", "gv_mppi_constrain", "gv_get_mppi_control_costs", "gv_mppi_control_costs", "gv_mppi_average_cc",
 ]
 
 
@@ -180,6 +181,26 @@ class MppiConfig(C.Structure):
             c.u_max[i] = float(hi[i]) if i < len(hi) else np.inf
         c.lambda_, c.flags = float(lambda_), int(flags)
         return c
+
+
+class MppiLimits(C.Structure):
+    """gv_mppi_limits: per-channel rate limits per second (inf: none), the control in force before step 0 (NaN: free), the
+    minimum turning radius in metres (0: off) and the control-cost weight gamma (0: off)"""
+    _fields_ = [("rate_up", C.c_double * 3), ("rate_down", C.c_double * 3), ("u_prev", C.c_float * 3),
+                ("min_turn_radius", C.c_double), ("gamma", C.c_double), ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, rate_up=(), rate_down=(), u_prev=(), min_turn_radius=0.0, gamma=0.0, flags=0):
+        """rate_up, rate_down, u_prev: up to three values each (missing rates are +inf, missing u_prev NaN); of() alone
+        is the neutral struct that changes nothing"""
+        m = cls()
+        up, dn, prev = list(rate_up), list(rate_down), list(u_prev)
+        for i in range(3):
+            m.rate_up[i] = float(up[i]) if i < len(up) else np.inf
+            m.rate_down[i] = float(dn[i]) if i < len(dn) else np.inf
+            m.u_prev[i] = float(prev[i]) if i < len(prev) else np.nan
+        m.min_turn_radius, m.gamma, m.flags = float(min_turn_radius), float(gamma), int(flags)
+        return m
 
 
 class FrameDesc(C.Structure):
@@ -483,6 +504,45 @@ def mppi_average(cfg, controls, totals, nominal):
                                 C.c_int32(u.shape[1]), _ptr(nom), _ptr(out))
     if rc:
         raise GVError(rc, "gv_mppi_average")
+    return out
+
+
+def mppi_constrain(limits, model, controls):
+    """float32 (K, P, C) controls passed through the chain of an MppiLimits under a MotionModel (its dt and C): a new
+    array, the library's own arithmetic (host only; needs no GPU)"""
+    u = _f32(controls).copy()
+    assert u.ndim == 3 and u.shape[2] == model.n_controls
+    rc = load().gv_mppi_constrain(C.byref(limits), C.byref(model), _ptr(u), C.c_int32(u.shape[0]), C.c_int32(u.shape[1]))
+    if rc:
+        raise GVError(rc, "gv_mppi_constrain")
+    return u
+
+
+def mppi_control_costs(cfg, limits, controls, nominal, shift=False):
+    """the fp64 (K,) control costs g_k of float32 (K, P, C) controls around the float32 (P, C) nominal their sampling read
+    (shift: it had MPPI_SHIFT): the 64 partial sums and the tree of the header (host only; needs no GPU)"""
+    u, nom = _f32(controls), _f32(nominal)
+    assert u.ndim == 3 and nom.shape == u.shape[1:]
+    out = np.zeros(max(u.shape[0], 1), np.float64)
+    rc = load().gv_mppi_control_costs(C.byref(cfg), C.byref(limits), C.c_int32(u.shape[2]), _ptr(u), _ptr(nom),
+                                      C.c_int32(u.shape[0]), C.c_int32(u.shape[1]), C.c_uint32(MPPI_SHIFT if shift else 0), _ptr(out))
+    if rc:
+        raise GVError(rc, "gv_mppi_control_costs")
+    return out[:u.shape[0]]
+
+
+def mppi_average_cc(cfg, controls, totals, control_costs, nominal):
+    """mppi_average with the fp64 (K,) control costs in the exponent (None: mppi_average itself): the sequential fp64
+    sums (host only; needs no GPU)"""
+    u, nom = _f32(controls), _f32(nominal)
+    t = np.ascontiguousarray(totals, np.uint64)
+    g = np.ascontiguousarray(control_costs, np.float64) if control_costs is not None else None
+    assert u.ndim == 3 and nom.shape == u.shape[1:] and len(t) == len(u) and (g is None or len(g) == len(u))
+    out = np.zeros_like(nom)
+    rc = load().gv_mppi_average_cc(C.byref(cfg), C.c_int32(u.shape[2]), _ptr(u), _ptr(t), _ptr(g), C.c_int32(u.shape[0]),
+                                   C.c_int32(u.shape[1]), _ptr(nom), _ptr(out))
+    if rc:
+        raise GVError(rc, "gv_mppi_average_cc")
     return out
 
 
@@ -1024,6 +1084,16 @@ class GridVisionHIP:
                                          C.c_uint32(MPPI_SHIFT if shift else 0), C.byref(weights), C.c_uint32(CONTROL_KEEP_TOTALS),
                                          _ptr(res), _ptr(totals), _ptr(nom)), "gv_mppi_cycle")
         return res[0], totals[:K], nom
+
+    def set_mppi_limits(self, limits):
+        """the MppiLimits of the mppi_* calls that follow; set_mppi_limits(None) turns them off"""
+        self._ck(self._lib.gv_set_mppi_limits(self._h, C.byref(limits) if limits is not None else None), "gv_set_mppi_limits")
+
+    def mppi_control_costs(self):
+        """the fp64 (K,) control costs g_k of the last mppi_update / mppi_cycle that ran with gamma > 0"""
+        out = np.zeros(max(self.device_controls()[1], 1), np.float64)
+        self._ck(self._lib.gv_get_mppi_control_costs(self._h, _ptr(out)), "gv_get_mppi_control_costs")
+        return out[:self.device_controls()[1]]
 
     # ---- fused frame
     def _desc(self, flags, bboxes=None, poses=None, net=None):

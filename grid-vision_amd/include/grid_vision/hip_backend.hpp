@@ -320,6 +320,40 @@ public:
     if (result) *result = r;
     return nominal;
   }
+  // [EXTENSION] X12 rate and turning-radius limits on the sampled controls and the control-cost weight gamma of the
+  // mppiCycle() calls that follow: call it every control cycle with the measured velocity in u_prev.  A car-like base
+  // sets min_turn_radius under GV_MOTION_DIFF.  clearMppiLimits() turns them off.
+  void setMppiLimits(const gv_mppi_limits &l) { gv::check(gv_set_mppi_limits(ctx_.handle(), &l), ctx_.handle(), "gv_set_mppi_limits"); }
+  void clearMppiLimits() { gv::check(gv_set_mppi_limits(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_mppi_limits"); }
+  // the control costs g_k of the last mppiCycle() that ran with gamma > 0 (K values)
+  std::vector<double> mppiControlCosts(int32_t K) const
+  {
+    std::vector<double> g((size_t)K);
+    gv::check(gv_get_mppi_control_costs(ctx_.handle(), g.data()), ctx_.handle(), "gv_get_mppi_control_costs");
+    return g;
+  }
+  // the host twins (no handle): the chain over controls[K][P][C] in place, e.g. K = 1 for the command to execute; the
+  // control costs; the sequential average with them
+  static void mppiConstrain(const gv_mppi_limits &l, const gv_motion_model &m, std::vector<float> &controls, int32_t K, int32_t P)
+  {
+    gv::check(gv_mppi_constrain(&l, &m, controls.data(), K, P), nullptr, "gv_mppi_constrain");
+  }
+  static std::vector<double> mppiControlCostsHost(const gv_mppi_config &c, const gv_mppi_limits &l, int32_t C, const std::vector<float> &controls,
+                                                  const std::vector<float> &nominal, int32_t K, int32_t P, bool shift = false)
+  {
+    std::vector<double> g((size_t)K);
+    gv::check(gv_mppi_control_costs(&c, &l, C, controls.data(), nominal.data(), K, P, shift ? (uint32_t)GV_MPPI_SHIFT : 0u, g.data()), nullptr,
+              "gv_mppi_control_costs");
+    return g;
+  }
+  static std::vector<float> mppiAverageCc(const gv_mppi_config &c, int32_t C, const std::vector<float> &controls, const std::vector<uint64_t> &totals,
+                                          const std::vector<double> *costs, int32_t K, int32_t P, const std::vector<float> &nominal)
+  {
+    std::vector<float> out(nominal.size());
+    gv::check(gv_mppi_average_cc(&c, C, controls.data(), totals.data(), costs ? costs->data() : nullptr, K, P, nominal.data(), out.data()), nullptr,
+              "gv_mppi_average_cc");
+    return out;
+  }
   // GridMapRosConverter::toOccupancyGrid(map, "occupancy", 0, 1, msg)  grid_vision_node.cpp:270-271
   std::vector<int8_t> toOccupancyGrid(gv_grid_info *info = nullptr) const
   {

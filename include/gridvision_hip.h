@@ -657,8 +657,8 @@ int gv_control_select(const gv_critic_weights *w, const gv_traj_score *traj, con
 /* X11.  The two ends of an MPPI iteration that X10 left with the caller: sampling the K x P x C controls around a
  * nominal sequence, and the softmax average of them over the totals that becomes the next nominal sequence.  Both run on
  * the device over buffers of the handle's own, so one iteration takes a seed and 16 bytes in and gives P x C floats
- * back.  The reference has no such step; this text is its definition, modelled on nav2's mppi::Optimizer (its control-cost
- * term, coloured noise and acceleration limits are not part of it).
+ * back.  The reference has no such step; this text is its definition, modelled on nav2's mppi::Optimizer (coloured noise
+ * is not part of it; X12 below adds the limits on the samples and the control-cost term).
  *
  * Configuration (gv_mppi_config).  sigma[c] the standard deviation of channel c, [u_min[c], u_max[c]] its clamp, lambda
  *   the temperature in units of a total.  gv_set_mppi is handle configuration like gv_set_footprint: no device work,
@@ -745,6 +745,78 @@ int gv_mppi_sample_controls(const gv_mppi_config *cfg, int32_t C, const float *n
                             uint64_t iteration, uint32_t flags, float *controls_out);
 int gv_mppi_average(const gv_mppi_config *cfg, int32_t C, const float *controls, const uint64_t *totals, int32_t K,
                     int32_t P, const float *nominal_in, float *nominal_out);
+
+/* ------------------------- [EXTENSION] MPPI rate and turning-radius limits, control cost (planner) -- */
+/* X12.  What X11 left out of nav2's mppi::Optimizer, except coloured noise: limits on how fast a sampled control may
+ * change from one step to the next, a minimum turning radius for a car-like base, and the control-cost term in the
+ * exponent of the weights.  All three run on the device between the nominal and the next nominal; with no limits set
+ * (the state after gv_create) every X11 call gives the bytes it gave before.
+ *
+ * Configuration (gv_mppi_limits).  rate_up[c] / rate_down[c] the largest increase / decrease of control channel c per
+ *   SECOND; u_prev[c] the control in force before step 0 (the measured velocity; NaN: step 0 of that channel is free);
+ *   min_turn_radius in metres (0: off); gamma the control-cost weight in units of a total (0: off).
+ *   gv_set_mppi_limits is handle configuration like gv_set_mppi: no device work, kept through gv_reset,
+ *   gv_set_log_odds and gv_grid_move; NULL turns it off; every sampling, update and cycle carries the limits in force
+ *   when it is enqueued, by value; it is meant to be called every control cycle with the measured velocity.
+ *   GV_ERR_BAD_ARG, limits unchanged, for a null handle, a rate that is NaN or < 0 (+inf: none), a radius or gamma
+ *   that is negative or not finite, or flags other than 0; all three channels are checked.  A radius > 0 needs
+ *   GV_MOTION_DIFF: the sampling or cycle call that would use it under GV_MOTION_OMNI returns GV_ERR_STATE and
+ *   enqueues nothing (the setter cannot know the model a later call runs under).
+ * Constrained sampling.  Let f[p][c] be the X11 value of controls[k][p][c], the complete text above, clamp included
+ *   (trajectory 0: z = 0).  Once per call, with the model's dt:
+ *     up[c] = (float)(rate_up[c] * dt);  dn[c] = (float)(rate_down[c] * dt)
+ *     inv_r = min_turn_radius > 0 ? (float)(1.0 / min_turn_radius) : 0
+ *   Then per trajectory k, every operation one float32 operation in exactly this order, never contracted:
+ *     s[c] = u_prev[c]
+ *     for p = 0 .. P-1:
+ *       for c:  q[c] = f[p][c]
+ *               if s[c] is not NaN:  lo = s[c] - dn[c];  hi = s[c] + up[c]
+ *                                    q[c] = q[c] < lo ? lo : q[c];   q[c] = q[c] > hi ? hi : q[c]
+ *       if inv_r > 0:  b = fabsf(q[0]) * inv_r;  q[1] = q[1] < -b ? -b : q[1];  q[1] = q[1] > b ? b : q[1]
+ *       s = q;  controls[k][p][c] = q[c]
+ *   The limits are signed rates on the control value: rate_up bounds an increase of the value, rate_down a decrease,
+ *   whatever its sign.  nav2 tells accelerating from braking by the sign of v; THIS DEFINITION DOES NOT.  The radius is
+ *   applied behind the rate window and wins: where it binds, q[1] may lie outside [lo, hi].  Trajectory 0
+ *   is the constrained nominal; the rollout, the scorers and the average read the constrained controls.  Limits with
+ *   every rate +inf, every u_prev NaN and radius 0 change no byte.  The chain holds no library call, so the device
+ *   equals gv_mppi_constrain byte for byte given the same f.  The new nominal an update writes is a weighted mean of
+ *   constrained sequences; IT IS NOT PASSED THROUGH THE CHAIN AGAIN.  A caller who wants the executed command
+ *   constrained applies gv_mppi_constrain with K = 1; the next cycle's trajectory 0 is constrained anyway.
+ *   gv_mppi_constrain is host only: controls[K][P][C] in place, C from m->model, the rollout's limits on K and P;
+ *   GV_ERR_BAD_ARG for a null pointer, limits or a model that the setters refuse, or a radius > 0 under OMNI.
+ * Control cost.  Active when gamma > 0 (gamma == 0: the update is X11's text and bytes).  Over the resident controls
+ *   and the nominal the sampling read -- pn = p, or min(p + 1, P - 1) when the sampling that made the controls had
+ *   GV_MPPI_SHIFT (the handle remembers it) -- with J = P * C and j = p * C + c, in fp64, never contracted:
+ *     q_c    = sigma[c] > 0 ? gamma / (sigma[c] * sigma[c]) : 0.0
+ *     term_j = q_c * ((double)nominal[pn][c] * ((double)controls[k][p][c] - (double)nominal[pn][c]))
+ *     a_l    = 0.0;  a_l = a_l + term_j   for j = l, l + 64, l + 128, ..   (l = 0 .. 63, ascending j)
+ *     for w = 32, 16, 8, 4, 2, 1:  a_l = a_l + a_(l+w)   for l < w
+ *     g_k    = a_0
+ *   for every k, rejected or not.  Then, over the admitted trajectories,
+ *     x_k = (double)(total_k - best_total) + g_k;   m = min x_k;   e_k = exp(-((x_k - m) / lambda))
+ *   and S, N and the new nominal exactly as in X11, in the same order of sums.  The trajectory that attains m
+ *   contributes e = 1, so S >= 1.  result, best, best_total and totals remain the critics' alone, byte for byte what
+ *   gv_control_step returns.  With no trajectory admitted the nominal stays as it is (g is still written).
+ *   gv_get_mppi_control_costs is a synchronous read-back of the K values g_k of the last update; GV_ERR_STATE when
+ *   the last update ran without gamma > 0 (or none has run).  gv_mppi_control_costs (host only) is the same text:
+ *   the first C sigmas of cfg, lim->gamma, sample_flags 0 or GV_MPPI_SHIFT.  gv_mppi_average_cc (host only) is
+ *   gv_mppi_average with x_k and m as above, sums in index order; control_costs == NULL: gv_mppi_average itself. */
+typedef struct {
+  double rate_up[3], rate_down[3];  /* largest increase / decrease of control channel c per SECOND; >= 0, +inf = none, no NaN */
+  float  u_prev[3];                 /* the control in force before step 0 (the measured velocity); NaN = step 0 of that channel is free */
+  double min_turn_radius;           /* m; 0 = off; finite, >= 0; > 0 needs GV_MOTION_DIFF when a call uses it */
+  double gamma;                     /* control-cost weight, in units of a total; finite, >= 0; 0 = off */
+  uint32_t flags;                   /* 0 */
+} gv_mppi_limits;
+int gv_set_mppi_limits(gv_handle h, const gv_mppi_limits *lim);   /* NULL = off, the state after gv_create */
+int gv_mppi_constrain(const gv_mppi_limits *lim, const gv_motion_model *m, float *controls /* [K][P][C], in place */,
+                      int32_t K, int32_t P);
+int gv_get_mppi_control_costs(gv_handle h, double *out);
+int gv_mppi_control_costs(const gv_mppi_config *cfg, const gv_mppi_limits *lim, int32_t C, const float *controls,
+                          const float *nominal, int32_t K, int32_t P, uint32_t sample_flags, double *g_out);
+int gv_mppi_average_cc(const gv_mppi_config *cfg, int32_t C, const float *controls, const uint64_t *totals,
+                       const double *control_costs /* may be NULL: gv_mppi_average */, int32_t K, int32_t P,
+                       const float *nominal_in, float *nominal_out);
 
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,

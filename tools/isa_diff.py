@@ -6,9 +6,11 @@ lines that differ between any two builds of one text (the __hip_cuid_* symbol, .
 `identical` or the number of differing lines.  A file only one tree has is reported as such (a rename: compare it by
 hand with --pair).
 
-    python3 tools/isa_diff.py PARENT_TREE THIS_TREE [--pair OLD.hip=NEW.hip ...] [--keep DIR]
+    python3 tools/isa_diff.py PARENT_TREE THIS_TREE [--pair OLD.hip=NEW.hip ...] [--keep DIR] [--kernels FILE.hip ...]
 
-Exit status 0 when every compared file is identical."""
+--kernels FILE.hip: the file is meant to differ (it gained kernels, say); print each of its gv:: kernels as identical,
+differs, or only in one tree, by instruction lines.
+Exit status 0 when every compared file (but those named by --kernels) is identical."""
 from __future__ import annotations
 
 import argparse
@@ -48,12 +50,31 @@ def differing_lines(a: list, b: list) -> int:
                if ln[:1] in "+-" and not ln.startswith(("+++", "---")))
 
 
+def kernel_bodies(asm: list) -> dict:
+    """{symbol: its instruction lines} of every gv:: function of one file's assembly, comments dropped: what --kernels
+    compares when a file changed but one of its kernels must not have."""
+    out, cur = {}, None
+    for ln in asm:
+        m = re.match(r"^(_ZN2gv\w+):", ln)
+        if m:
+            cur = m.group(1)
+            out[cur] = []
+        elif cur is not None:
+            if ln.startswith(".Lfunc_end"):
+                cur = None
+            elif not ln.lstrip().startswith(";"):
+                out[cur].append(ln)
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("parent")
     ap.add_argument("this")
     ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW", help="a renamed file: parent's name = this tree's name")
     ap.add_argument("--keep", metavar="DIR", help="keep the assembly files there")
+    ap.add_argument("--kernels", action="append", default=[], metavar="FILE.hip",
+                    help="also compare this file kernel by kernel (its differing lines then do not count for the exit status)")
     a = ap.parse_args()
     ca, cb = csrc_of(a.parent), csrc_of(a.this)
     hips = lambda d: sorted(f for f in os.listdir(d) if f.endswith(".hip"))   # noqa: E731
@@ -75,9 +96,16 @@ def main() -> int:
     worst = 0
     for k, (o, n) in sorted(enumerate(pairs), key=lambda kp: kp[1][1]):
         d = differing_lines(asm[k], asm[len(pairs) + k])
-        worst = max(worst, d)
+        if n not in a.kernels:
+            worst = max(worst, d)
         name = n if o == n else o + " -> " + n
         print(f"{name:44s} {'identical' if d == 0 else str(d) + ' lines differ'}  ({len(asm[len(pairs) + k])} lines)")
+        if n in a.kernels:
+            ka, kb = kernel_bodies(asm[k]), kernel_bodies(asm[len(pairs) + k])
+            for sym in sorted(set(ka) | set(kb)):
+                what = ("only in the parent tree" if sym not in kb else "only in this tree" if sym not in ka
+                        else "identical" if ka[sym] == kb[sym] else "differs")
+                print(f"    {sym:60s} {what}  ({len(kb.get(sym, ka.get(sym)))} lines)")
     for f in fa:
         if f not in paired_a:
             print(f"{f:44s} only in the parent tree")

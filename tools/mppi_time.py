@@ -15,7 +15,14 @@ against gv_mppi_average over the device's own read-backs.
 Kernel times come from a separate run:
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/mppi_time.py
 and then `python tools/mppi_time.py --trace DIR` (no GPU), which prints the mean duration of the seven kernels per shape.
---out FILE appends what is printed."""
+--out FILE appends what is printed.
+
+--limits ([EXTENSION] X12) is the leg with gv_set_mppi_limits in force: rate limits on (v, w) from a measured velocity, a
+minimum turning radius and gamma > 0, so every cycle also dispatches k_mppi_constrain and k_mppi_control_cost (and one
+8-byte memset).  The same two figures per shape; the check is gv_mppi_average_cc over the device's own read-backs, the
+control costs included, and those against gv_mppi_control_costs by bytes.  The host yardstick has no such path and is
+left out, so with --limits (also behind --trace) every kernel is dispatched warmup + 1 + 2 n times per shape.  Without
+the flag the script is what it was and runs against a library that has no limits (tools/lib_ab.py's GV_LIB_AB)."""
 from __future__ import annotations
 
 import argparse
@@ -40,10 +47,13 @@ SIGMA, U_MIN, U_MAX, LAMBDA = (0.4, 0.35), (0.0, -1.0), (4.0, 1.0), 1000.0
 SEED = 42
 KERNELS = ["k_mppi_sample", "k_rollout", "k_score_trajectories", "k_score_nav", "k_control_select", "k_mppi_partial",
            "k_mppi_finish"]
+LIMIT_KERNELS = ["k_mppi_sample", "k_mppi_constrain", "k_rollout", "k_score_trajectories", "k_score_nav", "k_control_select",
+                 "k_mppi_control_cost", "k_mppi_partial", "k_mppi_finish"]
+RATE_UP, RATE_DOWN, U_PREV, RADIUS, GAMMA = (1.5, 0.8), (3.0, 0.8), (2.4, 0.0), 4.0, 30.0
 YARD = ("k_rollout", "k_score_trajectories", "k_score_nav", "k_control_select")   # the yardstick dispatches these too
 
 
-def run(n, warmup):
+def run(n, warmup, limits=False):
     import gvamd
     from gvamd import synth
     hip = common.load_hip()
@@ -60,6 +70,10 @@ def run(n, warmup):
     h.set_motion_model(gvamd.MotionModel(gvamd.MOTION_DIFF, DT, 0))
     cfg = gvamd.MppiConfig.of(SIGMA, U_MIN, U_MAX, LAMBDA)
     h.set_mppi(cfg)
+    lim = None
+    if limits:
+        lim = gvamd.MppiLimits.of(RATE_UP, RATE_DOWN, U_PREV, RADIUS, GAMMA)
+        h.set_mppi_limits(lim)
     w = gvamd.CriticWeights(*WEIGHTS, 0)
     lines = [f"goal field: {info['n_seeds_used']} seed used, {info['rounds']} rounds"]
     slower = []
@@ -93,11 +107,17 @@ def run(n, warmup):
         cycle()
         h.synchronize()
         got = nom_d.reshape(P, 2).copy()
-        want = gvamd.mppi_average(cfg, h.controls_array(), tot_d, before)
+        if limits:
+            g = h.mppi_control_costs()
+            assert g.tobytes() == gvamd.mppi_control_costs(cfg, lim, h.controls_array(), before).tobytes(), (K, P, "control costs")
+            want = gvamd.mppi_average_cc(cfg, h.controls_array(), tot_d, g, before)
+        else:
+            want = gvamd.mppi_average(cfg, h.controls_array(), tot_d, before)
         differ = int((got.view(np.uint32) != want.view(np.uint32)).sum())
         assert np.abs(got - want).max() <= 1e-6 * (1.0 + np.abs(want).max()), (K, P, "the device's average is off the host's")
         admitted = int(res_d["n_valid"][0])
-        yardstick()
+        if not limits:
+            yardstick()
         us = common.event_us_per_call(hip, h, n, cycle)
         h.synchronize()
         t0 = time.perf_counter()
@@ -105,6 +125,13 @@ def run(n, warmup):
             cycle()
             h.synchronize()
         wall = (time.perf_counter() - t0) / n * 1e6
+        if limits:
+            lines.append(f"{K:5d} x {P:2d}: {n} cycles, events {us:8.2f} us, cycle {wall:8.2f} us | limits and gamma on | {admitted} of {K} "
+                         f"admitted, nominal floats that differ from the host average {differ} of {got.size}")
+            print(lines[-1], flush=True)
+            for p in (pin_r, pin_t, pin_n, pin_u):
+                p.close()
+            continue
         t0 = time.perf_counter()
         for _ in range(n):
             yardstick()
@@ -125,18 +152,19 @@ def run(n, warmup):
     return lines, slower
 
 
-def kernel_times(trace_dir, n, warmup):
+def kernel_times(trace_dir, n, warmup, limits=False):
     """per shape: mean duration in us of the events loop's dispatches of each kernel from rocprofv3's kernel trace of one
     run of this script.  Per shape the cycle dispatches every kernel warmup + 1 + 2 n times (warm-up, the checked cycle,
     the events loop, the wall-clock loop); the yardstick dispatches four of them once behind the checked cycle and 2 n
     times at the end of the shape."""
-    d = common.kernel_durations(trace_dir, KERNELS)
+    kernels = LIMIT_KERNELS if limits else KERNELS
+    d = common.kernel_durations(trace_dir, kernels)
     own, extra = warmup + 1 + 2 * n, 1 + 2 * n
     lines = []
     for i, (K, P) in enumerate(SHAPES):
         parts = []
-        for k in KERNELS:
-            yard = k in YARD
+        for k in kernels:
+            yard = k in YARD and not limits
             first = i * (own + (extra if yard else 0)) + warmup + 1 + (1 if yard else 0)
             part = d[k][first:first + n]
             assert len(part) == n, (K, P, k, len(part), len(d[k]))
@@ -150,17 +178,18 @@ def main():
     ap.add_argument("--calls", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--trace", default=None, help="directory of a rocprofv3 --kernel-trace run of this script: print kernel times")
+    ap.add_argument("--limits", action="store_true", help="the leg with gv_set_mppi_limits (rates, radius, gamma) in force")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     slower = []
     if a.trace:
-        lines = ["per kernel (rocprofv3 --kernel-trace of the same script):"] + kernel_times(a.trace, a.calls, a.warmup)
+        lines = ["per kernel (rocprofv3 --kernel-trace of the same script):"] + kernel_times(a.trace, a.calls, a.warmup, a.limits)
         print("\n".join(lines), flush=True)
     else:
         head = ("per MPPI iteration (gv_mppi_cycle_async; %d cycles), 2000 x 2000 cells at 0.1 m, P1, rectangle footprint, goal "
-                "field, weights %s, sigma %s, lambda %g:" % (a.calls, WEIGHTS, SIGMA, LAMBDA))
+                "field, weights %s, sigma %s, lambda %g%s:" % (a.calls, WEIGHTS, SIGMA, LAMBDA, ", limits and gamma on" if a.limits else ""))
         print(head, flush=True)
-        lines, slower = run(a.calls, a.warmup)
+        lines, slower = run(a.calls, a.warmup, a.limits)
         lines = [head] + lines
     if a.out:
         common.append_out(a.out, lines)
