@@ -398,9 +398,11 @@ static int segment_ground_device(gv_context *h, double threshold, int32_t iterat
   return GV_OK;
 }
 
-int gv_segment_ground_plane(gv_handle h, double threshold, int32_t iterations, uint64_t seed, uint8_t *is_ground,
-                            float coeff[4], int64_t *n_inliers)
+// gv_segment_ground_plane; st: the state the call brings home anyway (handed on by gv_test_ransac_state only)
+static int segment_ground_plane_impl(gv_handle h, double threshold, int32_t iterations, uint64_t seed, uint8_t *is_ground,
+                                     float coeff[4], int64_t *n_inliers, RansacState &st)
 {
+  st = RansacState{};
   if (!h || !(threshold > 0.0) || iterations < 1 || iterations > 4096) return GV_ERR_BAD_ARG;
   if (!h->has_cl) return GV_ERR_TF;
   GV_TRY
@@ -409,7 +411,6 @@ int gv_segment_ground_plane(gv_handle h, double threshold, int32_t iterations, u
   if (coeff) coeff[0] = coeff[1] = coeff[2] = coeff[3] = 0.0f;
   if (n_inliers) *n_inliers = 0;
   if (is_ground && h->n) std::memset(is_ground, 0, h->n);
-  RansacState st;
   if ((rc = segment_ground_device(h, threshold, iterations, seed, st))) return rc;
   if (!st.best_count) return GV_OK;   // "Could not estimate a planar model" (:122-126)
   if (is_ground) {   // the caller asked for the per-point mask: the only O(N) transfer of this call
@@ -422,15 +423,23 @@ int gv_segment_ground_plane(gv_handle h, double threshold, int32_t iterations, u
   GV_CATCH
 }
 
-int gv_compute_bbox_pose_ground_removed(gv_handle h, const gv_bbox *bboxes, int32_t nb, gv_lshape_pose *poses_out,
-                                        uint8_t *valid, int32_t *n_poses_or_fail)
+int gv_segment_ground_plane(gv_handle h, double threshold, int32_t iterations, uint64_t seed, uint8_t *is_ground,
+                            float coeff[4], int64_t *n_inliers)
 {
+  RansacState st;
+  return segment_ground_plane_impl(h, threshold, iterations, seed, is_ground, coeff, n_inliers, st);
+}
+
+// gv_compute_bbox_pose_ground_removed; st: as above
+static int bbox_pose_ground_removed_impl(gv_handle h, const gv_bbox *bboxes, int32_t nb, gv_lshape_pose *poses_out,
+                                         uint8_t *valid, int32_t *n_poses_or_fail, RansacState &st)
+{
+  st = RansacState{};
   if (!h || nb < 0 || (nb && (!bboxes || !poses_out || !valid))) return GV_ERR_BAD_ARG;
   if (!h->has_cl) return GV_ERR_TF;
   // computeBBoxPose (cloud_detections.cpp:300-321): segmentGroundPlane -> extractCloudPerBBox -> PCA, enqueued as
   // one batch: the device decides the "empty segmented cloud" cases, the host reads 56 bytes of state + the poses
   if (n_poses_or_fail) *n_poses_or_fail = 0;
-  RansacState st;
   int rc = compute_bbox_pose_impl(h, bboxes, nb, poses_out, valid, true, &st);
   if (rc) return rc;
   if (segmented_cloud_empty(st, h->n)) {
@@ -441,6 +450,29 @@ int gv_compute_bbox_pose_ground_removed(gv_handle h, const gv_bbox *bboxes, int3
   if (n_poses_or_fail)
     for (int32_t b = 0; b < nb; ++b) *n_poses_or_fail += valid[b];
   return GV_OK;
+}
+
+int gv_compute_bbox_pose_ground_removed(gv_handle h, const gv_bbox *bboxes, int32_t nb, gv_lshape_pose *poses_out,
+                                        uint8_t *valid, int32_t *n_poses_or_fail)
+{
+  RansacState st;
+  return bbox_pose_ground_removed_impl(h, bboxes, nb, poses_out, valid, n_poses_or_fail, st);
+}
+
+// test hook (gv_test_hooks.h): one of the two public calls above, and the RansacState it brought home
+int gv_test_ransac_state(gv_handle h, double threshold, int32_t iterations, uint64_t seed, int32_t pose_path,
+                         const gv_bbox *bboxes, int32_t nb, uint8_t *is_ground, gv_lshape_pose *poses_out, uint8_t *valid,
+                         int32_t *n_poses_or_fail, gv_test_ransac_state_t *out)
+{
+  if (!out) return GV_ERR_BAD_ARG;
+  RansacState st;
+  const int rc = pose_path ? bbox_pose_ground_removed_impl(h, bboxes, nb, poses_out, valid, n_poses_or_fail, st)
+                           : segment_ground_plane_impl(h, threshold, iterations, seed, is_ground, nullptr, nullptr, st);
+  const float4 pl = st.plane, rf = st.refined;
+  out->plane[0] = pl.x; out->plane[1] = pl.y; out->plane[2] = pl.z; out->plane[3] = pl.w;
+  out->refined[0] = rf.x; out->refined[1] = rf.y; out->refined[2] = rf.z; out->refined[3] = rf.w;
+  out->m = st.m; out->n_inliers = st.n_inliers; out->best_count = st.best_count; out->pad = 0u;
+  return rc;
 }
 
 // test hook (gv_test_hooks.h): the public call, then the selected points and their keep flags as it left them

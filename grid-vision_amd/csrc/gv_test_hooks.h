@@ -27,6 +27,20 @@ int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, con
 int gv_test_bbox_pose_nodes(gv_handle h, const gv_bbox *bboxes, int32_t nb, int32_t with_ground, gv_lshape_pose *poses_out,
                             uint8_t *valid, int32_t *n_poses_or_fail, float *nodes /* n*4 */, uint8_t *keep /* n */,
                             int64_t *n_sel);
+/* gv_segment_ground_plane(threshold, iterations, seed, is_ground) (pose_path == 0; bboxes .. n_poses_or_fail unused), or
+ * gv_compute_bbox_pose_ground_removed(bboxes, nb, poses_out, valid, n_poses_or_fail) with its fixed 0.04 / 50 / 12345
+ * (pose_path != 0; threshold .. is_ground unused): the product's own call through the same function, and the RansacState
+ * that call brings home anyway -- the sampled plane, the refined plane, m = the sampled plane's inliers as the moments pass
+ * counted them, n_inliers = the refined plane's as the mask / classify pass counted them, best_count = the winner's count as
+ * the counting pass left it (0: no plane, everything else zero).  No kernel of its own (tests/test_gpu_ransac.py). */
+typedef struct gv_test_ransac_state_t {
+  float plane[4], refined[4];
+  uint64_t m, n_inliers;
+  uint32_t best_count, pad;
+} gv_test_ransac_state_t;
+int gv_test_ransac_state(gv_handle h, double threshold, int32_t iterations, uint64_t seed, int32_t pose_path,
+                         const gv_bbox *bboxes, int32_t nb, uint8_t *is_ground /* n */, gv_lshape_pose *poses_out,
+                         uint8_t *valid, int32_t *n_poses_or_fail, gv_test_ransac_state_t *out);
 /* Host only, no handle and no device: the plan of the sharded frame (host::ShardPlan, csrc/gv_host_math.hpp) that a handle
  * over an nx x ny grid keeps for a communicator of `world` ranks: words of one end-bitmap slice and of one packed free-cell
  * band, whether one ncclReduceScatter of *cnt0 cells per rank serves the hit counts (else one ncclReduce per band: the

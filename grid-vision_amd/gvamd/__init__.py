@@ -220,6 +220,12 @@ class TickResult(C.Structure):
                 ("base_points_xyz", C.c_void_p), ("poses", C.c_void_p), ("n_poses", C.c_int32), ("pca_empty", C.c_int32)]
 
 
+class RansacStateOut(C.Structure):
+    """gv_test_ransac_state_t (csrc/gv_test_hooks.h)"""
+    _fields_ = [("plane", C.c_float * 4), ("refined", C.c_float * 4), ("m", C.c_uint64), ("n_inliers", C.c_uint64),
+                ("best_count", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class PinnedI8:
     """int8 array in page-locked host memory: the packed grid's landing place (gv_tick grid_out, gv_to_occupancy_grid_async)"""
 
@@ -748,6 +754,29 @@ class GridVisionHIP:
                                                    _ptr(poses), _ptr(valid), C.byref(npz), _ptr(nodes), _ptr(keep),
                                                    C.byref(m)), "gv_test_bbox_pose_nodes")
         return poses[:len(b)], valid[:len(b)], nodes[:m.value].copy(), keep[:m.value].copy()
+
+    def ransac_state(self, threshold=0.04, iterations=50, seed=12345, bboxes=None):
+        """test hook (csrc/gv_test_hooks.h): segment_ground_plane (bboxes None) or compute_bbox_pose_ground_removed
+        (bboxes given: its fixed 0.04 / 50 / 12345) and the RANSAC state the call brought home, as a dict: plane and
+        refined (float32[4]), m, n_inliers, best_count, and mask (uint8[n]) or poses, valid, n_poses"""
+        st = RansacStateOut()
+        if bboxes is None:
+            mask = np.zeros(max(self.n, 1), np.uint8)
+            self._ck(self._lib.gv_test_ransac_state(self._h, C.c_double(threshold), C.c_int32(iterations), C.c_uint64(seed),
+                                                    C.c_int32(0), None, C.c_int32(0), _ptr(mask), None, None, None,
+                                                    C.byref(st)), "gv_test_ransac_state")
+            out = {"mask": mask[:self.n]}
+        else:
+            b = _boxes(bboxes)
+            poses, valid = _pose_outputs(b)
+            npz = C.c_int32(0)
+            self._ck(self._lib.gv_test_ransac_state(self._h, C.c_double(0.0), C.c_int32(0), C.c_uint64(0), C.c_int32(1),
+                                                    _ptr(b), C.c_int32(len(b)), None, _ptr(poses), _ptr(valid),
+                                                    C.byref(npz), C.byref(st)), "gv_test_ransac_state")
+            out = {"poses": poses[:len(b)], "valid": valid[:len(b)], "n_poses": npz.value}
+        out.update(plane=np.array(st.plane, np.float32), refined=np.array(st.refined, np.float32), m=int(st.m),
+                   n_inliers=int(st.n_inliers), best_count=int(st.best_count))
+        return out
 
     def transform_lshape_objects(self, poses):
         p = np.ascontiguousarray(poses, dtype=LSHAPE_DTYPE).copy()
