@@ -164,15 +164,16 @@ def camera_frame(x, y, z):
     return ol.transform_cloud(ol.tf_to_matrix4f(IDENT_TF), x, y, z)
 
 
-def run(cx, cy, cz, boxes, drop=None):
+def run(cx, cy, cz, boxes, drop=None, K=K_SYNTH, w=IMG_W, h=IMG_H):
     """one whole call on a camera-frame cloud.  drop: bool mask of points removed before the split (the ground).
+    K, w, h: the camera (row-major intrinsics, image size).
     ids[n] (-1: not selected), keep[n] bool, poses[nb], valid[nb], rects[nb] (Rect or None)"""
     cx, cy, cz = (np.ascontiguousarray(a, F32) for a in (cx, cy, cz))
     boxes = np.ascontiguousarray(boxes, BBOX_DTYPE)
     n, nb = len(cx), len(boxes)
     live = np.ones(n, bool) if drop is None else ~np.asarray(drop, bool)
     ids = np.full(n, -1, np.int32)
-    ids[live] = ol.extract_cloud_per_bbox(K_SYNTH, cx[live], cy[live], cz[live], boxes, IMG_W, IMG_H)
+    ids[live] = ol.extract_cloud_per_bbox(K, cx[live], cy[live], cz[live], boxes, w, h)
     keep = np.zeros(n, bool)
     poses, valid, rects = np.zeros(nb, LSHAPE_DTYPE), np.zeros(nb, np.uint8), [None] * nb
     order = np.argsort(ids, kind="stable")
@@ -215,9 +216,9 @@ def make_boxes(rects):
     return b
 
 
-def grid_boxes(cols, rows, count=None):
-    """cols x rows boxes that tile the image, row major; count: only the first ones"""
-    w, h = IMG_W / cols, IMG_H / rows
+def grid_boxes(cols, rows, count=None, w=IMG_W, h=IMG_H):
+    """cols x rows boxes that tile the w x h image, row major; count: only the first ones"""
+    w, h = w / cols, h / rows
     r = [(c * w, q * h, (c + 1) * w, (q + 1) * h) for q in range(rows) for c in range(cols)]
     return make_boxes(r[:count] if count is not None else r)
 
@@ -226,9 +227,9 @@ def box_centre(b):
     return 0.5 * (b["x_min"] + b["x_max"]), 0.5 * (b["y_min"] + b["y_max"])
 
 
-def ray_point(u, v, zc):
-    """camera point of depth zc that projects to pixel (u, v)"""
-    return (u - 320.0) / 320.0 * zc, (v - 240.0) / 320.0 * zc, zc
+def ray_point(u, v, zc, K=K_SYNTH):
+    """camera point of depth zc that projects to pixel (u, v) under the intrinsics K"""
+    return (u - K[2]) / K[0] * zc, (v - K[5]) / K[4] * zc, zc
 
 
 def cell_of(a):
@@ -609,9 +610,10 @@ def family(name):
 _REF = {}
 
 
-def reference(scene):
-    """(camera-frame cloud, Result) of a scene, computed once and shared"""
-    if scene.tag not in _REF:
+def reference(scene, K=K_SYNTH, w=IMG_W, h=IMG_H):
+    """(camera-frame cloud, Result) of a scene at the camera K, w, h, computed once and shared"""
+    key = (scene.tag, tuple(float(t) for t in K), w, h)
+    if key not in _REF:
         cam = camera_frame(scene.x, scene.y, scene.z)
-        _REF[scene.tag] = (cam, run(*cam, scene.boxes))
-    return _REF[scene.tag]
+        _REF[key] = (cam, run(*cam, scene.boxes, K=K, w=w, h=h))
+    return _REF[key]

@@ -36,7 +36,9 @@ def make_handle(gvamd, config, perturbed=False):
     return h, tfs
 
 
-def oracle_frame(og, tfs, x, y, z, bboxes=None, poses=None, raymarch=True):
+def oracle_frame(og, tfs, x, y, z, bboxes=None, poses=None, raymarch=True, camera=None):
+    """camera: (fx, fy, cx, cy, image_w, image_h) of the handle, gvamd.synth's when None"""
+    fx, fy, pcx, pcy, img_w, img_h = camera or (synth.FX, synth.FY, synth.CX, synth.CY, synth.IMG_W, synth.IMG_H)
     m_base = ol.tf_to_matrix4f(tfs["base_lidar"])
     m_cam = ol.tf_to_matrix4f(tfs["cam_lidar"])
     hits, cell = og.bin_points(m_base, x, y, z)
@@ -44,8 +46,8 @@ def oracle_frame(og, tfs, x, y, z, bboxes=None, poses=None, raymarch=True):
     ids = None
     if bboxes is not None:
         cx, cy, cz = ol.transform_cloud(m_cam, x, y, z)
-        K = ol.set_intrinsic(synth.FX, synth.FY, synth.CX, synth.CY)
-        ids = ol.extract_cloud_per_bbox(K, cx, cy, cz, bboxes, synth.IMG_W, synth.IMG_H)
+        K = ol.set_intrinsic(fx, fy, pcx, pcy)
+        ids = ol.extract_cloud_per_bbox(K, cx, cy, cz, bboxes, img_w, img_h)
     og.frame_update(poses, hits, miss)
     return hits, cell, miss, ids, visits
 
@@ -1116,10 +1118,10 @@ def _radius_keep_ckdtree(x, y, z, r=0.4, min_pts=10):
     return keep
 
 
-def _pose_reference(cx, cy, cz, K, b, keep_fn, points=False):
+def _pose_reference(cx, cy, cz, K, b, keep_fn, points=False, image=(synth.IMG_W, synth.IMG_H)):
     """per bbox: ids as extractCloudPerBBox, radius filter, oracle PCA rectangle on the kept points in cloud order
     (points=True: also the kept points of every bbox, (x, y, z) in cloud order, for _check_pose_fp64)"""
-    ids = ol.extract_cloud_per_bbox(K, cx, cy, cz, b, synth.IMG_W, synth.IMG_H)
+    ids = ol.extract_cloud_per_bbox(K, cx, cy, cz, b, image[0], image[1])
     out, kept = [], []
     for i in range(len(b)):
         sel = ids == i
