@@ -8,8 +8,10 @@
 //   [EXTENSION] X11 MPPI's two ends around them: sampling the controls and the softmax average (gv_set_mppi, gv_mppi_*).
 //   [EXTENSION] X12 rate and turning-radius limits on those samples and the control cost in the average
 //                   (gv_set_mppi_limits, gv_mppi_constrain, gv_*mppi_control_costs, gv_mppi_average_cc).
+//   [EXTENSION] X13 scoring of trajectories against predicted moving objects, as a call of its own and as a third
+//                   record of the control step (gv_set_dyn_config, gv_set_moving_objects, gv_score_dynamic*).
 // The kernels are gv_inflate.hip, gv_trajscore.hip, gv_navfield.hip (which also argues why the rounds end at the
-// exact field), gv_rollout.hip and gv_mppi.hip.  What the two samplers do alike, and what a control step and an MPPI
+// exact field), gv_rollout.hip, gv_mppi.hip and gv_dynscore.hip.  What the two samplers do alike, and what a control step and an MPPI
 // update enqueue alike, is written once, in front of the entry points.
 #include <algorithm>
 #include <cstring>
@@ -117,15 +119,106 @@ bool control_args_ok(const gv_critic_weights *w, uint32_t flags, const gv_contro
          (!(flags & GV_CONTROL_KEEP_TOTALS) || totals);
 }
 
-// The two samplers over the resident rollout into their device record buffers, then the selection into `result` and
-// `totals` (null: no totals), on the public stream: what a control step and an MPPI update enqueue alike.
-int enqueue_control_scores(gv_context *h, const gv_critic_weights &w, gv_control_result *result, uint64_t *totals)
+// ---- X13: what the device calls and their host twins check alike
+// the cost table of a configuration; false (t untouched) for anything gv_set_dyn_config rejects.  The radii, the
+// factor, the quantum and Rc <= 63 are host::inflation_table's own checks.
+bool dyn_config_table(const gv_dyn_config &c, host::InflationTable &t)
+{
+  if (c.n_circles < 1 || c.n_circles > kDynMaxCircles) return false;
+  for (int32_t i = 0; i < c.n_circles; ++i)
+    if (!std::isfinite(c.off_x[i])) return false;
+  if (!std::isfinite(c.t0) || !std::isfinite(c.dt) || !(c.dt >= 0.0)) return false;
+  if (c.collision_cost < 1 || c.collision_cost > 255 || c.w_sum > 65535u || c.w_max > 65535u || c.flags != 0u) return false;
+  gv_inflation f{};
+  f.inscribed_radius = c.radius;
+  f.inflation_radius = c.influence_radius;
+  f.cost_scaling_factor = c.cost_scaling_factor;
+  f.lethal_threshold = 100;
+  f.flags = 0;
+  return host::inflation_table(f, c.quantum, t);
+}
+
+bool moving_objects_ok(const gv_moving_object *objs, int32_t n)
+{
+  if (n < 0 || n > kDynMaxObjects || (n > 0 && !objs)) return false;
+  for (int32_t j = 0; j < n; ++j) {
+    const gv_lshape_pose &q = objs[j].pose;
+    const double read[] = {q.px, q.py, q.qx, q.qy, q.qz, q.qw, q.length, q.width, objs[j].vx, objs[j].vy};
+    for (double v : read)
+      if (!std::isfinite(v)) return false;
+    if (q.length < 0.0 || q.width < 0.0) return false;
+  }
+  return true;
+}
+
+// `bytes` (> 0) of host data into the slot of `u` that is not the current one, of `cap` bytes, by a copy command on the
+// public stream; that slot is the current one afterwards.  Inflation's mechanism for its table, written once for X13.
+int upload_slot(gv_context *h, gv_context::UploadSlots &u, const void *src, size_t bytes, size_t cap)
+{
+  const int k = u.slot ^ 1;
+  int rc = GV_OK;
+  if ((rc = u.dev[k].reserve(h, cap)) || (rc = u.stage[k].reserve(h, cap, hipHostMallocDefault))) return rc;
+  if (!u.staged[k]) GV_HIP(u.staged[k].create(hipEventDisableTiming));
+  if (u.staged_used[k]) GV_HIP(hipEventSynchronize(u.staged[k]));
+  std::memcpy(u.stage[k].get(), src, bytes);
+  GV_HIP(hipMemcpyAsync(u.dev[k], u.stage[k].get(), bytes, hipMemcpyHostToDevice, h->stream));
+  GV_HIP(hipEventRecord(u.staged[k], h->stream));
+  u.staged_used[k] = true;
+  u.slot = k;
+  return GV_OK;
+}
+
+// What every launch of the dyn sampler carries, with the configuration and the set in force now; a changed cost table
+// goes to the device first.
+int dyn_kernel_args(gv_context *h, DynArgs &a)
+{
+  gv_context::DynScore &d = h->dyn;
+  if (d.dirty) {
+    constexpr size_t kTableBytes = (size_t)(host::kInflateMaxRc + 1) * (host::kInflateMaxRc + 1);
+    if (int rc = upload_slot(h, d.table, d.tab.cost.data(), d.tab.cost.size(), kTableBytes)) return rc;
+    d.dirty = false;
+  }
+  a.p = dyn_params(d.cfg, d.tab.d2max + 1);
+  a.objs = reinterpret_cast<const DynObject *>(d.objs.dev[d.objs.slot].get());
+  a.n_obj = d.n_obj;
+  a.table = d.table.dev[d.table.slot];
+  return GV_OK;
+}
+
+// host only: control_total / control_take (gv_motion.hpp) in a loop; dyn null: the two records alone
+void control_select_host(const gv_critic_weights &w, const gv_traj_score *traj, const gv_nav_score *nav, const gv_dyn_score *dyn,
+                         uint32_t w_dyn_sum, uint32_t w_dyn_max, int32_t K, gv_control_result *result, uint64_t *totals)
 {
   const bool nav_used = critic_nav_used(w);
+  uint64_t best_total = UINT64_MAX;
+  int32_t best_k = -1, n = 0;
+  for (int32_t k = 0; k < K; ++k) {
+    uint64_t total = UINT64_MAX;
+    const bool ok = control_total(w, nav_used, traj[k], nav_used ? nav + k : nullptr, dyn ? dyn + k : nullptr, w_dyn_sum, w_dyn_max, total);
+    if (!ok) total = UINT64_MAX;
+    if (totals) totals[k] = total;
+    if (ok) {
+      ++n;
+      control_take(total, k, best_total, best_k);
+    }
+  }
+  result->best = best_k;
+  result->n_valid = n;
+  result->best_total = best_k < 0 ? UINT64_MAX : best_total;
+}
+
+// The samplers over the resident rollout into their device record buffers (X7, X9 when a nav weight is set, X13 when a
+// dyn configuration is), then the selection into `result` and `totals` (null: no totals), on the public stream: what a
+// control step and an MPPI update enqueue alike.
+int enqueue_control_scores(gv_context *h, const gv_critic_weights &w, gv_control_result *result, uint64_t *totals)
+{
+  const bool nav_used = critic_nav_used(w), dyn_used = h->dyn.set;
   gv_context::Rollout &r = h->roll;
   const int32_t K = r.K, P = r.P;
   int rc = GV_OK;
-  if ((rc = h->traj.d_scores.reserve(h, (size_t)K)) || (nav_used && (rc = h->nav.d_scores.reserve(h, (size_t)K)))) return rc;
+  if ((rc = h->traj.d_scores.reserve(h, (size_t)K)) || (nav_used && (rc = h->nav.d_scores.reserve(h, (size_t)K))) ||
+      (dyn_used && (rc = h->dyn.d_scores.reserve(h, (size_t)K))))
+    return rc;
   TrajArgs t{};
   t.g = h->g;
   t.fp = h->traj.fp;
@@ -144,10 +237,22 @@ int enqueue_control_scores(gv_context *h, const gv_critic_weights &w, gv_control
     n.scores = h->nav.d_scores;
     launch_score_nav(n, h->stream);
   }
+  if (dyn_used) {
+    DynArgs d{};
+    if ((rc = dyn_kernel_args(h, d))) return rc;
+    d.poses = r.poses;
+    d.K = K; d.P = P;
+    d.scores = h->dyn.d_scores;
+    d.pose_cost = nullptr;
+    launch_score_dynamic(d, h->stream);
+  }
   ControlSelectArgs s{};
   s.w = w;
   s.traj = h->traj.d_scores;
   s.nav = nav_used ? h->nav.d_scores.get() : nullptr;
+  s.dyn = dyn_used ? h->dyn.d_scores.get() : nullptr;
+  s.w_dyn_sum = h->dyn.cfg.w_sum;
+  s.w_dyn_max = h->dyn.cfg.w_max;
   s.K = K;
   s.result = result;
   s.totals = totals;
@@ -781,23 +886,8 @@ int gv_control_select(const gv_critic_weights *w, const gv_traj_score *traj, con
                       gv_control_result *result, uint64_t *totals)
 {
   if (!w || !traj || !result || !critic_weights_valid(*w) || K < 0 || K > (1 << 20)) return GV_ERR_BAD_ARG;
-  const bool nav_used = critic_nav_used(*w);
-  if (nav_used && !nav) return GV_ERR_BAD_ARG;
-  uint64_t best_total = UINT64_MAX;
-  int32_t best_k = -1, n = 0;
-  for (int32_t k = 0; k < K; ++k) {
-    uint64_t total = UINT64_MAX;
-    const bool ok = control_total(*w, nav_used, traj[k], nav_used ? nav + k : nullptr, total);
-    if (!ok) total = UINT64_MAX;
-    if (totals) totals[k] = total;
-    if (ok) {
-      ++n;
-      control_take(total, k, best_total, best_k);
-    }
-  }
-  result->best = best_k;
-  result->n_valid = n;
-  result->best_total = best_k < 0 ? UINT64_MAX : best_total;
+  if (critic_nav_used(*w) && !nav) return GV_ERR_BAD_ARG;
+  control_select_host(*w, traj, nav, nullptr, 0u, 0u, K, result, totals);
   return GV_OK;
 }
 
@@ -1075,6 +1165,142 @@ int gv_mppi_average_cc(const gv_mppi_config *cfg, int32_t C, const float *contro
   }
   return GV_OK;
   GV_CATCH
+}
+
+// ---- [EXTENSION] X13: scoring against predicted moving objects ----
+int gv_dyn_cost_table(const gv_dyn_config *cfg, uint8_t *table, int32_t cap, int32_t *n)
+{
+  gv_context *h = nullptr;
+  if (!cfg) return GV_ERR_BAD_ARG;
+  GV_TRY
+  host::InflationTable t;
+  if (!dyn_config_table(*cfg, t)) return GV_ERR_BAD_ARG;
+  if (n) *n = t.d2max + 1;
+  if (!table || cap < t.d2max + 1) return GV_ERR_BAD_ARG;
+  std::memcpy(table, t.cost.data(), t.cost.size());
+  return GV_OK;
+  GV_CATCH
+}
+
+// handle configuration: the table is built here on the host and reaches the device with the next call that scores
+// (dyn_kernel_args).  A rejected configuration leaves the one in force alone.
+int gv_set_dyn_config(gv_handle h, const gv_dyn_config *cfg)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  gv_context::DynScore &d = h->dyn;
+  if (!cfg) {
+    d.set = false;
+    return GV_OK;
+  }
+  host::InflationTable t;
+  if (!dyn_config_table(*cfg, t)) return GV_ERR_BAD_ARG;
+  d.tab = std::move(t);
+  d.cfg = *cfg;
+  for (int32_t i = cfg->n_circles; i < kDynMaxCircles; ++i) d.cfg.off_x[i] = 0.0;
+  d.dirty = true;
+  d.set = true;
+  return GV_OK;
+  GV_CATCH
+}
+
+// The object table is built on the host into a pinned slot and goes to the device by one copy command on the public
+// stream: the calls enqueued before it read the slot they were given, the calls after it the new one.
+int gv_set_moving_objects(gv_handle h, const gv_moving_object *objs, int32_t n)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!moving_objects_ok(objs, n)) return GV_ERR_BAD_ARG;
+  gv_context::DynScore &d = h->dyn;
+  if (n > 0) {
+    int rc = set_device_only(h);
+    if (rc) return rc;
+    DynObject rows[kDynMaxObjects];
+    for (int32_t j = 0; j < n; ++j) rows[j] = dyn_object(objs[j]);
+    if ((rc = upload_slot(h, d.objs, rows, (size_t)n * sizeof(DynObject), sizeof(rows)))) return rc;
+  }
+  d.n_obj = n;
+  return GV_OK;
+  GV_CATCH
+}
+
+// gv_score_trajectories_async with another kernel and another record; no grid and no costmap is read
+int gv_score_dynamic_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_dyn_score *scores,
+                           uint8_t *pose_cost)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  const bool keep = (flags & GV_TRAJ_KEEP_POSE_COST) != 0;
+  if (!batch_ok(poses, scores, K, P, flags, host::kTrajFlags) || (keep && !pose_cost)) return GV_ERR_BAD_ARG;
+  gv_context::DynScore &d = h->dyn;
+  if (!d.set) {
+    h->err = "gv_score_dynamic: no configuration set (gv_set_dyn_config)";
+    return GV_ERR_STATE;
+  }
+  int rc = GV_OK;
+  if (K == 0 || (rc = set_device_only(h))) return rc;
+  const size_t n_poses = (size_t)K * (size_t)P;
+  DynArgs a{};
+  a.K = K; a.P = P;
+  ResultDest<gv_dyn_score> to_scores;
+  ResultDest<uint8_t> to_pose_cost;   // stays closed (null, no copy) without GV_TRAJ_KEEP_POSE_COST
+  if ((rc = dyn_kernel_args(h, a)) || (rc = stage_poses(h, poses, n_poses, flags, &a.poses)) ||
+      (rc = to_scores.open(h, scores, (size_t)K, 8, d.d_scores)) || (keep && (rc = to_pose_cost.open(h, pose_cost, n_poses, 1, d.d_pose_cost))))
+    return rc;
+  a.scores = to_scores.dev;
+  a.pose_cost = to_pose_cost.dev;
+  launch_score_dynamic(a, h->stream);
+  GV_HIP(hipGetLastError());
+  if ((rc = to_scores.copy_back(h)) || (rc = to_pose_cost.copy_back(h))) return rc;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_score_dynamic(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_dyn_score *scores,
+                     uint8_t *pose_cost)
+{
+  return wait_scored(h, gv_score_dynamic_async(h, poses, K, P, flags, scores, pose_cost), K);
+}
+
+// host only: gv_dyn.hpp's text in loops, one trajectory after the other, one pose after the other
+int gv_dyn_score_poses(const gv_dyn_config *cfg, const gv_moving_object *objs, int32_t n, const float *poses, int32_t K,
+                       int32_t P, gv_dyn_score *scores, uint8_t *pose_cost)
+{
+  gv_context *h = nullptr;
+  if (!cfg || !batch_ok(poses, scores, K, P, 0u, 0u) || !moving_objects_ok(objs, n)) return GV_ERR_BAD_ARG;
+  GV_TRY
+  host::InflationTable t;
+  if (!dyn_config_table(*cfg, t)) return GV_ERR_BAD_ARG;
+  const DynParams c = dyn_params(*cfg, t.d2max + 1);
+  std::vector<DynObject> rows((size_t)n);
+  for (int32_t j = 0; j < n; ++j) rows[(size_t)j] = dyn_object(objs[j]);
+  for (size_t k = 0; k < (size_t)K; ++k) {
+    DynAccum acc;
+    for (int32_t p = 0; p < P; ++p) {
+      double best = INFINITY;
+      int32_t best_j = -1;
+      dyn_pose_min(c, rows.data(), n, 0, 1, poses + (k * (size_t)P + (size_t)p) * 3, p, best, best_j);
+      const int32_t cost = dyn_cost(c, t.cost.data(), best);
+      dyn_accumulate(c, p, cost, best, best_j, acc);
+      if (pose_cost) pose_cost[k * (size_t)P + (size_t)p] = (uint8_t)cost;
+    }
+    scores[k] = dyn_record(acc);
+  }
+  return GV_OK;
+  GV_CATCH
+}
+
+// host only: gv_control_select with the third record
+int gv_control_select_dyn(const gv_critic_weights *w, const gv_traj_score *traj, const gv_nav_score *nav,
+                          const gv_dyn_score *dyn, const gv_dyn_config *cfg, int32_t K, gv_control_result *result,
+                          uint64_t *totals)
+{
+  if (!cfg) return gv_control_select(w, traj, nav, K, result, totals);
+  if (!w || !traj || !dyn || !result || !critic_weights_valid(*w) || K < 0 || K > (1 << 20) || cfg->w_sum > 65535u ||
+      cfg->w_max > 65535u || (critic_nav_used(*w) && !nav))
+    return GV_ERR_BAD_ARG;
+  control_select_host(*w, traj, nav, dyn, cfg->w_sum, cfg->w_max, K, result, totals);
+  return GV_OK;
 }
 
 }  // extern "C"

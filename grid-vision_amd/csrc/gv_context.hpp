@@ -410,6 +410,30 @@ struct __attribute__((visibility("hidden"))) gv_context {
     int32_t costK = 0;                      // of the last update with gamma > 0
     bool have_costs = false;                // the last update ran with gamma > 0
   } mppi;
+  // [EXTENSION] X13 scoring against predicted moving objects (gv_set_dyn_config / gv_set_moving_objects /
+  // gv_score_dynamic*).  The configuration and its host-built cost table are handle state; a changed table reaches the
+  // device with the next call that scores, through Inflation's mechanism (UploadSlots).  The object table is built on the
+  // host by gv_set_moving_objects and copied on the public stream through slots of its own; n_obj travels in the kernel
+  // arguments.  Neither depends on the map: gv_reset keeps both.  d_scores / d_pose_cost follow TrajScore's rules, and
+  // d_scores is also where the control step's dyn sampler writes.
+  struct UploadSlots {
+    DevBuf<uint8_t> dev[2];                 // slot k is rewritten behind every kernel that was given it: one in-order stream
+    PinnedBuf stage[2];                     // ... and staging slot k only once its last copy has left it (the one host wait)
+    Event staged[2];
+    bool staged_used[2] = {false, false};
+    int slot = 0;                           // of the current contents
+  };
+  struct DynScore {
+    bool set = false;
+    gv_dyn_config cfg{};
+    host::InflationTable tab;
+    bool dirty = false;                     // `tab` is newer than the device slot
+    UploadSlots table;
+    int32_t n_obj = 0;                      // of the set in force for the calls enqueued from now on
+    UploadSlots objs;
+    DevBuf<gv_dyn_score> d_scores;
+    DevBuf<uint8_t> d_pose_cost;
+  } dyn;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
   // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gv_types.hpp"
+#include "gv_dyn.hpp"
 
 namespace gv {
 
@@ -181,6 +182,8 @@ struct ControlSelectArgs {
   gv_critic_weights w;
   const gv_traj_score *traj;    // K records (device)
   const gv_nav_score *nav;      // K records (device), or null when no nav weight is set
+  const gv_dyn_score *dyn;      // [EXTENSION] X13: K records (device), or null when no dyn configuration is set
+  uint32_t w_dyn_sum, w_dyn_max;   // ... and its two weights
   int32_t K;
   gv_control_result *result;    // one record (device memory, or the device view of pinned host memory; 16-byte aligned)
   uint64_t *totals;             // K, or null (device memory, or the device view of pinned host memory)
@@ -240,6 +243,20 @@ struct MppiCostArgs {
   uint64_t *x_min_key;          // one (device)
 };
 void launch_mppi_control_cost(const MppiCostArgs &a, hipStream_t s);
+// [EXTENSION] X13 scoring against predicted moving objects (gv_dynscore.hip; the arithmetic is gv_dyn.hpp's).  The
+// configuration and the number of objects travel by value; the object table and the cost table are read when the
+// kernel runs, behind the copy commands that filled them on the same stream.
+struct DynArgs {
+  DynParams p;
+  const float *poses;           // K * P * 3 (device)
+  int32_t K, P;
+  const DynObject *objs;        // n_obj rows (device); not read when n_obj == 0
+  int32_t n_obj;                // 0 .. kDynMaxObjects
+  const uint8_t *table;         // p.T costs (device)
+  gv_dyn_score *scores;         // K records (device memory, or the device view of pinned host memory; 8-byte aligned)
+  uint8_t *pose_cost;           // K * P, or null
+};
+void launch_score_dynamic(const DynArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

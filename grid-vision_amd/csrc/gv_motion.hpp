@@ -3,7 +3,7 @@
 //   motion_yaw, motion_increment   the yaw chain and the increments of a pose: the pieces of one step of the motion
 //                    model (include/gridvision_hip.h has the definition) that k_rollout hands to different lanes;
 //   motion_step      the whole step made of them, for the host twin;
-//   control_total    combine and reject of one trajectory's two records.
+//   control_total    combine and reject of one trajectory's two records (three with [EXTENSION] X13's dyn record).
 // Every operation is one fp64 operation in the header's order; the build never contracts (-ffp-contract=off).
 #pragma once
 
@@ -61,19 +61,27 @@ GV_HD bool critic_nav_used(const gv_critic_weights &w) { return (w.w_nav_last | 
 // The largest total of an admitted trajectory: every weight 65535, P = 4096 poses of cost 255 (cost_sum, max_cost) on
 // field values of 0xFFFFFFFD, the largest below the two sentinels (sum over 4096 poses, last, best):
 //   65535 * (4096 * 255 + 255 + (4096 + 2) * 0xFFFFFFFD) = 1.1535e18 < 2^61 = 2.3058e18
-static_assert(65535ull * (4096ull * 255ull + 255ull + (4096ull + 2ull) * 0xFFFFFFFDull) < (1ull << 61),
+// [EXTENSION] X13 adds the dyn record's two terms, at most 65535 * (4096 * 255 + 255) more: 1.1535e18 still.
+static_assert(65535ull * (4096ull * 255ull + 255ull + (4096ull + 2ull) * 0xFFFFFFFDull) + 65535ull * (4096ull * 255ull + 255ull) <
+                  (1ull << 61),
               "an admitted total stays below 2^61, far from UINT64_MAX, the mark of a rejected trajectory");
 
-// false: the trajectory is rejected (it collides, or a nav weight is set and a pose is not good); else its total.
-// nav may be null when no nav weight is set.  With n_bad == 0 last and best are field values, never a sentinel.
+// false: the trajectory is rejected (it collides, or a nav weight is set and a pose is not good, or a dyn configuration
+// is set and a pose collides with a moving object); else its total.  nav may be null when no nav weight is set, dyn is
+// null when no dyn configuration is set (w_dyn_sum, w_dyn_max are not read then).  With n_bad == 0 last and best are
+// field values, never a sentinel.
 GV_HD bool control_total(const gv_critic_weights &w, bool nav_used, const gv_traj_score &t, const gv_nav_score *nav,
-                         uint64_t &total)
+                         const gv_dyn_score *dyn, uint32_t w_dyn_sum, uint32_t w_dyn_max, uint64_t &total)
 {
   if (t.first_collision >= 0) return false;
   uint64_t v = (uint64_t)w.w_cost_sum * (uint64_t)t.cost_sum + (uint64_t)w.w_max_cost * (uint64_t)(uint32_t)t.max_cost;
   if (nav_used) {
     if (nav->n_bad > 0) return false;
     v += (uint64_t)w.w_nav_last * (uint64_t)nav->last + (uint64_t)w.w_nav_sum * nav->sum + (uint64_t)w.w_nav_best * (uint64_t)nav->best;
+  }
+  if (dyn) {
+    if (dyn->first_collision >= 0) return false;
+    v += (uint64_t)w_dyn_sum * (uint64_t)dyn->cost_sum + (uint64_t)w_dyn_max * (uint64_t)(uint32_t)dyn->max_cost;
   }
   total = v;
   return true;

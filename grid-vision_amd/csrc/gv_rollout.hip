@@ -139,7 +139,8 @@ __global__ void __launch_bounds__(kSelectThreads) k_control_select(ControlSelect
   int32_t best_k = -1, n = 0;
   for (int32_t k = tid; k < a.K; k += kSelectThreads) {
     uint64_t total = UINT64_MAX;
-    const bool ok = control_total(a.w, nav_used, a.traj[k], nav_used ? a.nav + k : nullptr, total);
+    const bool ok = control_total(a.w, nav_used, a.traj[k], nav_used ? a.nav + k : nullptr, a.dyn ? a.dyn + k : nullptr,
+                                  a.w_dyn_sum, a.w_dyn_max, total);
     if (!ok) total = UINT64_MAX;
     if (a.totals) a.totals[k] = total;
     if (ok) {

@@ -51,6 +51,11 @@ CONTROL_KEEP_TOTALS = 1 << 0
 CONTROL_RESULT_DTYPE = np.dtype([("best", np.int32), ("n_valid", np.int32), ("best_total", np.uint64)])   # gv_control_result
 MPPI_SHIFT = 1 << 0
 
+DYN_MAX_OBJECTS = 128
+DYN_SCORE_DTYPE = np.dtype([("max_cost", np.int32), ("first_collision", np.int32), ("cost_sum", np.uint32),
+                            ("nearest_object", np.int32), ("min_dist2", np.float64)])   # gv_dyn_score
+MOVING_OBJECT_DTYPE = np.dtype([("pose", LSHAPE_DTYPE), ("vx", np.float64), ("vy", np.float64)])   # gv_moving_object
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -83,6 +88,8 @@ ABI_SYMBOLS = [
     "gv_device_controls", "gv_get_controls", "gv_mppi_update_async", "gv_mppi_update", "gv_mppi_cycle_async",
     "gv_mppi_cycle", "gv_mppi_words", "gv_mppi_sample_controls", "gv_mppi_average",
     "gv_set_mppi_limits", "gv_mppi_constrain", "gv_get_mppi_control_costs", "gv_mppi_control_costs", "gv_mppi_average_cc",
+    "gv_dyn_cost_table", "gv_set_dyn_config", "gv_set_moving_objects", "gv_score_dynamic_async", "gv_score_dynamic",
+    "gv_dyn_score_poses", "gv_control_select_dyn",
 ]
 
 
@@ -201,6 +208,40 @@ class MppiLimits(C.Structure):
             m.u_prev[i] = float(prev[i]) if i < len(prev) else np.nan
         m.min_turn_radius, m.gamma, m.flags = float(min_turn_radius), float(gamma), int(flags)
         return m
+
+
+class DynConfig(C.Structure):
+    """gv_dyn_config: the robot as n_circles circles of one radius at off_x on its x axis, the cost table's radii,
+    scaling factor and distance quantum, the time t0 + p * dt of pose p, the collision cost and the two weights of the
+    control step"""
+    _fields_ = [("n_circles", C.c_int32), ("off_x", C.c_double * 8), ("radius", C.c_double), ("influence_radius", C.c_double),
+                ("cost_scaling_factor", C.c_double), ("quantum", C.c_double), ("t0", C.c_double), ("dt", C.c_double),
+                ("collision_cost", C.c_int32), ("w_sum", C.c_uint32), ("w_max", C.c_uint32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, off_x=(0.0,), radius=0.5, influence_radius=None, cost_scaling_factor=3.0, quantum=0.05, t0=0.0, dt=0.1,
+           collision_cost=253, w_sum=1, w_max=0, flags=0):
+        c = cls()
+        c.n_circles = len(off_x)
+        for i, v in enumerate(list(off_x)[:8]):
+            c.off_x[i] = float(v)
+        c.radius = float(radius)
+        c.influence_radius = float(radius if influence_radius is None else influence_radius)
+        c.cost_scaling_factor, c.quantum, c.t0, c.dt = float(cost_scaling_factor), float(quantum), float(t0), float(dt)
+        c.collision_cost, c.w_sum, c.w_max, c.flags = int(collision_cost), int(w_sum), int(w_max), int(flags)
+        return c
+
+
+def moving_objects(rows):
+    """a MOVING_OBJECT_DTYPE array from rows of (px, py, yaw, length, width, vx, vy): the quaternion is that of the yaw
+    about z"""
+    rows = np.asarray(rows, np.float64).reshape(-1, 7)
+    o = np.zeros(len(rows), MOVING_OBJECT_DTYPE)
+    o["pose"]["px"], o["pose"]["py"] = rows[:, 0], rows[:, 1]
+    o["pose"]["qz"], o["pose"]["qw"] = np.sin(0.5 * rows[:, 2]), np.cos(0.5 * rows[:, 2])
+    o["pose"]["length"], o["pose"]["width"] = rows[:, 3], rows[:, 4]
+    o["vx"], o["vy"] = rows[:, 5], rows[:, 6]
+    return o
 
 
 class FrameDesc(C.Structure):
@@ -473,6 +514,50 @@ def control_select(weights, traj, nav=None, keep_totals=False):
     rc = load().gv_control_select(C.byref(weights), _ptr(traj), _ptr(nav), C.c_int32(len(traj)), _ptr(res), _ptr(totals))
     if rc:
         raise GVError(rc, "gv_control_select")
+    return (res[0], totals[:len(traj)]) if keep_totals else res[0]
+
+
+def _objects(objs):
+    return np.ascontiguousarray(objs if objs is not None else [], MOVING_OBJECT_DTYPE).reshape(-1)
+
+
+def dyn_cost_table(cfg):
+    """the uint8 cost table (T entries) a DynConfig gives (host only; needs no GPU)"""
+    table = np.zeros(4096, np.uint8)
+    n = C.c_int32(0)
+    rc = load().gv_dyn_cost_table(C.byref(cfg), _ptr(table), C.c_int32(table.size), C.byref(n))
+    if rc:
+        raise GVError(rc, "gv_dyn_cost_table")
+    return table[:n.value].copy()
+
+
+def dyn_score_poses(cfg, objs, poses, keep_pose_cost=False):
+    """the DYN_SCORE_DTYPE records of float32 (K, P, 3) poses against MOVING_OBJECT_DTYPE objects under a DynConfig, and
+    with keep_pose_cost also the uint8 (K, P) pose costs: the library's own arithmetic with the host's sin and cos (host
+    only; needs no GPU)"""
+    src, K, P, _ = _pose_batch(poses, None)
+    o = _objects(objs)
+    scores = np.zeros(max(K, 1), DYN_SCORE_DTYPE)
+    pc = np.zeros(max(K * P, 1), np.uint8) if keep_pose_cost else None
+    rc = load().gv_dyn_score_poses(C.byref(cfg), _ptr(o), C.c_int32(len(o)), src, C.c_int32(K), C.c_int32(P), _ptr(scores),
+                                   _ptr(pc))
+    if rc:
+        raise GVError(rc, "gv_dyn_score_poses")
+    return (scores[:K], pc[:K * P].reshape(K, P)) if keep_pose_cost else scores[:K]
+
+
+def control_select_dyn(weights, traj, nav, dyn, cfg, keep_totals=False):
+    """control_select with the DYN_SCORE_DTYPE records of a DynConfig as the third critic (cfg None: control_select)"""
+    traj = np.ascontiguousarray(traj, TRAJ_SCORE_DTYPE)
+    nav = np.ascontiguousarray(nav, NAV_SCORE_DTYPE) if nav is not None else None
+    dyn = np.ascontiguousarray(dyn, DYN_SCORE_DTYPE) if dyn is not None else None
+    assert (nav is None or len(nav) == len(traj)) and (dyn is None or len(dyn) == len(traj))
+    res = np.zeros(1, CONTROL_RESULT_DTYPE)
+    totals = np.zeros(max(len(traj), 1), np.uint64) if keep_totals else None
+    rc = load().gv_control_select_dyn(C.byref(weights), _ptr(traj), _ptr(nav), _ptr(dyn), C.byref(cfg) if cfg is not None else None,
+                                      C.c_int32(len(traj)), _ptr(res), _ptr(totals))
+    if rc:
+        raise GVError(rc, "gv_control_select_dyn")
     return (res[0], totals[:len(traj)]) if keep_totals else res[0]
 
 
@@ -918,6 +1003,36 @@ class GridVisionHIP:
         self._ck(self._lib.gv_score_trajectories(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores),
                                                  _ptr(pc)), "gv_score_trajectories")
         return (scores, pc.reshape(K, P)) if keep_pose_cost else scores
+
+    # ---- [EXTENSION] trajectory scoring against predicted moving objects
+    def set_dyn_config(self, cfg):
+        """the DynConfig of the score_dynamic() calls, control steps and MPPI updates that follow; None turns it off"""
+        self._ck(self._lib.gv_set_dyn_config(self._h, C.byref(cfg) if cfg is not None else None), "gv_set_dyn_config")
+
+    def set_moving_objects(self, objs):
+        """replace the set of moving objects: a MOVING_OBJECT_DTYPE array of at most 128 (None or empty: no objects);
+        ordered on stream() between the calls before and after it"""
+        o = _objects(objs)
+        self._ck(self._lib.gv_set_moving_objects(self._h, _ptr(o) if len(o) else None, C.c_int32(len(o))), "gv_set_moving_objects")
+
+    def score_dynamic_async(self, poses, K, P, scores, pose_cost=None, device_ptr=None):
+        """enqueue on stream(): poses as in score_trajectories_async, scores a DYN_SCORE_DTYPE array of K, pose_cost None
+        or a uint8 array of K * P; both complete after synchronize()"""
+        src, K, P, flags = _pose_batch(poses, device_ptr, K, P)
+        flags |= TRAJ_KEEP_POSE_COST if pose_cost is not None else 0
+        self._ck(self._lib.gv_score_dynamic_async(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores),
+                                                  _ptr(pose_cost)), "gv_score_dynamic_async")
+
+    def score_dynamic(self, poses, keep_pose_cost=False, device_ptr=None):
+        """poses: float32 (K, P, 3) as in score_trajectories.  Returns the DYN_SCORE_DTYPE array of K, and with
+        keep_pose_cost also the uint8 (K, P) pose costs."""
+        src, K, P, flags = _pose_batch(poses, device_ptr)
+        flags |= TRAJ_KEEP_POSE_COST if keep_pose_cost else 0
+        scores = np.zeros(max(K, 1), DYN_SCORE_DTYPE)
+        pc = np.zeros(max(K * P, 1), np.uint8) if keep_pose_cost else None
+        self._ck(self._lib.gv_score_dynamic(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores), _ptr(pc)),
+                 "gv_score_dynamic")
+        return (scores[:K], pc[:K * P].reshape(K, P)) if keep_pose_cost else scores[:K]
 
     # ---- [EXTENSION] goal / path distance field over the resident costmap
     def set_nav_config(self, obstacle_cost=253, cost_weight=0):

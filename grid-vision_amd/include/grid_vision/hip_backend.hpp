@@ -332,6 +332,21 @@ public:
     gv::check(gv_get_mppi_control_costs(ctx_.handle(), g.data()), ctx_.handle(), "gv_get_mppi_control_costs");
     return g;
   }
+  // [EXTENSION] X13 predicted moving objects: the dynamic boxes of a tick (LShapePose) with a velocity each.  With a
+  // configuration set, controlStep() and mppiCycle() also score the resident rollout against them, each pose at its own
+  // time; scoreDynamic() is the sampler alone.  clearDynConfig() turns it off.
+  void setDynConfig(const gv_dyn_config &c) { gv::check(gv_set_dyn_config(ctx_.handle(), &c), ctx_.handle(), "gv_set_dyn_config"); }
+  void clearDynConfig() { gv::check(gv_set_dyn_config(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_dyn_config"); }
+  void setMovingObjects(const std::vector<gv_moving_object> &objs)
+  {
+    gv::check(gv_set_moving_objects(ctx_.handle(), objs.data(), (int32_t)objs.size()), ctx_.handle(), "gv_set_moving_objects");
+  }
+  std::vector<gv_dyn_score> scoreDynamic(const std::vector<float> &poses, int32_t K, int32_t P)
+  {
+    std::vector<gv_dyn_score> scores((size_t)K);
+    gv::check(gv_score_dynamic(ctx_.handle(), poses.data(), K, P, 0u, scores.data(), nullptr), ctx_.handle(), "gv_score_dynamic");
+    return scores;
+  }
   // the host twins (no handle): the chain over controls[K][P][C] in place, e.g. K = 1 for the command to execute; the
   // control costs; the sequential average with them
   static void mppiConstrain(const gv_mppi_limits &l, const gv_motion_model &m, std::vector<float> &controls, int32_t K, int32_t P)

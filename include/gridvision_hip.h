@@ -818,6 +818,110 @@ int gv_mppi_average_cc(const gv_mppi_config *cfg, int32_t C, const float *contro
                        const double *control_costs /* may be NULL: gv_mppi_average */, int32_t K, int32_t P,
                        const float *nominal_in, float *nominal_out);
 
+/* ------------------------------ [EXTENSION] scoring against predicted moving objects (planner) -- */
+/* X13.  The costmap X7 scores against is a snapshot: a car that crosses the path is lethal where it was at the last map
+ * update and free where it will be when the robot gets there.  gv_score_dynamic tests every pose of K trajectories
+ * against a set of moving oriented rectangles -- what gv_tick returns as gv_lshape_pose, plus a velocity -- propagated
+ * at constant velocity to the pose's own time, and gives one integer record per trajectory, which the control step and
+ * the MPPI update use like the X7 and X9 records.  The reference has no such step; this text is its definition.  With
+ * no configuration set (the state after gv_create) every X10 .. X12 call gives the bytes it gave before.
+ *
+ * Robot.  n_circles circles of one radius with their centres at (off_x[i], 0) in the robot frame, x forward.
+ * Cost table.  table[q] for q = 0 .. d2max is what gv_inflation_cost_table returns for {inscribed_radius = radius,
+ *   inflation_radius = influence_radius, cost_scaling_factor, lethal_threshold = 100, flags = 0} at resolution =
+ *   quantum -- the same host code: 254 at q == 0, 253 while sqrt(q) * quantum <= radius, then nav2's exponential, 0
+ *   beyond the influence radius.  T = d2max + 1 entries, Rc = isqrt(d2max) <= 63 as for X6.  A moving object costs
+ *   what an inflated lethal rectangle would cost at that distance, on the 0..254 scale of the X7 costs it is added to.
+ * Object table.  Built once per gv_set_moving_objects, on the host, in fp64, every operation one operation in this
+ *   order:
+ *     c  = 1.0 - 2.0 * (qy*qy + qz*qz);    s  = 2.0 * (qw*qz + qx*qy)
+ *     hl = 0.5 * length;                   hw = 0.5 * width
+ *   the terms of gv_grid_move's yaw: no atan2 and no normalisation, THE QUATERNION IS USED AS GIVEN.  Length lies along
+ *   the heading, width across it; an identity quaternion gives the axis-aligned rectangle updateMap(poses) stamps.
+ * Per pose p (x, y, yaw: three float32 as for X7), circle i and object j, in fp64, every operation one operation in
+ *   exactly this order, never contracted:
+ *     t  = t0 + (double)p * dt
+ *     ax = (double)x,  ay = (double)y                                   when off_x[i] == 0.0 (the yaw is not read)
+ *     ax = (double)x + cy * off_x[i],  ay = (double)y + sy * off_x[i]   otherwise; cy, sy = cos, sin of (double)yaw,
+ *                                                       computed once per pose and only if some off_x != 0
+ *     ox = x_j + vx_j * t;   oy = y_j + vy_j * t
+ *     dx = ax - ox;          dy = ay - oy
+ *     lx = c_j * dx + s_j * dy;      ly = c_j * dy - s_j * dx
+ *     ex = fabs(lx) - hl_j;  ex = ex > 0.0 ? ex : 0.0      -- a NaN lands on 0.0: a NaN pose lies "inside" every object
+ *     ey = fabs(ly) - hw_j;  ey = ey > 0.0 ? ey : 0.0
+ *     d2 = ex * ex + ey * ey                               -- squared distance, circle centre to rectangle
+ * Pose cost.  m2 = the minimum of d2 over all circles and objects, +inf with no objects; u = m2 * inv_q2 with
+ *   inv_q2 = 1.0 / (quantum * quantum) computed once on the host; the cost is u < (double)T ? table[(uint32_t)u] : 0.
+ *   A minimum over finite-or-inf fp64 values does not depend on order, so no order shows in any field.
+ * Per trajectory (gv_dyn_score, 24 bytes): max_cost, first_collision and cost_sum as for X7 over these pose costs;
+ *   min_dist2 the smallest d2 over poses, circles and objects (+inf with no objects); nearest_object the smallest j
+ *   whose own minimum over poses and circles equals min_dist2 (-1 with no objects).
+ *   On the device cos and sin are the device library's, in gv_dyn_score_poses the C library's; they may differ in the
+ *   last bit.  When every off_x is 0 neither is called and the two agree byte for byte.
+ *
+ * gv_dyn_cost_table is host only and takes no handle, in the manner of gv_inflation_cost_table: *n = T whenever the
+ *   configuration is valid; GV_ERR_BAD_ARG for a null or invalid configuration, a null table or cap < T.
+ * gv_set_dyn_config is handle configuration like gv_set_footprint: no device work, kept through gv_reset,
+ *   gv_set_log_odds and gv_grid_move; NULL turns it off (the state after gv_create).  Every enqueued call keeps the
+ *   configuration and the table it was enqueued with (the table reaches the device through X6's alternating slots).
+ *   GV_ERR_BAD_ARG, configuration unchanged, for a null handle or any field outside the ranges written beside it.
+ * gv_set_moving_objects replaces the set: n in 0..128, objs may be NULL when n == 0; every field that is read must be
+ *   finite, length and width >= 0, else GV_ERR_BAD_ARG and the set is unchanged.  The caller's array is free on return.
+ *   The set is stream-ordered on gv_stream(h): calls enqueued before it keep the old set, calls after it see the new
+ *   one.  It is kept through gv_reset; the state after gv_create is n = 0.
+ * gv_score_dynamic_async takes the arguments, flags (GV_TRAJ_KEEP_POSE_COST, GV_TRAJ_DEVICE_POSES), limits and
+ *   destination rules of gv_score_trajectories_async; pinned scores aligned to 8 bytes are written by the kernel.  It
+ *   needs neither a grid nor a costmap: GV_ERR_STATE only without a configuration.  K == 0 is a successful no-op.
+ *   Allowed between gv_tick_enqueue and gv_tick_wait.  gv_score_dynamic is the same call followed by the wait.
+ * gv_dyn_score_poses is host only and takes no handle: the same arithmetic text compiled for the host (pose_cost may
+ *   be NULL; the rules of the three calls above on cfg, objs, n, K and P).
+ *
+ * Control step.  dyn_used holds iff a configuration is set.  Then gv_control_step*, gv_mppi_update* and gv_mppi_cycle*
+ *   launch this sampler over the resident rollout between the nav sampler and the selection, trajectory k is also
+ *   REJECTED when dyn[k].first_collision >= 0, and an admitted total gains
+ *     w_sum * cost_sum + w_max * max_cost      (max_cost taken as uint32),
+ *   at most 65535 * (4096 * 255 + 255) more: the total stays below 2^61.  With zero objects every dyn record is
+ *   {0, -1, 0, -1, +inf} and the totals are those without a configuration.
+ *   gv_control_select_dyn is the host twin: gv_control_select with the third record; cfg gives w_sum and w_max.  With
+ *   cfg == NULL it is gv_control_select (dyn is not read); with one, GV_ERR_BAD_ARG for a null dyn or weights above
+ *   65535. */
+typedef struct {
+  gv_lshape_pose pose;   /* frame of the trajectory poses (base_link at the last map update): px, py, the quaternion,
+                            length, width are read; pz and height are ignored */
+  double vx, vy;         /* m/s in that frame */
+} gv_moving_object;      /* 96 bytes */
+typedef struct {
+  int32_t n_circles;            /* 1..8: the robot is n circles of one radius on its x axis */
+  double off_x[8];              /* m, robot frame, x forward; the first n_circles are read, all finite */
+  double radius;                /* m, finite, >= 0: circle radius, any safety margin included */
+  double influence_radius;      /* m, finite, >= radius: a centre farther than this from every object costs 0 */
+  double cost_scaling_factor;   /* 1/m, finite, >= 0 */
+  double quantum;               /* m, finite, > 0: distance step of the cost table; Rc <= 63 as for X6 */
+  double t0, dt;                /* s, finite, dt >= 0: pose p is at time t0 + p * dt */
+  int32_t collision_cost;       /* 1..255: a pose collides when its cost is >= this */
+  uint32_t w_sum, w_max;        /* 0..65535: weights in the control step */
+  uint32_t flags;               /* 0 */
+} gv_dyn_config;
+typedef struct {
+  int32_t max_cost;          /* maximum pose cost */
+  int32_t first_collision;   /* smallest pose index with cost >= collision_cost, -1 when none */
+  uint32_t cost_sum;         /* sum of the pose costs */
+  int32_t nearest_object;    /* smallest object index that attains min_dist2, -1 with no objects */
+  double min_dist2;          /* smallest d2 over poses, circles and objects; +inf with no objects */
+} gv_dyn_score;              /* 24 bytes */
+int gv_dyn_cost_table(const gv_dyn_config *cfg, uint8_t *table, int32_t cap, int32_t *n);
+int gv_set_dyn_config(gv_handle h, const gv_dyn_config *cfg);   /* NULL = off, the state after gv_create */
+int gv_set_moving_objects(gv_handle h, const gv_moving_object *objs, int32_t n);
+int gv_score_dynamic_async(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_dyn_score *scores,
+                           uint8_t *pose_cost);
+int gv_score_dynamic(gv_handle h, const float *poses, int32_t K, int32_t P, uint32_t flags, gv_dyn_score *scores,
+                     uint8_t *pose_cost);
+int gv_dyn_score_poses(const gv_dyn_config *cfg, const gv_moving_object *objs, int32_t n, const float *poses, int32_t K,
+                       int32_t P, gv_dyn_score *scores, uint8_t *pose_cost /* may be NULL */);
+int gv_control_select_dyn(const gv_critic_weights *w, const gv_traj_score *traj, const gv_nav_score *nav,
+                          const gv_dyn_score *dyn, const gv_dyn_config *cfg, int32_t K, gv_control_result *result,
+                          uint64_t *totals /* may be NULL */);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
@@ -919,7 +1023,7 @@ typedef struct {
  * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map*,
  * gv_grid_move, gv_set_transforms, gv_set_height_band, gv_set_inflation, gv_inflate, the costmap getters,
  * gv_set_footprint, gv_score_trajectories*, gv_set_motion_model, gv_rollout*, the rollout getters and
- * gv_control_step* may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
+ * gv_control_step*, gv_set_dyn_config, gv_set_moving_objects and gv_score_dynamic* may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
  * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
  * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform or height
  * band set in between applies from the next tick on.  (tests/test_gpu_tick.py) */
