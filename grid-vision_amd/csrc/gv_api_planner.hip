@@ -10,8 +10,10 @@
 //                   (gv_set_mppi_limits, gv_mppi_constrain, gv_*mppi_control_costs, gv_mppi_average_cc).
 //   [EXTENSION] X13 scoring of trajectories against predicted moving objects, as a call of its own and as a third
 //                   record of the control step (gv_set_dyn_config, gv_set_moving_objects, gv_score_dynamic*).
+//   [EXTENSION] X14 the tracker over the tick's boxes that gives those objects their velocities, and can feed X13's set
+//                   on the device (gv_set_track_config, gv_set_tracks, gv_get_tracks, gv_track_update*, gv_track_step).
 // The kernels are gv_inflate.hip, gv_trajscore.hip, gv_navfield.hip (which also argues why the rounds end at the
-// exact field), gv_rollout.hip, gv_mppi.hip and gv_dynscore.hip.  What the two samplers do alike, and what a control step and an MPPI
+// exact field), gv_rollout.hip, gv_mppi.hip, gv_dynscore.hip and gv_track.hip.  What the two samplers do alike, and what a control step and an MPPI
 // update enqueue alike, is written once, in front of the entry points.
 #include <algorithm>
 #include <cstring>
@@ -168,6 +170,51 @@ int upload_slot(gv_context *h, gv_context::UploadSlots &u, const void *src, size
   return GV_OK;
 }
 
+// A slot of X13's object table: the rows, and behind them the count that a fed gv_track_update (X14) writes.
+constexpr size_t kDynRowsBytes = (size_t)kDynMaxObjects * sizeof(DynObject);
+constexpr size_t kDynSlotBytes = kDynRowsBytes + 16;
+
+// ---- X14: what the device calls and the host twin check alike
+bool transform_finite(const gv_transform &m)
+{
+  const double v[] = {m.qx, m.qy, m.qz, m.qw, m.tx, m.ty, m.tz};
+  for (double x : v)
+    if (!std::isfinite(x)) return false;
+  return true;
+}
+
+bool track_update_ok(const gv_lshape_pose *dets, int32_t n, double dt, const gv_transform *motion)
+{
+  return n >= 0 && n <= kTrackSlots && (n == 0 || dets) && std::isfinite(dt) && dt >= 0.0 && (!motion || transform_finite(*motion));
+}
+
+// gv_set_tracks' rules into a state block; false (st untouched) when they do not hold
+bool track_state_from(const gv_track *tracks, int32_t n, uint32_t next_id, TrackState &st)
+{
+  if (n < 0 || n > kTrackSlots || (n > 0 && !tracks)) return false;
+  for (int32_t i = 0; i < n; ++i)
+    if (tracks[i].slot < 0 || tracks[i].slot >= kTrackSlots || (i > 0 && tracks[i].slot <= tracks[i - 1].slot)) return false;
+  std::memset(&st, 0, sizeof(st));
+  for (int32_t i = 0; i < n; ++i) {
+    st.t[tracks[i].slot] = tracks[i];
+    st.live[tracks[i].slot] = 1;
+  }
+  st.next_id = next_id;
+  return true;
+}
+
+// gv_get_tracks' order: the live records in ascending slot order into out when they fit; returns their number
+int32_t track_state_live(const TrackState &st, gv_track *out, int32_t cap)
+{
+  int32_t n = 0;
+  for (int32_t s = 0; s < kTrackSlots; ++s) n += st.live[s] ? 1 : 0;
+  if (!out || cap < n) return n;
+  int32_t k = 0;
+  for (int32_t s = 0; s < kTrackSlots; ++s)
+    if (st.live[s]) out[k++] = st.t[s];
+  return n;
+}
+
 // What every launch of the dyn sampler carries, with the configuration and the set in force now; a changed cost table
 // goes to the device first.
 int dyn_kernel_args(gv_context *h, DynArgs &a)
@@ -181,6 +228,7 @@ int dyn_kernel_args(gv_context *h, DynArgs &a)
   a.p = dyn_params(d.cfg, d.tab.d2max + 1);
   a.objs = reinterpret_cast<const DynObject *>(d.objs.dev[d.objs.slot].get());
   a.n_obj = d.n_obj;
+  a.n_obj_dev = d.n_obj_dev;
   a.table = d.table.dev[d.table.slot];
   return GV_OK;
 }
@@ -1217,9 +1265,10 @@ int gv_set_moving_objects(gv_handle h, const gv_moving_object *objs, int32_t n)
     if (rc) return rc;
     DynObject rows[kDynMaxObjects];
     for (int32_t j = 0; j < n; ++j) rows[j] = dyn_object(objs[j]);
-    if ((rc = upload_slot(h, d.objs, rows, (size_t)n * sizeof(DynObject), sizeof(rows)))) return rc;
+    if ((rc = upload_slot(h, d.objs, rows, (size_t)n * sizeof(DynObject), kDynSlotBytes))) return rc;
   }
   d.n_obj = n;
+  d.n_obj_dev = nullptr;   // a set a gv_track_update fed (X14) ends here
   return GV_OK;
   GV_CATCH
 }
@@ -1301,6 +1350,149 @@ int gv_control_select_dyn(const gv_critic_weights *w, const gv_traj_score *traj,
     return GV_ERR_BAD_ARG;
   control_select_host(*w, traj, nav, dyn, cfg->w_sum, cfg->w_max, K, result, totals);
   return GV_OK;
+}
+
+// ---- [EXTENSION] X14: the tracker over the tick's boxes ----
+// handle configuration: it travels in the kernel arguments of the updates enqueued from now on.  Turning it off makes
+// the state the one after gv_create without touching the device: the next update is told to ignore the block.
+int gv_set_track_config(gv_handle h, const gv_track_config *cfg)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  gv_context::Track &t = h->trk;
+  if (!cfg) {
+    t.set = false;
+    t.fresh = true;
+    return GV_OK;
+  }
+  if (!track_config_valid(*cfg)) return GV_ERR_BAD_ARG;
+  t.cfg = *cfg;
+  t.set = true;
+  return GV_OK;
+}
+
+// The block is built on the host into a pinned staging slot and replaces the resident one by one copy command on the
+// public stream, behind the updates enqueued before it.
+int gv_set_tracks(gv_handle h, const gv_track *tracks, int32_t n, uint32_t next_id)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  TrackState st;
+  if (!track_state_from(tracks, n, next_id, st)) return GV_ERR_BAD_ARG;
+  gv_context::Track &t = h->trk;
+  int rc = GV_OK;
+  if ((rc = set_device_only(h)) || (rc = t.state.reserve(h, 1))) return rc;
+  const int k = t.up.slot ^ 1;
+  if ((rc = t.up.stage[k].reserve(h, sizeof(TrackState), hipHostMallocDefault))) return rc;
+  if (!t.up.staged[k]) GV_HIP(t.up.staged[k].create(hipEventDisableTiming));
+  if (t.up.staged_used[k]) GV_HIP(hipEventSynchronize(t.up.staged[k]));
+  std::memcpy(t.up.stage[k].get(), &st, sizeof(st));
+  GV_HIP(hipMemcpyAsync(t.state.get(), t.up.stage[k].get(), sizeof(st), hipMemcpyHostToDevice, h->stream));
+  GV_HIP(hipEventRecord(t.up.staged[k], h->stream));
+  t.up.staged_used[k] = true;
+  t.up.slot = k;
+  t.fresh = false;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_get_tracks(gv_handle h, gv_track *out, int32_t cap, int32_t *n, uint32_t *next_id)
+{
+  if (!h || cap < 0 || (cap > 0 && !out)) return GV_ERR_BAD_ARG;
+  GV_TRY
+  gv_context::Track &t = h->trk;
+  std::vector<TrackState> st(1);
+  if (t.fresh) {
+    std::memset(st.data(), 0, sizeof(TrackState));
+    st[0].next_id = 1u;
+  } else {
+    if (int rc = set_device_only(h)) return rc;
+    GV_HIP(hipMemcpyAsync(st.data(), t.state.get(), sizeof(TrackState), hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipStreamSynchronize(h->stream));
+  }
+  const int32_t live = track_state_live(st[0], out, cap);
+  if (n) *n = live;
+  if (next_id) *next_id = st[0].next_id;
+  return live <= cap ? GV_OK : GV_ERR_BAD_ARG;
+  GV_CATCH
+}
+
+// One kernel on the public stream; with GV_TRACK_FEED_DYNAMIC it also writes the slot of X13's object table that is not
+// the current one -- every kernel that was given that slot is ahead of it on the stream -- and the slot is the current
+// one for the calls enqueued from now on, with its count on the device.
+int gv_track_update_async(gv_handle h, const gv_lshape_pose *dets, int32_t n, double dt, const gv_transform *motion,
+                          uint32_t flags, gv_track_info *info, gv_track *tracks)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!track_update_ok(dets, n, dt, motion) || (flags & ~(uint32_t)(GV_TRACK_DEVICE_DETS | GV_TRACK_FEED_DYNAMIC)) != 0)
+    return GV_ERR_BAD_ARG;
+  gv_context::Track &t = h->trk;
+  gv_context::DynScore &d = h->dyn;
+  if (!t.set) {
+    h->err = "gv_track_update: no configuration set (gv_set_track_config)";
+    return GV_ERR_STATE;
+  }
+  const bool feed = (flags & GV_TRACK_FEED_DYNAMIC) != 0;
+  const int k = d.objs.slot ^ 1;
+  int rc = GV_OK;
+  if ((rc = set_device_only(h)) || (rc = t.state.reserve(h, 1)) || (feed && (rc = d.objs.dev[k].reserve(h, kDynSlotBytes)))) return rc;
+  TrackArgs a{};
+  a.p = track_params(t.cfg);
+  a.ego = track_ego(motion);
+  a.dt = dt;
+  a.fresh = t.fresh ? 1 : 0;
+  a.n = n;
+  a.dets = dets;
+  if (n > 0 && !(flags & GV_TRACK_DEVICE_DETS)) {
+    if ((rc = upload_slot(h, t.dets, dets, (size_t)n * sizeof(gv_lshape_pose), (size_t)kTrackSlots * sizeof(gv_lshape_pose)))) return rc;
+    a.dets = reinterpret_cast<const gv_lshape_pose *>(t.dets.dev[t.dets.slot].get());
+  }
+  a.state = t.state;
+  ResultDest<gv_track_info> to_info;   // each stays closed (null, no copy) when the caller passes null
+  ResultDest<gv_track> to_tracks;
+  if ((info && (rc = to_info.open(h, info, 1, 8, t.d_info))) || (tracks && (rc = to_tracks.open(h, tracks, (size_t)kTrackSlots, 8, t.d_tracks))))
+    return rc;
+  a.info = to_info.dev;
+  a.tracks = to_tracks.dev;
+  if (feed) {
+    a.feed_objs = reinterpret_cast<DynObject *>(d.objs.dev[k].get());
+    a.feed_n = reinterpret_cast<int32_t *>(d.objs.dev[k].get() + kDynRowsBytes);
+  }
+  launch_track_update(a, h->stream);
+  GV_HIP(hipGetLastError());
+  t.fresh = false;
+  if (feed) {
+    d.objs.slot = k;
+    d.n_obj = kDynMaxObjects;   // the host does not learn the count: up to 128
+    d.n_obj_dev = a.feed_n;
+  }
+  if ((rc = to_info.copy_back(h)) || (rc = to_tracks.copy_back(h))) return rc;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_track_update(gv_handle h, const gv_lshape_pose *dets, int32_t n, double dt, const gv_transform *motion, uint32_t flags,
+                    gv_track_info *info, gv_track *tracks)
+{
+  return wait_scored(h, gv_track_update_async(h, dets, n, dt, motion, flags, info, tracks), 1);
+}
+
+// host only: gv_track.hpp's text, the association as a literal sort
+int gv_track_step(const gv_track_config *cfg, gv_track *tracks, int32_t *n_tracks, uint32_t *next_id, const gv_lshape_pose *dets,
+                  int32_t n, double dt, const gv_transform *motion, gv_track_info *info, gv_moving_object *objs, int32_t *n_objs)
+{
+  gv_context *h = nullptr;
+  if (!cfg || !track_config_valid(*cfg) || !tracks || !n_tracks || !next_id || !track_update_ok(dets, n, dt, motion) ||
+      (objs != nullptr) != (n_objs != nullptr))
+    return GV_ERR_BAD_ARG;
+  GV_TRY
+  std::vector<TrackState> st(1);
+  if (!track_state_from(tracks, *n_tracks, *next_id, st[0])) return GV_ERR_BAD_ARG;
+  track_step(track_params(*cfg), st[0], dets, n, dt, motion, info, objs, n_objs);
+  *n_tracks = track_state_live(st[0], tracks, kTrackSlots);
+  *next_id = st[0].next_id;
+  return GV_OK;
+  GV_CATCH
 }
 
 }  // extern "C"

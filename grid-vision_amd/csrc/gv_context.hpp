@@ -433,7 +433,27 @@ struct __attribute__((visibility("hidden"))) gv_context {
     UploadSlots objs;
     DevBuf<gv_dyn_score> d_scores;
     DevBuf<uint8_t> d_pose_cost;
+    // [EXTENSION] X14: non-null when the set in force was written on the device by a fed gv_track_update; it points
+    // at the count beside the rows of objs' current slot, and n_obj is then the bound 128.
+    const int32_t *n_obj_dev = nullptr;
   } dyn;
+  // [EXTENSION] X14 the tracker over the tick's boxes (gv_set_track_config / gv_set_tracks / gv_get_tracks /
+  // gv_track_update*).  The configuration is handle state and travels in the kernel arguments.  The 128 slots and
+  // next_id are resident in `state`, which the one update kernel rewrites in place on the public stream; `fresh` says
+  // that the state is the one after gv_create (no tracks, next_id 1) whatever the block holds, so that turning the
+  // tracker off needs no device work.  gv_set_tracks goes through `up`'s staging slots (its device slots stay empty).
+  // Host detections go through `dets`' alternating slots like X13's object table (the caller's array is free on return).  d_info and
+  // d_tracks are the landing buffers of destinations that are not pinned.  gv_reset keeps all of it.
+  struct Track {
+    bool set = false;
+    gv_track_config cfg{};
+    bool fresh = true;
+    DevBuf<TrackState> state;
+    UploadSlots up;
+    UploadSlots dets;
+    DevBuf<gv_track_info> d_info;
+    DevBuf<gv_track> d_tracks;
+  } trk;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
   // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in

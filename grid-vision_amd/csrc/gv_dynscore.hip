@@ -17,7 +17,8 @@
 //   record   after the last chunk: integer maximum, sum and minimum and the (d2, j) minimum across the wavefront by
 //            shuffles, one 24-byte record per trajectory from one lane.  No atomics, no order shows.
 // Bounds: pose p0 + lane is read only below P, trajectory k only below K (the grid is K workgroups), objects only
-// below n_obj <= 128 = the LDS rows, table entries only at (uint32_t)u with u < T <= the LDS bytes.
+// below n_obj <= 128 = the LDS rows (a count read from the device, X14's fed set, is clamped to 0..128 first), table
+// entries only at (uint32_t)u with u < T <= the LDS bytes.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
 #include "gv_device.hpp"
 #include "gv_dyn.hpp"
@@ -30,6 +31,9 @@ constexpr int kWaves = 4;       // wavefronts per workgroup: they share the obje
 constexpr int kTableMax = 4096; // (63 + 1)^2: more than any table with Rc <= 63 holds
 }  // namespace
 
+// kFed: the set was written on the device by a fed gv_track_update (X14) and its count is read from there; the other
+// instantiation is the kernel as it was, n_obj from the arguments.
+template <bool kFed>
 __global__ void __launch_bounds__(kChunk *kWaves) k_score_dynamic(DynArgs a)
 {
   __shared__ __attribute__((aligned(16))) DynObject obj_s[kDynMaxObjects];
@@ -40,7 +44,9 @@ __global__ void __launch_bounds__(kChunk *kWaves) k_score_dynamic(DynArgs a)
   const int k = (int)blockIdx.x;
   if (k >= a.K) return;
   const int P = a.P;
-  const int n_obj = min(a.n_obj, kDynMaxObjects), T = min(a.p.T, kTableMax);
+  // a fed set has its count on the device: one uniform read per workgroup, clamped to the rows
+  const int n_obj = kFed ? max(0, min(*a.n_obj_dev, kDynMaxObjects)) : min(a.n_obj, kDynMaxObjects);
+  const int T = min(a.p.T, kTableMax);
   const float *traj = a.poses + (size_t)k * (size_t)P * 3u;
 
   {
@@ -90,7 +96,8 @@ __global__ void __launch_bounds__(kChunk *kWaves) k_score_dynamic(DynArgs a)
 
 void launch_score_dynamic(const DynArgs &a, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_score_dynamic, dim3((uint32_t)a.K), dim3(kChunk * kWaves), 0, s, a);
+  if (a.n_obj_dev) hipLaunchKernelGGL(k_score_dynamic<true>, dim3((uint32_t)a.K), dim3(kChunk * kWaves), 0, s, a);
+  else hipLaunchKernelGGL(k_score_dynamic<false>, dim3((uint32_t)a.K), dim3(kChunk * kWaves), 0, s, a);
 }
 
 }  // namespace gv

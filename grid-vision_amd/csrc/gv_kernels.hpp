@@ -6,6 +6,7 @@
 
 #include "gv_types.hpp"
 #include "gv_dyn.hpp"
+#include "gv_track.hpp"
 
 namespace gv {
 
@@ -255,8 +256,26 @@ struct DynArgs {
   const uint8_t *table;         // p.T costs (device)
   gv_dyn_score *scores;         // K records (device memory, or the device view of pinned host memory; 8-byte aligned)
   uint8_t *pose_cost;           // K * P, or null
+  const int32_t *n_obj_dev;     // [EXTENSION] X14: null, or the count of a set a fed gv_track_update wrote on the device;
+                                // read once per workgroup, clamped to 0 .. kDynMaxObjects, and n_obj is not used
 };
 void launch_score_dynamic(const DynArgs &a, hipStream_t s);
+// [EXTENSION] X14 one update of the tracker (gv_track.hip; the arithmetic is gv_track.hpp's).  The configuration, dt and
+// the motion travel by value.  One workgroup rewrites `state` in place.
+struct TrackArgs {
+  TrackParams p;
+  TrackEgo ego;                 // ego.on == 0: no motion given
+  double dt;
+  int32_t fresh;                // != 0: the state is the one after gv_create whatever the block holds
+  int32_t n;                    // detections, 0 .. kTrackSlots
+  const gv_lshape_pose *dets;   // n records (device); not read when n == 0
+  TrackState *state;            // device
+  gv_track_info *info;          // one record or null (device memory, or the device view of pinned host memory)
+  gv_track *tracks;             // kTrackSlots records or null (likewise; 8-byte aligned)
+  DynObject *feed_objs;         // kTrackSlots rows of X13's object table or null (device)
+  int32_t *feed_n;              // their count, beside them; null with feed_objs
+};
+void launch_track_update(const TrackArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

@@ -56,6 +56,17 @@ DYN_SCORE_DTYPE = np.dtype([("max_cost", np.int32), ("first_collision", np.int32
                             ("nearest_object", np.int32), ("min_dist2", np.float64)])   # gv_dyn_score
 MOVING_OBJECT_DTYPE = np.dtype([("pose", LSHAPE_DTYPE), ("vx", np.float64), ("vy", np.float64)])   # gv_moving_object
 
+TRACK_SLOTS = 128
+TRACK_DEVICE_DETS = 1 << 0
+TRACK_FEED_DYNAMIC = 1 << 1
+TRACK_DTYPE = np.dtype([("id", np.uint32), ("slot", np.int32), ("hits", np.int32), ("misses", np.int32), ("age", np.int32),
+                        ("det", np.int32)] + [(n, np.float64) for n in ("x", "y", "vx", "vy", "qx", "qy", "qz", "qw", "length",
+                                                                         "width", "p00", "p01", "p11")])   # gv_track
+TRACK_INFO_DTYPE = np.dtype([(n, np.int32) for n in ("n_tracks", "n_confirmed", "n_exported", "n_matched", "n_born", "n_deleted",
+                                                     "n_dropped", "n_invalid")] +
+                            [("next_id", np.uint32), ("reserved", np.uint32)])   # gv_track_info
+assert TRACK_DTYPE.itemsize == 128 and TRACK_INFO_DTYPE.itemsize == 40
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -90,6 +101,7 @@ ABI_SYMBOLS = [
     "gv_set_mppi_limits", "gv_mppi_constrain", "gv_get_mppi_control_costs", "gv_mppi_control_costs", "gv_mppi_average_cc",
     "gv_dyn_cost_table", "gv_set_dyn_config", "gv_set_moving_objects", "gv_score_dynamic_async", "gv_score_dynamic",
     "gv_dyn_score_poses", "gv_control_select_dyn",
+    "gv_set_track_config", "gv_set_tracks", "gv_get_tracks", "gv_track_update_async", "gv_track_update", "gv_track_step",
 ]
 
 
@@ -230,6 +242,18 @@ class DynConfig(C.Structure):
         c.cost_scaling_factor, c.quantum, c.t0, c.dt = float(cost_scaling_factor), float(quantum), float(t0), float(dt)
         c.collision_cost, c.w_sum, c.w_max, c.flags = int(collision_cost), int(w_sum), int(w_max), int(flags)
         return c
+
+
+class TrackConfig(C.Structure):
+    """gv_track_config: the association gate, the filter's three sigmas, the speed below which a track is exported as
+    standing, the hits that confirm a track and the consecutive misses it survives"""
+    _fields_ = [("gate", C.c_double), ("sigma_accel", C.c_double), ("sigma_meas", C.c_double), ("sigma_v0", C.c_double),
+                ("min_speed", C.c_double), ("confirm_hits", C.c_int32), ("max_misses", C.c_int32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, gate=2.0, sigma_accel=1.0, sigma_meas=0.2, sigma_v0=5.0, min_speed=0.0, confirm_hits=2, max_misses=3, flags=0):
+        return cls(float(gate), float(sigma_accel), float(sigma_meas), float(sigma_v0), float(min_speed), int(confirm_hits),
+                   int(max_misses), int(flags))
 
 
 def moving_objects(rows):
@@ -544,6 +568,35 @@ def dyn_score_poses(cfg, objs, poses, keep_pose_cost=False):
     if rc:
         raise GVError(rc, "gv_dyn_score_poses")
     return (scores[:K], pc[:K * P].reshape(K, P)) if keep_pose_cost else scores[:K]
+
+
+def _detections(dets):
+    return np.ascontiguousarray(dets if dets is not None else np.zeros(0, LSHAPE_DTYPE), LSHAPE_DTYPE).reshape(-1)
+
+
+def _motion(motion):
+    """None, a Transform, or (qx, qy, qz, qw, tx, ty, tz)"""
+    if motion is None or isinstance(motion, Transform):
+        return motion
+    return Transform(*[float(v) for v in motion])
+
+
+def track_step(cfg, tracks, next_id, dets, dt, motion=None):
+    """one update of the tracker on the host (gv_track_step; needs no GPU): tracks a TRACK_DTYPE array of the live
+    records in ascending slot order, dets an LSHAPE_DTYPE array.  Returns (tracks, next_id, info, objs): the new live
+    records, the counter, the TRACK_INFO_DTYPE record and the exported MOVING_OBJECT_DTYPE array."""
+    buf = np.zeros(TRACK_SLOTS, TRACK_DTYPE)
+    tracks = np.ascontiguousarray(tracks if tracks is not None else buf[:0], TRACK_DTYPE).reshape(-1)
+    assert len(tracks) <= TRACK_SLOTS
+    buf[:len(tracks)] = tracks
+    z = _detections(dets)
+    n_t, nid, n_o = C.c_int32(len(tracks)), C.c_uint32(int(next_id)), C.c_int32(0)
+    info, objs, m = np.zeros(1, TRACK_INFO_DTYPE), np.zeros(TRACK_SLOTS, MOVING_OBJECT_DTYPE), _motion(motion)
+    rc = load().gv_track_step(C.byref(cfg), _ptr(buf), C.byref(n_t), C.byref(nid), _ptr(z) if len(z) else None, C.c_int32(len(z)),
+                              C.c_double(dt), C.byref(m) if m is not None else None, _ptr(info), _ptr(objs), C.byref(n_o))
+    if rc != GV_OK:
+        raise GVError(rc, "gv_track_step")
+    return buf[:n_t.value].copy(), nid.value, info[0], objs[:n_o.value].copy()
 
 
 def control_select_dyn(weights, traj, nav, dyn, cfg, keep_totals=False):
@@ -1033,6 +1086,49 @@ class GridVisionHIP:
         self._ck(self._lib.gv_score_dynamic(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores), _ptr(pc)),
                  "gv_score_dynamic")
         return (scores[:K], pc[:K * P].reshape(K, P)) if keep_pose_cost else scores[:K]
+
+    # ---- [EXTENSION] the tracker over the tick's boxes
+    def set_track_config(self, cfg):
+        """the TrackConfig of the track_update() calls that follow; None turns the tracker off and empties its tracks"""
+        self._ck(self._lib.gv_set_track_config(self._h, C.byref(cfg) if cfg is not None else None), "gv_set_track_config")
+
+    def set_tracks(self, tracks, next_id=1):
+        """replace the tracker's state: a TRACK_DTYPE array of at most 128 with distinct ascending slots (None or empty:
+        no tracks) and the id counter; ordered on stream() between the calls before and after it"""
+        t = np.ascontiguousarray(tracks if tracks is not None else np.zeros(0, TRACK_DTYPE), TRACK_DTYPE).reshape(-1)
+        self._ck(self._lib.gv_set_tracks(self._h, _ptr(t) if len(t) else None, C.c_int32(len(t)), C.c_uint32(int(next_id))),
+                 "gv_set_tracks")
+
+    def get_tracks(self):
+        """(the live TRACK_DTYPE records in ascending slot order, next_id); waits for stream()"""
+        out, n, nid = np.zeros(TRACK_SLOTS, TRACK_DTYPE), C.c_int32(0), C.c_uint32(0)
+        self._ck(self._lib.gv_get_tracks(self._h, _ptr(out), C.c_int32(TRACK_SLOTS), C.byref(n), C.byref(nid)), "gv_get_tracks")
+        return out[:n.value].copy(), nid.value
+
+    def track_update_async(self, dets, dt, motion=None, feed=False, info=None, tracks=None, device_ptr=None, n=None):
+        """enqueue one update on stream(): dets an LSHAPE_DTYPE array, free on return (with
+        device_ptr and n: n records at that device address), motion None, a Transform or its seven values, feed: the
+        exported tracks become the moving objects of the scoring calls that follow; info None or a TRACK_INFO_DTYPE
+        array of 1, tracks None or a TRACK_DTYPE array of 128, both complete after synchronize()"""
+        flags = TRACK_FEED_DYNAMIC if feed else 0
+        if device_ptr is not None:
+            src, cnt, flags = C.c_void_p(int(device_ptr)), int(n), flags | TRACK_DEVICE_DETS
+        else:
+            assert dets is None or (dets.dtype == LSHAPE_DTYPE and dets.flags.c_contiguous)
+            cnt = 0 if dets is None else len(dets)
+            src = _ptr(dets) if cnt else None
+        m = _motion(motion)
+        self._ck(self._lib.gv_track_update_async(self._h, src, C.c_int32(cnt), C.c_double(dt), C.byref(m) if m is not None else None,
+                                                 C.c_uint32(flags), _ptr(info), _ptr(tracks)), "gv_track_update_async")
+
+    def track_update(self, dets, dt, motion=None, feed=False):
+        """one update, waited for: returns (info, tracks), the TRACK_INFO_DTYPE record and the live TRACK_DTYPE records"""
+        z, m = _detections(dets), _motion(motion)
+        info, tracks = np.zeros(1, TRACK_INFO_DTYPE), np.zeros(TRACK_SLOTS, TRACK_DTYPE)
+        self._ck(self._lib.gv_track_update(self._h, _ptr(z) if len(z) else None, C.c_int32(len(z)), C.c_double(dt),
+                                           C.byref(m) if m is not None else None, C.c_uint32(TRACK_FEED_DYNAMIC if feed else 0),
+                                           _ptr(info), _ptr(tracks)), "gv_track_update")
+        return info[0], tracks[:int(info[0]["n_tracks"])].copy()
 
     # ---- [EXTENSION] goal / path distance field over the resident costmap
     def set_nav_config(self, obstacle_cost=253, cost_weight=0):

@@ -6,6 +6,7 @@
 // Compiled and run without ROS by examples/flow_demo.cpp (tests/test_gpu_parity.py::test_cpp_flow_demo).
 #pragma once
 
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -44,6 +45,16 @@ struct FlowParams {
   // false (default): no costmap is made, every output of the flow is what it was.
   bool inflate_costmap = false;
   gv_inflation inflation{0.35, 0.55, 10.0, 65, 0};
+  // [EXTENSION] X14: every tick that knows its dynamic objects (an empty list included) hands them, TickInput::dt and --
+  // with ego_motion -- the motion moveMap was given to the tracker, which feeds its confirmed tracks to X13 as the moving
+  // objects of the control steps that follow (GV_TRACK_FEED_DYNAMIC): nothing comes back to the host, the call is
+  // enqueued behind the tick.  At most the first 128 poses are passed.  A tick that does not get that far (missing
+  // inputs, no transform) leaves the tracker alone; its dt is added to the next update's and its motion, which the grid
+  // has followed all the same, is composed with the next update's (compose_motion), so the tracks stay in the grid's
+  // frame.  The configuration is set once by the constructor.  false (default): no tracker, every output of the flow
+  // is what it was.
+  bool track_objects = false;
+  gv_track_config track{2.0, 2.0, 0.3, 5.0, 0.3, 2, 3, 0};
 };
 
 // what one tick of the 50 ms timer (grid_vision_node.cpp:49-50) has to work with
@@ -62,6 +73,8 @@ struct TickInput {
   // [EXTENSION] X3 (FlowParams::ego_motion): base_prev <- base_now since the previous tick, the tf2 lookup
   // lookupTransform(base, t_prev, base, t_now, odom); nullptr: no motion known this tick
   const gv_transform *motion = nullptr;
+  // [EXTENSION] X14 (FlowParams::track_objects): seconds since the previous tick; the reference's timer runs at 50 ms
+  double dt = 0.05;
 };
 
 enum class TickBranch {
@@ -84,18 +97,69 @@ struct TickResult {
   std::string warning;
 };
 
+// base_a <- base_c from base_a <- base_b (`first`, the earlier tick's motion) and base_b <- base_c (`second`): a point of
+// the newest frame goes through `second`, then through `first`.  q = q_first * q_second (Hamilton), t = R(q_first) t_second
+// + t_first with R the rotation of the quaternion taken as a unit quaternion, which tf2's are.
+inline gv_transform compose_motion(const gv_transform &first, const gv_transform &second)
+{
+  const double ax = first.qx, ay = first.qy, az = first.qz, aw = first.qw;
+  const double bx = second.qx, by = second.qy, bz = second.qz, bw = second.qw;
+  gv_transform m;
+  m.qw = aw * bw - ax * bx - ay * by - az * bz;
+  m.qx = aw * bx + ax * bw + ay * bz - az * by;
+  m.qy = aw * by - ax * bz + ay * bw + az * bx;
+  m.qz = aw * bz + ax * by - ay * bx + az * bw;
+  // v' = v + 2 w (u x v) + 2 u x (u x v), u = (ax, ay, az), w = aw
+  const double vx = second.tx, vy = second.ty, vz = second.tz;
+  const double cx = ay * vz - az * vy, cy = az * vx - ax * vz, cz = ax * vy - ay * vx;
+  const double dx = ay * cz - az * cy, dy = az * cx - ax * cz, dz = ax * cy - ay * cx;
+  m.tx = vx + 2.0 * (aw * cx + dx) + first.tx;
+  m.ty = vy + 2.0 * (aw * cy + dy) + first.ty;
+  m.tz = vz + 2.0 * (aw * cz + dz) + first.tz;
+  return m;
+}
+
 class FrameFlow {
 public:
   FrameFlow(GridVisionContext &ctx, OccupancyGridMap &grid, const FlowParams &p) : ctx_(ctx), grid_(grid), vision_(ctx), p_(p)
   {
     if (p_.lidar_height_band) grid_.setHeightBand(p_.lidar_ground_z, p_.lidar_max_obstacle_z, p_.lidar_ground_clears);
     if (p_.inflate_costmap) grid_.setInflation(p_.inflation);
+    if (p_.track_objects) grid_.setTrackConfig(p_.track);
   }
 
   // base <- camera and camera <- lidar known (transformLidarToCamera's lookup, :280-307)
   void setTransformsAvailable(bool ok) { have_tf_ = ok; }
 
   TickResult tick(const TickInput &in)
+  {
+    TickResult r = tickMap(in);
+    if (p_.track_objects) {
+      // what the tracker is owed: the time and the motion of every tick since its last update, the skipped ones included
+      // (moveMap has run for each of them)
+      track_dt_ += in.dt;
+      if (p_.ego_motion && in.motion) {
+        track_motion_ = have_track_motion_ ? compose_motion(track_motion_, *in.motion) : *in.motion;
+        have_track_motion_ = true;
+      }
+      if (r.branch != TickBranch::MissingInputs && r.branch != TickBranch::NoTransform) {
+        const std::vector<LShapePose> dets(r.bboxes_pose.begin(),
+                                           r.bboxes_pose.begin() + (std::ptrdiff_t)std::min<size_t>(r.bboxes_pose.size(), 128));
+        grid_.trackUpdateAsync(dets, track_dt_, have_track_motion_ ? &track_motion_ : nullptr, true);   // dets is free on return
+        track_dt_ = 0.0;
+        have_track_motion_ = false;
+      }
+    }
+    return r;
+  }
+
+  // pinned landing place of OccupancyGrid.data (gv_host_alloc, G bytes): the fused tick copies the packed grid there
+  // behind its grid pass; nullptr (default): the caller fetches it with toOccupancyGrid as before
+  void setGridOut(int8_t *pinned) { grid_out_ = pinned; }
+
+private:
+  // the reference's timer callback: the map side of a tick
+  TickResult tickMap(const TickInput &in)
   {
     TickResult r;
     // the vehicle moved whatever this tick goes on to do: the grid follows first, ahead of the map update
@@ -150,11 +214,6 @@ public:
     return r;
   }
 
-  // pinned landing place of OccupancyGrid.data (gv_host_alloc, G bytes): the fused tick copies the packed grid there
-  // behind its grid pass; nullptr (default): the caller fetches it with toOccupancyGrid as before
-  void setGridOut(int8_t *pinned) { grid_out_ = pinned; }
-
-private:
   // the fused form needs the tile path when the lidar extension is on (gv_tick_enqueue says so too)
   bool fusable() const
   {
@@ -215,6 +274,9 @@ private:
   FlowParams p_;
   bool have_tf_ = false;
   int8_t *grid_out_ = nullptr;
+  double track_dt_ = 0.0;                // X14: time and motion since the tracker's last update
+  gv_transform track_motion_{};
+  bool have_track_motion_ = false;
 };
 
 inline const char *branch_name(TickBranch b)

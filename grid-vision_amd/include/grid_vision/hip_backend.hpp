@@ -347,6 +347,59 @@ public:
     gv::check(gv_score_dynamic(ctx_.handle(), poses.data(), K, P, 0u, scores.data(), nullptr), ctx_.handle(), "gv_score_dynamic");
     return scores;
   }
+  // [EXTENSION] X14 the tracker that gives those objects their identity and velocity: trackUpdate() associates the
+  // boxes of a tick with the resident tracks, filters position and velocity and, with feed, makes the confirmed tracks
+  // the moving objects of the scoring calls that follow, without the set crossing the host.  motion is moveMap()'s
+  // argument for the same interval; without it the velocities are relative to the vehicle.
+  void setTrackConfig(const gv_track_config &c) { gv::check(gv_set_track_config(ctx_.handle(), &c), ctx_.handle(), "gv_set_track_config"); }
+  void clearTrackConfig() { gv::check(gv_set_track_config(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_track_config"); }
+  void setTracks(const std::vector<gv_track> &tracks, uint32_t next_id)
+  {
+    gv::check(gv_set_tracks(ctx_.handle(), tracks.data(), (int32_t)tracks.size(), next_id), ctx_.handle(), "gv_set_tracks");
+  }
+  std::vector<gv_track> getTracks(uint32_t *next_id = nullptr)
+  {
+    std::vector<gv_track> t(128);
+    int32_t n = 0;
+    gv::check(gv_get_tracks(ctx_.handle(), t.data(), 128, &n, next_id), ctx_.handle(), "gv_get_tracks");
+    t.resize((size_t)n);
+    return t;
+  }
+  // enqueued on the context's stream, no host wait; dets is free on return
+  void trackUpdateAsync(const std::vector<LShapePose> &dets, double dt, const gv_transform *motion, bool feed)
+  {
+    gv::check(gv_track_update_async(ctx_.handle(), dets.data(), (int32_t)dets.size(), dt, motion, feed ? GV_TRACK_FEED_DYNAMIC : 0u,
+                                    nullptr, nullptr),
+              ctx_.handle(), "gv_track_update_async");
+  }
+  gv_track_info trackUpdate(const std::vector<LShapePose> &dets, double dt, const gv_transform *motion, bool feed,
+                            std::vector<gv_track> *tracks = nullptr)
+  {
+    gv_track_info info{};
+    std::vector<gv_track> t(128);
+    gv::check(gv_track_update(ctx_.handle(), dets.data(), (int32_t)dets.size(), dt, motion, feed ? GV_TRACK_FEED_DYNAMIC : 0u, &info,
+                              t.data()),
+              ctx_.handle(), "gv_track_update");
+    t.resize((size_t)info.n_tracks);
+    if (tracks) *tracks = std::move(t);
+    return info;
+  }
+  // the host twin (no handle): tracks (the live records in ascending slot order) and next_id in and out; objs, when
+  // given, receives the exported objects
+  static gv_track_info trackStep(const gv_track_config &c, std::vector<gv_track> &tracks, uint32_t &next_id, const std::vector<LShapePose> &dets,
+                                 double dt, const gv_transform *motion, std::vector<gv_moving_object> *objs = nullptr)
+  {
+    gv_track_info info{};
+    int32_t n = (int32_t)tracks.size(), n_objs = 0;
+    tracks.resize(128);
+    std::vector<gv_moving_object> o(128);
+    gv::check(gv_track_step(&c, tracks.data(), &n, &next_id, dets.data(), (int32_t)dets.size(), dt, motion, &info, o.data(), &n_objs), nullptr,
+              "gv_track_step");
+    tracks.resize((size_t)n);
+    o.resize((size_t)n_objs);
+    if (objs) *objs = std::move(o);
+    return info;
+  }
   // the host twins (no handle): the chain over controls[K][P][C] in place, e.g. K = 1 for the command to execute; the
   // control costs; the sequential average with them
   static void mppiConstrain(const gv_mppi_limits &l, const gv_motion_model &m, std::vector<float> &controls, int32_t K, int32_t P)

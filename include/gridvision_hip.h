@@ -922,6 +922,142 @@ int gv_control_select_dyn(const gv_critic_weights *w, const gv_traj_score *traj,
                           const gv_dyn_score *dyn, const gv_dyn_config *cfg, int32_t K, gv_control_result *result,
                           uint64_t *totals /* may be NULL */);
 
+/* ------------------------------ [EXTENSION] tracking the detected boxes (perception -> planner) -- */
+/* X14.  X13 takes a velocity for each rectangle, and gv_tick returns gv_lshape_pose boxes one frame at a time, with no
+ * identity and no motion.  gv_track_update is the link: a multi-object tracker over the tick's boxes, nearest-neighbour
+ * association inside a gate and a constant-velocity Kalman filter per axis, with at most 128 tracks.  Its state lives
+ * on the device next to its consumer, it is enqueued on gv_stream(h) like every planner call, and it can hand its
+ * confirmed tracks to X13 without the set crossing the host.  The reference has no such step; this text is its
+ * definition, and the device kernel, the host twin gv_track_step and tests/track_ref.py follow it byte for byte.  With
+ * no configuration set (the state after gv_create) every existing call gives the bytes it gave before.
+ *
+ * State.  128 slots; a live slot holds a gv_track (128 bytes).  Beside the slots a uint32_t next_id, 1 after gv_create.
+ *   The frame is X13's: the base frame at the last map update, velocities over ground expressed in its axes.
+ *   WITHOUT motion THE VELOCITIES ARE RELATIVE TO THE VEHICLE: a parked car seen from a vehicle that drives at 5 m/s
+ *   gets -5 m/s.  Pass every update the motion that gv_grid_move was given for the same interval.
+ * Configuration (gv_track_config).  Computed once on the host:
+ *     q = sigma_accel*sigma_accel;  r = sigma_meas*sigma_meas;  v0 = sigma_v0*sigma_v0;
+ *     gate2 = gate*gate;            min2 = min_speed*min_speed
+ * One update.  The inputs are dets[n], dt and an optional motion.  All arithmetic is fp64; every operation is one
+ *   operation in exactly the order given here, never contracted.
+ *   Step 1, ego motion, only when motion != NULL.  motion is gv_grid_move's argument, base_prev <- base_now, and as in
+ *   X13 THE QUATERNION IS USED AS GIVEN:
+ *     ce = 1.0 - 2.0*(qy*qy + qz*qz);    se = 2.0*(qw*qz + qx*qy)
+ *   and for every live track
+ *     dx = x - tx;  dy = y - ty
+ *     x = ce*dx + se*dy;       y = ce*dy - se*dx
+ *     vx' = ce*vx + se*vy;     vy' = ce*vy - se*vx
+ *     q <- conj(q_motion) (x) q, a Hamilton product: with a = (-mx, -my, -mz, mw) and b = q, each line left to right,
+ *       w = aw*bw - ax*bx - ay*by - az*bz
+ *       x = aw*bx + ax*bw + ay*bz - az*by
+ *       y = aw*by - ax*bz + ay*bw + az*bx
+ *       z = aw*bz + ax*by - ay*bx + az*bw
+ *   Step 2, predict, for every live track, with dt2 = dt*dt and the old p's on the right-hand sides:
+ *     x = x + vx*dt;  y = y + vy*dt
+ *     p00' = ((p00 + (2.0*dt)*p01) + dt2*p11) + q*(0.25*(dt2*dt2))
+ *     p01' = (p01 + dt*p11) + q*(0.5*(dt2*dt))
+ *     p11' = p11 + q*dt2
+ *     age increases by 1 and saturates at 2^31 - 1;  det = -1.
+ *   Step 3, validity.  Detection d is valid iff px, py, qx, qy, qz, qw, length, width are all finite and length,
+ *     width >= 0.  Invalid detections take no part in the update and are counted in n_invalid.  pz and height are not
+ *     read.
+ *   Step 4, association.  For live slot s and valid detection d:
+ *     ex = px - x;  ey = py - y;  d2 = ex*ex + ey*ey
+ *     the pair is a candidate iff d2 <= gate2 (a NaN fails).  The matching is the greedy one over the total order
+ *     (d2, s, d): take the smallest remaining candidate, match it, drop every other candidate of that slot and of that
+ *     detection, repeat until no candidate remains.  No order of evaluation shows in the result.
+ *   Step 5, matched pair, old values on the right-hand sides:
+ *     S = p00 + r;  k0 = p00/S;  k1 = p01/S
+ *     x = x + k0*ex;  vx = vx + k1*ex
+ *     y = y + k0*ey;  vy = vy + k1*ey
+ *     p11' = p11 - k1*p01;  p01' = p01 - k1*p00;  p00' = p00 - k0*p00
+ *     q, length and width are taken from the detection; hits increases by 1 and saturates; misses = 0; det = d.
+ *   Step 6, unmatched live track.  misses increases by 1 (and saturates); the slot is freed when misses > max_misses and
+ *     counted in n_deleted.
+ *   Step 7, births.  Unmatched valid detections in ascending d, each into the lowest free slot; slots freed in step 6
+ *     count as free.  id = next_id++ (wraps mod 2^32); slot = the slot; hits = 1, misses = 0, age = 0, det = d; x, y from
+ *     the detection; vx = vy = 0.0; q, length, width from the detection; p00 = r, p01 = 0.0, p11 = v0.  With no free
+ *     slot the detection is dropped and counted in n_dropped.
+ *   Step 8, export.  Live slots in ascending order; a track is exported iff hits >= confirm_hits and x, y, vx, vy are
+ *     all finite.  sp2 = vx*vx + vy*vy; the exported velocity is (0.0, 0.0) when sp2 < min2, otherwise (vx, vy).  The
+ *     export is a gv_moving_object {pose = {x, y, 0, q, length, width, 0}, vx, vy}, and its X13 table row is what
+ *     gv_set_moving_objects builds of it, the same text.
+ * Update record (gv_track_info, 40 bytes).  n_tracks: live slots after the update; n_confirmed: those with hits >=
+ *   confirm_hits; n_exported, n_matched, n_born, n_deleted, n_dropped, n_invalid as above; next_id after the update;
+ *   reserved = 0.
+ *
+ * gv_set_track_config is handle configuration like gv_set_dyn_config: no device work, kept through gv_reset,
+ *   gv_set_log_odds and gv_grid_move (which keep the tracks too: they read no map).  NULL turns it off and empties the
+ *   tracks: the state after gv_create, next_id = 1.  GV_ERR_BAD_ARG, configuration unchanged, for a null handle or
+ *   any field outside the ranges written beside it.
+ * gv_set_tracks replaces the state, stream-ordered on gv_stream(h): n in 0..128 (n == 0 empties the state; tracks may
+ *   then be NULL), the slot fields distinct, ascending and in 0..127; every other value is taken as given, non-finite
+ *   included.  GV_ERR_BAD_ARG and the state unchanged otherwise.  The caller's array is free on return.
+ * gv_get_tracks is a synchronous read-back (it waits for gv_stream(h)) of the live records in ascending slot order:
+ *   *n receives their number and *next_id the counter (either may be NULL); GV_ERR_BAD_ARG when cap is below the
+ *   number, after writing *n, and then nothing is written to out.
+ * gv_track_update_async enqueues one update on gv_stream(h) without a host wait (the allocations of a first call
+ *   aside), behind everything enqueued before it; allowed between gv_tick_enqueue and gv_tick_wait.  dets is host
+ *   memory, copied through a pinned staging slot (the caller's array is free on return), or with GV_TRACK_DEVICE_DETS
+ *   device memory read in place; NULL is allowed when n == 0.  info (one record) and tracks (room for 128 records) may each be
+ *   NULL and follow the destination rules of gv_score_trajectories_async: pinned memory aligned to 8 bytes is written
+ *   by the kernel, other host memory by a copy behind it.  tracks receives the live records in ascending slot order
+ *   and zero bytes in the records after them, all 128 written.
+ *   With GV_TRACK_FEED_DYNAMIC the exported rows become X13's object set: they are written on the device, in slot
+ *   order, into the next object slot, with their count beside them.  This is stream-ordered exactly like
+ *   gv_set_moving_objects: calls enqueued before it keep the old set, calls after it see the new one, and a later
+ *   gv_set_moving_objects replaces it again.  The host does not learn the count: a fed set is "up to 128" to it.
+ *   GV_ERR_BAD_ARG for a null handle, n outside 0..128, null dets with n > 0, dt not finite or < 0, a non-finite field
+ *   of motion, or unknown flags; GV_ERR_STATE without a configuration.  gv_track_update is the same call followed by
+ *   the wait.
+ * gv_track_step is host only and takes no handle: the same arithmetic text compiled for the host.  tracks (room for
+ *   128), *n_tracks and *next_id are in/out, under gv_set_tracks' rules on the way in and gv_get_tracks' order on the
+ *   way out; info may be NULL; objs (room for 128) and n_objs may be NULL together.  Its objs, given to
+ *   gv_set_moving_objects, produce the rows the device feed writes.  GV_ERR_BAD_ARG for a null or invalid cfg and for
+ *   what the two calls above reject. */
+typedef struct {
+  uint32_t id;             /* unique while 2^32 births have not passed */
+  int32_t slot;            /* 0..127, where the track lives */
+  int32_t hits, misses;    /* matched updates in all; updates without a match since the last one */
+  int32_t age;             /* updates since birth */
+  int32_t det;             /* the detection matched in the last update, -1 when none */
+  double x, y, vx, vy;     /* m, m/s: centre and velocity in the frame above */
+  double qx, qy, qz, qw;   /* of the last matched detection, moved with the vehicle since */
+  double length, width;    /* of the last matched detection */
+  double p00, p01, p11;    /* position / position-velocity / velocity covariance, the same for both axes */
+} gv_track;                /* 128 bytes */
+typedef struct {
+  double gate;          /* m, finite, > 0: a detection farther than this from a track is no candidate */
+  double sigma_accel;   /* m/s^2, finite, >= 0: process noise */
+  double sigma_meas;    /* m, finite, > 0: measurement noise of a box centre */
+  double sigma_v0;      /* m/s, finite, >= 0: velocity uncertainty at birth */
+  double min_speed;     /* m/s, finite, >= 0: a slower track is exported with velocity (0, 0) */
+  int32_t confirm_hits; /* 1..255: a track is exported from this many hits on */
+  int32_t max_misses;   /* 0..255: a track is deleted after more consecutive misses than this */
+  uint32_t flags;       /* 0 */
+} gv_track_config;
+typedef struct {
+  int32_t n_tracks, n_confirmed, n_exported, n_matched, n_born, n_deleted, n_dropped, n_invalid;
+  uint32_t next_id, reserved;
+} gv_track_info;        /* 40 bytes */
+enum {
+  GV_TRACK_DEVICE_DETS  = 1 << 0,   /* dets is device memory, read in place                  */
+  GV_TRACK_FEED_DYNAMIC = 1 << 1    /* the exported tracks become X13's moving-object set    */
+};
+int gv_set_track_config(gv_handle h, const gv_track_config *cfg);   /* NULL = off, the state after gv_create */
+int gv_set_tracks(gv_handle h, const gv_track *tracks, int32_t n, uint32_t next_id);
+int gv_get_tracks(gv_handle h, gv_track *out, int32_t cap, int32_t *n, uint32_t *next_id);
+int gv_track_update_async(gv_handle h, const gv_lshape_pose *dets, int32_t n, double dt,
+                          const gv_transform *motion /* may be NULL */, uint32_t flags, gv_track_info *info /* may be NULL */,
+                          gv_track *tracks /* may be NULL, room for 128 */);
+int gv_track_update(gv_handle h, const gv_lshape_pose *dets, int32_t n, double dt,
+                    const gv_transform *motion /* may be NULL */, uint32_t flags, gv_track_info *info /* may be NULL */,
+                    gv_track *tracks /* may be NULL, room for 128 */);
+int gv_track_step(const gv_track_config *cfg, gv_track *tracks, int32_t *n_tracks, uint32_t *next_id,
+                  const gv_lshape_pose *dets, int32_t n, double dt, const gv_transform *motion /* may be NULL */,
+                  gv_track_info *info /* may be NULL */, gv_moving_object *objs /* may be NULL, room for 128 */,
+                  int32_t *n_objs);
+
 /* ------------------------------------------------------ [EXTENSION] frame -- */
 /* One fused per-frame pass over the resident cloud (SURVEY rows X1, X2, A5, A8,
  * A7, A18):  bin points into hit counts, ray-march free space from the sensor
@@ -1023,7 +1159,8 @@ typedef struct {
  * ...).  Cloud uploads (synchronous or not), gv_frame_*, the grid getters, gv_publish_grid_async, gv_update_map*,
  * gv_grid_move, gv_set_transforms, gv_set_height_band, gv_set_inflation, gv_inflate, the costmap getters,
  * gv_set_footprint, gv_score_trajectories*, gv_set_motion_model, gv_rollout*, the rollout getters and
- * gv_control_step*, gv_set_dyn_config, gv_set_moving_objects and gv_score_dynamic* may be called; their device work is ordered behind the tick on gv_stream(h), and an upload never
+ * gv_control_step*, gv_set_dyn_config, gv_set_moving_objects and gv_score_dynamic* may be called, and so may
+ * gv_set_track_config, gv_set_tracks, gv_get_tracks and gv_track_update*; their device work is ordered behind the tick on gv_stream(h), and an upload never
  * overwrites the cloud the tick reads.  What gv_tick_wait returns reflects the handle's state at gv_tick_enqueue: the
  * cloud (its size decides pca_empty) and the camera->base transform of the poses and base points; a transform or height
  * band set in between applies from the next tick on.  (tests/test_gpu_tick.py) */
