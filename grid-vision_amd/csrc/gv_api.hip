@@ -1,7 +1,8 @@
 // gv_api.hip -- C ABI (include/gridvision_hip.h) over the gfx950 kernels: the handle's life, transforms, getters,
 // plain map updates, grid publishing, ego motion, and the host-only helpers.  The frame pipeline is gv_api_frame.hip,
-// the sharded frame gv_api_shard.hip, the kNN / RANSAC / PCA path and the tick gv_api_pose.hip, everything that reads or
-// makes the costmap (inflation, trajectory scoring, the distance field) gv_api_planner.hip.
+// the sharded frame gv_api_shard.hip, the kNN / RANSAC / PCA path and the tick gv_api_pose.hip, everything that makes or
+// samples the costmap (inflation, the distance field, trajectory scoring) gv_api_planner.hip, the controller over them
+// (rollout, control step, MPPI, moving objects, tracker) gv_api_control.hip, their host-only twins gv_api_planner_host.hip.
 // One gv_context = one device + one resident grid + its HIP streams.  No exception
 // leaves these files; every entry point returns a gv_status.
 #include <chrono>

@@ -319,22 +319,33 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // [EXTENSION] X4 height band of the lidar map update (gv_set_height_band): handle configuration, copied into the
   // kernel arguments of every binning launch at enqueue
   HeightBand band{-INFINITY, INFINITY, 0};
+  // Host data on its way to the device through two pinned staging slots: slot k is filled by memcpy, leaves by one copy
+  // command on the public stream and is marked by an event, k alternating; it is rewritten only once its last copy has
+  // left it -- two uploads ago, the one host wait that can occur here (stage_upload, gv_api_planner.hip).
+  struct StageSlots {
+    PinnedBuf stage[2];
+    Event staged[2];
+    bool staged_used[2] = {false, false};
+    int slot = 0;                           // of the current contents
+  };
+  // ... into device slot k: a kernel already enqueued keeps reading the slot it was given, and the copy into a slot runs
+  // behind every kernel that was given it (one in-order stream).  upload_slot fills the slot that is not current and
+  // makes it current; so does a gv_track_update with GV_TRACK_FEED_DYNAMIC for X13's object table, whose kernel writes
+  // that slot itself (no staging) before the call flips st.slot.
+  struct UploadSlots {
+    DevBuf<uint8_t> dev[2];
+    StageSlots st;
+    uint8_t *current() const { return dev[st.slot].get(); }
+  };
   // [EXTENSION] X6 inflated costmap (gv_set_inflation / gv_inflate).  The configuration and its host-built table are
   // handle state; the buffers are made by the first gv_inflate (dist2 by the first one that keeps it).  A changed
-  // table reaches the device with the next gv_inflate: pinned staging slot k -> device slot k by a copy command on
-  // the public stream, k alternating, so a pass already enqueued keeps reading the slot it was given (the copy into a
-  // slot runs behind every earlier pass on that stream; the staging slot is rewritten only once its last copy has left
-  // it -- two reconfigurations ago, the one host wait that can occur here).
+  // table reaches the device with the next gv_inflate, through `table`.
   struct Inflation {
     bool set = false;
     int32_t thr = 0, flags = 0;
     host::InflationTable tab;
     bool dirty = false;               // `tab` is newer than the device slot
-    int slot = 0;                     // device slot of the current table
-    DevBuf<uint8_t> d_table[2];
-    PinnedBuf stage[2];
-    Event staged[2];
-    bool staged_used[2] = {false, false};
+    UploadSlots table;
     DevBuf<unsigned long long> bits;  // lethal bitmap (guard words zero since allocation)
     DevBuf<uint8_t> cost;
     DevBuf<uint16_t> dist2;
@@ -412,17 +423,10 @@ struct __attribute__((visibility("hidden"))) gv_context {
   } mppi;
   // [EXTENSION] X13 scoring against predicted moving objects (gv_set_dyn_config / gv_set_moving_objects /
   // gv_score_dynamic*).  The configuration and its host-built cost table are handle state; a changed table reaches the
-  // device with the next call that scores, through Inflation's mechanism (UploadSlots).  The object table is built on the
+  // device with the next call that scores, through `table` like Inflation's.  The object table is built on the
   // host by gv_set_moving_objects and copied on the public stream through slots of its own; n_obj travels in the kernel
   // arguments.  Neither depends on the map: gv_reset keeps both.  d_scores / d_pose_cost follow TrajScore's rules, and
   // d_scores is also where the control step's dyn sampler writes.
-  struct UploadSlots {
-    DevBuf<uint8_t> dev[2];                 // slot k is rewritten behind every kernel that was given it: one in-order stream
-    PinnedBuf stage[2];                     // ... and staging slot k only once its last copy has left it (the one host wait)
-    Event staged[2];
-    bool staged_used[2] = {false, false};
-    int slot = 0;                           // of the current contents
-  };
   struct DynScore {
     bool set = false;
     gv_dyn_config cfg{};
@@ -441,7 +445,7 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // gv_track_update*).  The configuration is handle state and travels in the kernel arguments.  The 128 slots and
   // next_id are resident in `state`, which the one update kernel rewrites in place on the public stream; `fresh` says
   // that the state is the one after gv_create (no tracks, next_id 1) whatever the block holds, so that turning the
-  // tracker off needs no device work.  gv_set_tracks goes through `up`'s staging slots (its device slots stay empty).
+  // tracker off needs no device work.  gv_set_tracks goes through `up`'s staging slots into `state`.
   // Host detections go through `dets`' alternating slots like X13's object table (the caller's array is free on return).  d_info and
   // d_tracks are the landing buffers of destinations that are not pinned.  gv_reset keeps all of it.
   struct Track {
@@ -449,7 +453,7 @@ struct __attribute__((visibility("hidden"))) gv_context {
     gv_track_config cfg{};
     bool fresh = true;
     DevBuf<TrackState> state;
-    UploadSlots up;
+    StageSlots up;
     UploadSlots dets;
     DevBuf<gv_track_info> d_info;
     DevBuf<gv_track> d_tracks;
@@ -613,5 +617,33 @@ void comm_destroy(gv_context *h);
 host::ShardPlan shard_plan(const gv_context *h, int world);
 // gv_api_planner.hip
 enum : unsigned { kNeedCostmap = 1u, kNeedField = 2u, kNeedRollout = 4u };
+int state_error(gv_context *h, const char *call, const char *why);
 int refuse_state(gv_context *h, const char *call, const char *missing, unsigned needs, const char *sharded);
+int stage_upload(gv_context *h, gv_context::StageSlots &s, const void *src, size_t bytes, size_t cap, void *dst);
+int upload_slot(gv_context *h, gv_context::UploadSlots &u, const void *src, size_t bytes, size_t cap);
+int wait_scored(gv_context *h, int rc, int32_t K);
+int enqueue_control_scores(gv_context *h, const gv_critic_weights &w, gv_control_result *result, uint64_t *totals);
+
+// Where a kernel writes n results bound for `dst`: dst's own device view when it is pinned host memory aligned to
+// `align` bytes, else `landing`, which copy_back empties into dst on the public stream behind the kernel.
+template <typename T>
+struct ResultDest {
+  T *dev = nullptr;    // what the kernel is given
+  T *host = nullptr;   // non-null: the results land in device memory and are copied here
+  size_t n = 0;
+  int open(gv_context *h, T *dst, size_t count, size_t align, DevBuf<T> &landing)
+  {
+    n = count;
+    if ((dev = static_cast<T *>(pinned_device_view(dst, align)))) return GV_OK;
+    if (int rc = landing.reserve(h, n)) return rc;
+    dev = landing;
+    host = dst;
+    return GV_OK;
+  }
+  int copy_back(gv_context *h) const
+  {
+    if (host) GV_HIP(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    return GV_OK;
+  }
+};
 }  // namespace gv_internal

@@ -388,6 +388,7 @@ inline GridMoveStep plan_grid_move(const Se2 &residue, const Se2 &motion, const 
 // configuration in fp64.  cost[q], q = 0 .. d2max, from dist = sqrt((double)q) * res; d2max is the largest q whose dist
 // is within the inflation radius, rc = isqrt(d2max) is how far the kernels search along a row and across rows.
 constexpr int32_t kInflateMaxRc = 63;
+constexpr size_t kTableBytes = (size_t)(kInflateMaxRc + 1) * (kInflateMaxRc + 1);   // room of a table's device and staging slot
 constexpr int32_t kInflateFlags = GV_INFLATE_KEEP_DIST2 | GV_INFLATE_OCCUPANCY_SCALE;
 
 struct InflationTable {

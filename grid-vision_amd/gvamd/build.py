@@ -13,8 +13,8 @@ PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libgridvision_hip.so")
-SOURCES = ["gv_api.hip", "gv_api_frame.hip", "gv_api_shard.hip", "gv_api_pose.hip", "gv_api_planner.hip", "gv_kernels.hip",
-           "gv_binning.hip", "gv_raysector.hip", "gv_shard.hip", "gv_knn_pca.hip", "gv_cloudops.hip", "gv_gridmove.hip",
+SOURCES = ["gv_api.hip", "gv_api_frame.hip", "gv_api_shard.hip", "gv_api_pose.hip", "gv_api_planner.hip", "gv_api_control.hip",
+           "gv_api_planner_host.hip", "gv_kernels.hip", "gv_binning.hip", "gv_raysector.hip", "gv_shard.hip", "gv_knn_pca.hip", "gv_cloudops.hip", "gv_gridmove.hip",
            "gv_inflate.hip", "gv_trajscore.hip", "gv_navfield.hip", "gv_rollout.hip", "gv_mppi.hip", "gv_dynscore.hip",
            "gv_track.hip"]
 # -ffp-contract=off: cell indices must be bit-exact with the reference's separate

@@ -178,6 +178,34 @@ def test_five_updates_without_a_wait_and_two_handles(gvamd, name):
                 pt.close()
 
 
+def test_three_set_tracks_without_a_wait(gvamd):
+    """The staging slots at their reuse edge: the third gv_set_tracks on a fresh handle fills the slot the first one used,
+    which is the one host wait of the mechanism; the state is the last one's.  An update between the second and the third
+    reads the second's.  (The same edge of the inflation table is test_gpu_inflate.py::test_reconfiguration_in_flight's,
+    that of X13's object set and cost table test_gpu_dyn.py::test_set_and_configuration_are_stream_ordered's, that of the
+    host detections test_five_updates_without_a_wait_and_two_handles'.)"""
+    h = gvamd.GridVisionHIP(8, 8, 0.1)
+    states = [(tc.tracks_at([(0.0, 0.0), (2.0, 1.0), (4.0, -1.0)], slots=[0, 5, 127]), 7),
+              (tc.tracks_at([(1.0, 1.0)], slots=[3], v=[(0.5, -0.5)]), 0xFFFFFFFF),
+              (tc.tracks_at([(-1.0, 0.5), (3.0, 3.0)], slots=[1, 2], first_id=40), 42)]
+    cfg = ref.to_struct(gvamd, ref.config())
+    twin_tracks, _, twin_info, _ = gvamd.track_step(cfg, states[1][0], states[1][1], tc.boxes_at([(1.0, 1.0)]), 0.0)
+    pi, pt = gvamd.PinnedI8(40), gvamd.PinnedI8(128 * 128)
+    try:
+        h.set_track_config(cfg)
+        for k, (tracks, next_id) in enumerate(states):
+            h.set_tracks(tracks, next_id)
+            if k == 1:
+                h.track_update_async(tc.boxes_at([(1.0, 1.0)]), 0.0, info=pi.array.view(ref.INFO_DTYPE), tracks=pt.array.view(ref.TRACK_DTYPE))
+        got, nid = h.get_tracks()
+        assert got.tobytes() == np.ascontiguousarray(states[2][0]).tobytes() and nid == 42
+        assert pi.array.tobytes() == np.array([twin_info]).tobytes() and pt.array.tobytes() == _padded(twin_tracks)
+    finally:
+        pi.close()
+        pt.close()
+        h.close()
+
+
 def test_update_during_a_pending_tick(gvamd):
     """an update (and the other tracker calls) between gv_tick_enqueue and gv_tick_wait: the tick's result is that of the
     tick alone, the update's that of the twin"""

@@ -3,7 +3,11 @@ build (GV_LIB_AB) under HIP API tracing and compare the ordered lists of API nam
   GV_QUEUE_PROBE=0 GV_LIB_AB=tools/_ab/parent.so rocprofv3 --hip-trace --output-format csv -d out -o parent -- python3 tools/api_order.py
 GV_QUEUE_PROBE=0: the probe's round count depends on timing.  Every step is followed by a synchronize.
 python3 tools/api_order.py planner  runs the planner calls instead: inflate, score_trajectories, nav_field, score_nav with
-host and device poses and pinned and pageable destinations.
+host and device poses and pinned and pageable destinations; then the controller calls over them (run_controller): rollouts
+from host and device controls, control steps into pinned and pageable memory with and without totals, the MPPI calls
+without and with limits and a control cost, the dyn configuration and object set twice with score_dynamic from both pose
+sources into both kinds of destination, three set_tracks, track updates from the host and fed with a control step behind
+them, and a second set_inflation and inflate.
 python3 tools/api_order.py pose  runs the pose family on a fresh handle: kNN depth, poses of 1 and of 300 boxes (the second
 regrows the result block), the ground plane with and without its mask, the ground-removed pose with and without boxes,
 the vision post-process, a vision tick, a PCA tick with static and dynamic boxes, kNN depth again.
@@ -87,7 +91,92 @@ def run_planner():
         hip.hipFree(dptr)
         for p in (pin_s, pin_p, pin_n):
             p.close()
+    run_controller(h, gvamd, np, common, hip)
     h.close()
+
+
+def run_controller(h, gvamd, np, common, hip):
+    """the controller calls over the layers run_planner made: every step followed by a synchronize"""
+    synth = gvamd.synth
+    steps = []
+    step = steps.append
+    K, P, dt = 40, 130, 0.1
+    start = (h.pos_x - 4.0, h.pos_y + 1.0, 0.2)
+    rng = np.random.default_rng(3)
+    u = np.stack([rng.normal(1.0, 0.2, K * P), rng.normal(0.0, 0.2, K * P)], axis=1).astype(np.float32).reshape(K, P, 2)
+    u_dev = common.device_copy(hip, u)
+    nav_w, no_nav_w = gvamd.CriticWeights(1, 2, 4, 0, 1, 0), gvamd.CriticWeights(1, 2, 0, 0, 0, 0)
+    pin_r, pin_t, pin_n, pin_d, pin_c = (gvamd.PinnedI8(16), gvamd.PinnedI8(K * 8), gvamd.PinnedF32(P * 2), gvamd.PinnedI8(K * 24),
+                                        gvamd.PinnedI8(K * P))
+    res_pin, tot_pin = pin_r.array.view(gvamd.CONTROL_RESULT_DTYPE), pin_t.array.view(np.uint64)
+    res_pg, tot_pg, nom_pg = np.zeros(1, gvamd.CONTROL_RESULT_DTYPE), np.zeros(K, np.uint64), np.zeros(P * 2, np.float32)
+
+    def control_steps(w=nav_w):
+        for res, tot in ((res_pin, tot_pin), (res_pin, None), (res_pg, tot_pg), (res_pg, None)):
+            step(lambda res=res, tot=tot: h.control_step_async(w, res, tot))
+
+    step(lambda: h.set_motion_model(gvamd.MotionModel(gvamd.MOTION_DIFF, dt, 0)))
+    step(lambda: h.rollout_async(start, u))
+    step(lambda: h.rollout_async(start, u[:7, 0], constant=True, P=65))
+    step(lambda: h.rollout_async(start, u.shape, device_ptr=u_dev.value))
+    control_steps()
+    control_steps(no_nav_w)
+    # MPPI without limits, then with limits and gamma > 0
+    step(lambda: h.set_mppi(gvamd.MppiConfig.of((0.3, 0.4), (-0.5, -1.5), (3.0, 1.5), 30.0)))
+    for limits in (None, gvamd.MppiLimits.of(rate_up=(2.0, 3.0), rate_down=(3.0, 3.0), u_prev=(1.0, 0.0), min_turn_radius=1.5, gamma=0.05)):
+        step(lambda limits=limits: h.set_mppi_limits(limits))
+        step(lambda: h.mppi_set_nominal(u[0]))
+        step(lambda: h.mppi_sample(K, 11, 0, wait=False))
+        step(lambda: h.rollout_async(start, (K, P, 2), device_ptr=h.device_controls()[0]))
+        step(lambda: h.mppi_update_async(nav_w, res_pin, tot_pin, pin_n.array))
+        step(lambda: h.mppi_update_async(nav_w, res_pg, tot_pg, nom_pg))
+        step(lambda: h.mppi_update_async(no_nav_w, res_pg))
+        step(lambda: h.mppi_cycle_async(start, K, 11, 1, nav_w, res_pin, tot_pin, pin_n.array, shift=True))
+        step(lambda: h.mppi_cycle_async(start, 7, 11, 2, nav_w, res_pg))
+    # X13: each setter twice, the sampler with both pose sources and both destinations, then as a third critic
+    cfgs = [gvamd.DynConfig.of(off_x=(-1.0, 0.5, 2.0), radius=1.1, influence_radius=r, cost_scaling_factor=2.0, quantum=0.05, t0=dt, dt=dt,
+                               collision_cost=253, w_sum=1, w_max=2) for r in (3.0, 2.5)]
+    sets = [gvamd.moving_objects(np.array([[h.pos_x + 2.0 * j, h.pos_y + 1.0, 0.3, 4.0, 2.0, 1.0, -0.5] for j in range(n)])) for n in (3, 2)]
+    poses = common.arcs(h, K, P, seed=5, start=(-4.0, 1.0))
+    poses_dev = common.device_copy(hip, poses)
+    ds_pin, pc_pin = pin_d.array.view(gvamd.DYN_SCORE_DTYPE), pin_c.array.view(np.uint8)
+    ds_pg, pc_pg = np.zeros(K, gvamd.DYN_SCORE_DTYPE), np.zeros(K * P, np.uint8)
+    for cfg, objs in zip(cfgs, sets):
+        step(lambda cfg=cfg: h.set_dyn_config(cfg))
+        step(lambda objs=objs: h.set_moving_objects(objs))
+        for src, dev in ((poses, None), (None, poses_dev.value)):
+            step(lambda src=src, dev=dev: h.score_dynamic_async(src, K, P, ds_pin, pc_pin, device_ptr=dev))
+            step(lambda src=src, dev=dev: h.score_dynamic_async(src, K, P, ds_pg, pc_pg, device_ptr=dev))
+            step(lambda src=src, dev=dev: h.score_dynamic_async(src, K, P, ds_pg, None, device_ptr=dev))
+        control_steps()
+    # X14: three set_tracks (the third reuses a staging slot), updates from the host and fed, a control step behind them
+    xy = np.array([[h.pos_x + 3.0 * j, h.pos_y - 1.0] for j in range(3)])
+    dets = np.zeros(3, synth.LSHAPE_DTYPE)
+    dets["px"], dets["py"], dets["qw"], dets["length"], dets["width"], dets["height"] = xy[:, 0] + 0.1, xy[:, 1], 1.0, 4.5, 2.0, 1.5
+    tracks = np.zeros(3, gvamd.TRACK_DTYPE)
+    tracks["slot"], tracks["id"], tracks["hits"], tracks["det"] = np.arange(3), 1 + np.arange(3), 5, -1
+    tracks["x"], tracks["y"], tracks["qw"], tracks["length"], tracks["width"] = xy[:, 0], xy[:, 1], 1.0, 4.5, 2.0
+    tracks["p00"], tracks["p01"], tracks["p11"] = 0.05, 0.02, 0.5
+    dets_dev = common.device_copy(hip, dets)
+    info_pg, out_pg = np.zeros(1, gvamd.TRACK_INFO_DTYPE), np.zeros(gvamd.TRACK_SLOTS, gvamd.TRACK_DTYPE)
+    step(lambda: h.set_track_config(gvamd.TrackConfig.of(gate=2.0)))
+    for n in (3, 2, 1):
+        step(lambda n=n: h.set_tracks(tracks[:n], 10))
+    step(lambda: h.track_update_async(dets, 0.05, info=info_pg, tracks=out_pg))
+    step(lambda: h.track_update_async(dets, 0.05, feed=True))
+    step(lambda: h.track_update_async(None, 0.05, feed=True, device_ptr=dets_dev.value, n=3))
+    control_steps()
+    step(lambda: h.score_dynamic_async(poses, K, P, ds_pg, None))
+    step(h.get_tracks)
+    step(lambda: h.set_inflation(0.3, 0.6, 8.0, 65))
+    step(h.inflate)
+    for s in steps:
+        s()
+        h.synchronize()
+    for d in (u_dev, poses_dev, dets_dev):
+        hip.hipFree(d)
+    for p in (pin_r, pin_t, pin_n, pin_d, pin_c):
+        p.close()
 
 
 def run_pose():
