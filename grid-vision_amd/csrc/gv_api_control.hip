@@ -476,11 +476,14 @@ int gv_track_update_async(gv_handle h, const gv_lshape_pose *dets, int32_t n, do
 {
   if (!h) return GV_ERR_BAD_ARG;
   GV_TRY
-  if (!track_update_ok(dets, n, dt, motion) || (flags & ~(uint32_t)(GV_TRACK_DEVICE_DETS | GV_TRACK_FEED_DYNAMIC)) != 0)
-    return GV_ERR_BAD_ARG;
+  if (!track_update_ok(dets, n, dt, motion) || !track_update_flags_ok(flags, dets, n)) return GV_ERR_BAD_ARG;
   gv_context::Track &t = h->trk;
   gv_context::DynScore &d = h->dyn;
   if (!t.set) return state_error(h, "gv_track_update", "no configuration set (gv_set_track_config)");
+  // [EXTENSION] X15: the list of the most recently enqueued tick, pending or waited for; its count stays on the device
+  const bool from_tick = (flags & GV_TRACK_TICK_DETS) != 0;
+  if (from_tick && !h->tick.dets_live)
+    return state_error(h, "gv_track_update", "GV_TRACK_TICK_DETS: the last tick enqueued did not carry GV_TICK_KEEP_DETS");
   const bool feed = (flags & GV_TRACK_FEED_DYNAMIC) != 0;
   const int k = d.objs.st.slot ^ 1;
   int rc = GV_OK;
@@ -495,6 +498,11 @@ int gv_track_update_async(gv_handle h, const gv_lshape_pose *dets, int32_t n, do
   if (n > 0 && !(flags & GV_TRACK_DEVICE_DETS)) {
     if ((rc = upload_slot(h, t.dets, dets, (size_t)n * sizeof(gv_lshape_pose), (size_t)kTrackSlots * sizeof(gv_lshape_pose)))) return rc;
     a.dets = reinterpret_cast<const gv_lshape_pose *>(t.dets.current());
+  }
+  if (from_tick) {
+    a.n = 0;
+    a.dets = h->tick.dets.get()->p;
+    a.n_dev = &h->tick.dets.get()->n;
   }
   a.state = t.state;
   ResultDest<gv_track_info> to_info;   // each stays closed (null, no copy) when the caller passes null

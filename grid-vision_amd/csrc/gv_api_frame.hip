@@ -292,7 +292,7 @@ int32_t enqueue_rects(gv_context *h, const DetSet &D, Rect *rects, VisionOut *vo
 {
   const bool vision = frame_flags(D.flags).vision;
   if (vision && D.nb > 0) {
-    launch_vision(D.orient, D.conf, D.dims, D.bboxes, D.nb, h->cam, vout, D.poses, nullptr, s);
+    launch_vision(D.orient, D.conf, D.dims, D.bboxes, D.nb, h->cam, vout, D.poses, nullptr, nullptr, s);
     launch_rects_from_poses(D.poses, D.nb, h->g, true, h->x_bc, rects, s);
     return D.nb;
   }

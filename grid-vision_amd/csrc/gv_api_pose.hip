@@ -61,7 +61,7 @@ int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, 
   DetSet &d = h->det[2];
   if ((rc = upload_det(h, d, vision_upload(bboxes, nb, orient, conf, dims, h->stream)))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
-  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, nullptr, h->stream);
+  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, nullptr, nullptr, h->stream);
   GV_HIP(hipGetLastError());
   std::vector<VisionOut> vo((size_t)nb);
   GV_HIP(hipMemcpyAsync(vo.data(), h->sb[0].vout, (size_t)nb * sizeof(VisionOut), hipMemcpyDeviceToHost, h->stream));
@@ -85,7 +85,7 @@ int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, con
   GV_HIP(hipEventRecord(d.ready, h->stream));
   DevBuf<float> dsets;   // nb * 64 * (loc0, loc1, loc2, err), then nb winners
   if ((rc = dsets.reserve(h, (size_t)nb * 257))) return rc;
-  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, dsets, h->stream);
+  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, dsets, nullptr, h->stream);
   GV_HIP(hipGetLastError());
   GV_HIP(hipMemcpyAsync(sets, dsets, (size_t)nb * 256 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   GV_HIP(hipMemcpyAsync(winner, dsets + (size_t)nb * 256, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -231,8 +231,7 @@ struct PoseBlock {
 // (cloud_detections.cpp:307-309)
 static bool segmented_cloud_empty(const RansacState &st, size_t n)
 {
-  const uint64_t m = st.best_count ? st.n_inliers : 0;
-  return m == 0 || (size_t)m == n;
+  return tick_dets_empty(st.best_count, st.n_inliers, (uint64_t)n);   // (gv_pose_math.hpp: k_tick_dets decides the same)
 }
 
 // The scratch of enqueue_bbox_pose, group by group; a group has room for what its smallest member has room for.
@@ -289,7 +288,8 @@ static RadiusFilterArgs radius_filter_args(const gv_context *h, int32_t nb, bool
 }
 
 // centroid + PCA rectangle per bbox from order-independent integer sums over the kept points (:156-247), into `out`
-static PcaRectArgs pca_rect_args(const gv_context *h, int32_t nb, bool with_ground, const PoseBlock &out, gv_lshape_pose *poses_dev)
+static PcaRectArgs pca_rect_args(const gv_context *h, int32_t nb, bool with_ground, const PoseBlock &out, gv_lshape_pose *poses_dev,
+                                 uint8_t *valid_dev)
 {
   const gv_context::Pose &P = h->pose;
   PcaRectArgs a{};
@@ -297,6 +297,7 @@ static PcaRectArgs pca_rect_args(const gv_context *h, int32_t nb, bool with_grou
   a.acc = P.pca_acc; a.ext = P.pca_ext; a.ticket = P.pca_ticket; a.nb = nb;
   a.st = P.rstate; a.use_plane = with_ground;
   a.poses = out.poses(); a.valid = out.valid(); a.st_copy = out.state(); a.poses_dev = poses_dev;
+  a.valid_dev = valid_dev;
   return a;
 }
 
@@ -307,7 +308,7 @@ static PcaRectArgs pca_rect_args(const gv_context *h, int32_t nb, bool with_grou
 // poses_dev (optional): the camera-frame poses also go to device memory (a NaN length marks "no pose": its
 // corners fail getIndex, so k_rects_from_poses gives it no cells), for a map update enqueued right behind this without a trip to the host.
 static int enqueue_bbox_pose(gv_context *h, int32_t nb, bool with_ground, float thr_f, const PoseBlock &out, const CallDone &done,
-                             gv_lshape_pose *poses_dev = nullptr)
+                             gv_lshape_pose *poses_dev = nullptr, uint8_t *valid_dev = nullptr)
 {
   gv_context::Pose &P = h->pose;
   int rc;
@@ -317,7 +318,7 @@ static int enqueue_bbox_pose(gv_context *h, int32_t nb, bool with_ground, float 
     return rc;
   launch_radius_filter(radius_filter_args(h, nb, with_ground, thr_f), h->stream);
   h->last.bbox_id = true;
-  launch_pca_rect(pca_rect_args(h, nb, with_ground, out, poses_dev), done, h->stream);
+  launch_pca_rect(pca_rect_args(h, nb, with_ground, out, poses_dev, valid_dev), done, h->stream);
   GV_HIP(hipGetLastError());
   return GV_OK;
 }
@@ -518,6 +519,8 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   GV_TRY
   gv_context::Tick &T = h->tick;
   if (T.pending) return GV_ERR_STATE;   // one tick at a time (the node's timer is single threaded, grid_vision_node.cpp:49-50)
+  const bool keep_dets = d->flags & GV_TICK_KEEP_DETS;   // [EXTENSION] X15
+  T.dets_live = false;
   const int32_t n_all = d->n_bboxes;
   // filterBBoxes (:384-403), order preserving
   std::vector<gv_bbox> cat((size_t)2 * n_all + 1);
@@ -586,22 +589,36 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   int32_t n_rects = 0;
   Rect *rects = h->fs[0].rects;
   T.pca_ran = T.vision_ran = false;
+  TickDetsArgs da{};   // what k_tick_dets reads of the branch that ran (kTickDetsNone: an empty list)
+  if (keep_dets) {
+    if ((rc = T.dets.reserve(h, 1)) || (net && (rc = T.dets_vout.reserve(h, (size_t)nd + (size_t)nd / 4))) ||
+        (pca && (rc = T.dets_valid.reserve(h, (size_t)n_all + (size_t)n_all / 4))))
+      return rc;
+    da.tf_bc = h->tf_bc;
+    da.out = T.dets;
+  }
   if (net) {   // VisionOrientation::postProcessOutputs (:190-209)
     launch_vision(D.orient, D.conf, D.dims, D.bboxes + n_all + ns, nd, h->cam, reinterpret_cast<VisionOut *>(blk + T.off_vout),
-                  D.poses, nullptr, s);
+                  D.poses, nullptr, keep_dets ? T.dets_vout.get() : nullptr, s);
     launch_rects_from_poses(D.poses, nd, h->g, true, h->x_bc, rects, s);
     n_rects = nd;
     T.vision_ran = true;
+    da.mode = kTickDetsVision; da.n_cand = nd; da.vout = T.dets_vout;
   } else if (pca) {   // cloud_detections::computeBBoxPose (:210-231)
     const float thr_f = host::ceil_to_float(0.04);
     if ((rc = ensure_ransac_buffers(h, n, kPoseRansacIters))) return rc;
     launch_ransac_plane(ransac_args(h, thr_f, kPoseRansacIters, kPoseRansacSeed), s);
     h->pose.ground_n = 0;
-    if ((rc = enqueue_bbox_pose(h, n_all, true, thr_f, PoseBlock(blk + T.off_pose, n_all), none, D.poses))) return rc;
+    if ((rc = enqueue_bbox_pose(h, n_all, true, thr_f, PoseBlock(blk + T.off_pose, n_all), none, D.poses,
+                                keep_dets ? T.dets_valid.get() : nullptr)))
+      return rc;
     launch_rects_from_poses(D.poses, n_all, h->g, true, h->x_bc, rects, s);
     n_rects = n_all;
     T.pca_ran = true;
+    da.mode = kTickDetsPca; da.n_cand = n_all; da.cam = D.poses; da.valid = T.dets_valid;
+    da.st = h->pose.rstate; da.n_cloud = (uint64_t)n;
   }
+  if (keep_dets) launch_tick_dets(da, s);   // behind the pose kernels, inside `done`
   GV_HIP(hipGetLastError());
   // --- map update (:145, :206, :230, :235) + int8 pack (:265-278)
   if (lidar && n > 0) {   // [EXTENSION] the fused frame's kernels, serial on the public stream
@@ -636,6 +653,7 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
   T.tf_bc = h->tf_bc;
   T.x_bc = h->x_bc;
   T.pending = true;
+  T.dets_live = keep_dets;
   return GV_OK;
   GV_CATCH
 }
@@ -683,6 +701,32 @@ int gv_tick_wait(gv_handle h, gv_tick_result *r)
     r->pca_empty = 1;   // fewer than three points: no plane, no poses
   return GV_OK;
   GV_CATCH
+}
+
+// test hooks (gv_test_hooks.h): the list of the last GV_TICK_KEEP_DETS tick, read back; and its host twin
+int gv_test_tick_dets(gv_handle h, gv_lshape_pose *out, int32_t *n, int32_t *n_total)
+{
+  if (!h || !out || !n || !n_total) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!h->tick.dets_live) return state_error(h, "gv_test_tick_dets", "the last tick enqueued did not carry GV_TICK_KEEP_DETS");
+  int rc = set_device_only(h);
+  if (rc) return rc;
+  std::vector<TickDetList> l(1);
+  GV_HIP(hipMemcpyAsync(l.data(), h->tick.dets.get(), sizeof(TickDetList), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipStreamSynchronize(h->stream));
+  std::memcpy(out, l[0].p, sizeof(l[0].p));
+  *n = l[0].n;
+  *n_total = l[0].n_total;
+  return GV_OK;
+  GV_CATCH
+}
+
+int gv_test_tick_dets_host(const gv_lshape_pose *cam, const uint8_t *valid, int32_t n_cand, int32_t empty, const gv_transform *tf_bc,
+                           gv_lshape_pose *out, int32_t *n, int32_t *n_total)
+{
+  if (n_cand < 0 || n_cand > kTickDetCandidates || (n_cand && (!cam || !valid)) || !tf_bc || !out || !n || !n_total) return GV_ERR_BAD_ARG;
+  tick_dets_host(cam, valid, n_cand, empty != 0, *tf_bc, out, *n, *n_total);
+  return GV_OK;
 }
 
 int gv_tick(gv_handle h, const gv_tick_desc *d, gv_tick_result *r)

@@ -1155,7 +1155,7 @@ __global__ void __launch_bounds__(256) k_pca_extent(const CellNode *__restrict__
                                                     const RansacState *__restrict__ st, int use_plane, uint32_t n_cloud,
                                                     gv_lshape_pose *__restrict__ poses, uint8_t *__restrict__ valid,
                                                     RansacState *__restrict__ st_copy, CallDone done,
-                                                    gv_lshape_pose *__restrict__ poses_dev)
+                                                    gv_lshape_pose *__restrict__ poses_dev, uint8_t *__restrict__ valid_dev)
 {
   __shared__ PcaAxes s_ax[kPcaTab];
   __shared__ unsigned s_ext[kPcaTab][4];
@@ -1273,6 +1273,8 @@ __global__ void __launch_bounds__(256) k_pca_extent(const CellNode *__restrict__
     double2 *dst = reinterpret_cast<double2 *>(poses + b0);
     for (int i = threadIdx.x; i < nbc * 5; i += 256) dst[i] = src[i];
     for (int i = threadIdx.x; i < nbc; i += 256) valid[b0 + i] = s_ok[i];
+    if (valid_dev)   // a GV_TICK_KEEP_DETS tick only: the flags once more, in device memory (k_tick_dets reads them)
+      for (int i = threadIdx.x; i < nbc; i += 256) valid_dev[b0 + i] = s_ok[i];
     if (poses_dev) {
       double2 *dd = reinterpret_cast<double2 *>(poses_dev + b0);
       for (int i = threadIdx.x; i < nbc * 5; i += 256) {
@@ -1327,7 +1329,7 @@ void launch_pca_rect(const PcaRectArgs &a, const CallDone &done, hipStream_t s)
   const uint32_t blk = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)a.n + 1023) / 1024, 256));
   hipLaunchKernelGGL(k_pca_cov, dim3(blk), dim3(256), 0, s, a.sorted, a.n_sel, a.keep, a.acc, a.nb);
   hipLaunchKernelGGL(k_pca_extent, dim3(blk), dim3(256), 0, s, a.sorted, a.n_sel, a.keep, a.acc, a.ext, a.ticket, a.nb, a.st,
-                     a.use_plane ? 1 : 0, a.n, a.poses, a.valid, a.st_copy, done, a.poses_dev);
+                     a.use_plane ? 1 : 0, a.n, a.poses, a.valid, a.st_copy, done, a.poses_dev, a.valid_dev);
 }
 
 size_t pca_acc_words(int nb) { return (size_t)nb * kAccStride; }

@@ -533,6 +533,14 @@ struct __attribute__((visibility("hidden"))) gv_context {
     Xform64 x_bc{};
     Event done;                      // public stream: everything the tick enqueued has finished
     Event fork, join;                // the kNN depth on a lane beside the pose branch
+    // [EXTENSION] X15 the detection list of a GV_TICK_KEEP_DETS tick (k_tick_dets, gv_track.hip): one block for the
+    // handle's life, written only by that kernel and read in place by gv_track_update*(GV_TRACK_TICK_DETS), all on the
+    // public stream.  dets_vout / dets_valid: what the pose kernels otherwise leave only in the pinned result block.
+    // dets_live: the most recently enqueued tick carried the flag (cleared when a gv_tick_enqueue starts).
+    DevBuf<TickDetList> dets;
+    DevBuf<VisionOut> dets_vout;
+    DevBuf<uint8_t> dets_valid;
+    bool dets_live = false;
   } tick;
 
   bool counts_dirty = false;   // generic path: hits/miss/clip_end hold a kept frame

@@ -9,84 +9,13 @@
 #include <vector>
 
 #include "gv_line.hpp"
+#include "gv_pose_math.hpp"
 #include "gv_types.hpp"
 
 namespace gv {
 namespace host {
 
-struct Quat {
-  double x, y, z, w;
-};
-
-// 3x3 fp64 rotation, row-major (tf2::Matrix3x3)
-struct Basis {
-  double m[9];
-
-  // tf2::Matrix3x3::setRotation(const Quaternion&)
-  static Basis from_quat(const Quat &q)
-  {
-    const double d = ((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w;
-    const double s = 2.0 / d;
-    const double xs = q.x * s, ys = q.y * s, zs = q.z * s;
-    const double wx = q.w * xs, wy = q.w * ys, wz = q.w * zs;
-    const double xx = q.x * xs, xy = q.x * ys, xz = q.x * zs;
-    const double yy = q.y * ys, yz = q.y * zs, zz = q.z * zs;
-    Basis b;
-    b.m[0] = 1.0 - (yy + zz); b.m[1] = xy - wz;         b.m[2] = xz + wy;
-    b.m[3] = xy + wz;         b.m[4] = 1.0 - (xx + zz); b.m[5] = yz - wx;
-    b.m[6] = xz - wy;         b.m[7] = yz + wx;         b.m[8] = 1.0 - (xx + yy);
-    return b;
-  }
-
-  // tf2::Matrix3x3::getRotation(Quaternion&)
-  Quat to_quat() const
-  {
-    const double trace = (m[0] + m[4]) + m[8];
-    double t[4];
-    if (trace > 0.0) {
-      double s = std::sqrt(trace + 1.0);
-      t[3] = s * 0.5;
-      s = 0.5 / s;
-      t[0] = (m[7] - m[5]) * s;
-      t[1] = (m[2] - m[6]) * s;
-      t[2] = (m[3] - m[1]) * s;
-    } else {
-      const int i = m[0] < m[4] ? (m[4] < m[8] ? 2 : 1) : (m[0] < m[8] ? 2 : 0);
-      const int j = (i + 1) % 3, k = (i + 2) % 3;
-      double s = std::sqrt(((m[i * 3 + i] - m[j * 3 + j]) - m[k * 3 + k]) + 1.0);
-      t[i] = s * 0.5;
-      s = 0.5 / s;
-      t[3] = (m[k * 3 + j] - m[j * 3 + k]) * s;
-      t[j] = (m[j * 3 + i] + m[i * 3 + j]) * s;
-      t[k] = (m[k * 3 + i] + m[i * 3 + k]) * s;
-    }
-    return Quat{t[0], t[1], t[2], t[3]};
-  }
-
-  Basis operator*(const Basis &o) const
-  {
-    Basis r;
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j)
-        r.m[i * 3 + j] = (m[i * 3 + 0] * o.m[0 * 3 + j] + m[i * 3 + 1] * o.m[1 * 3 + j]) + m[i * 3 + 2] * o.m[2 * 3 + j];
-    return r;
-  }
-};
-
-inline Xform64 xform_from_tf(const gv_transform &t)
-{
-  const Basis b = Basis::from_quat(Quat{t.qx, t.qy, t.qz, t.qw});
-  Xform64 x;
-  for (int i = 0; i < 9; ++i) x.b[i] = b.m[i];
-  x.o[0] = t.tx; x.o[1] = t.ty; x.o[2] = t.tz;
-  return x;
-}
-
-// tf2::Transform::operator()(Vector3): basis[r].dot(v) + origin[r]
-inline void apply(const Xform64 &x, const double v[3], double out[3])
-{
-  for (int r = 0; r < 3; ++r) out[r] = ((x.b[r * 3] * v[0] + x.b[r * 3 + 1] * v[1]) + x.b[r * 3 + 2] * v[2]) + x.o[r];
-}
+// Quat, Basis, xform_from_tf, apply, transform_pose: gv_pose_math.hpp (one text for the host and the device)
 
 // pcl_ros::transformPointCloud(in, out, tf2::Transform) matrix construction:
 // quaternion read back from the tf2 basis, narrowed to fp32,
@@ -113,21 +42,7 @@ inline Quat quat_from_rpy(double roll, double pitch, double yaw)
   const double cy = std::cos(hy), sy = std::sin(hy);
   const double cp = std::cos(hp), sp = std::sin(hp);
   const double cr = std::cos(hr), sr = std::sin(hr);
-  return Quat{sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy,
-              cr * cp * cy + sr * sp * sy};
-}
-
-// tf2::doTransform(Pose): Transform(t) * Transform(r, v)
-inline void transform_pose(const gv_transform &t, gv_lshape_pose &p)
-{
-  const Xform64 x = xform_from_tf(t);
-  const double v[3] = {p.px, p.py, p.pz};
-  double o[3];
-  apply(x, v, o);
-  const Basis prod = Basis::from_quat(Quat{t.qx, t.qy, t.qz, t.qw}) * Basis::from_quat(Quat{p.qx, p.qy, p.qz, p.qw});
-  const Quat q = prod.to_quat();
-  p.px = o[0]; p.py = o[1]; p.pz = o[2];
-  p.qx = q.x; p.qy = q.y; p.qz = q.z; p.qw = q.w;
+  return quat_from_half_angles(cr, sr, cp, sp, cy, sy);
 }
 
 // setIntrinsicMatrix / K.inverse() (Eigen 3x3 cofactor inverse)

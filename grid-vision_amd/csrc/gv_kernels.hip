@@ -492,7 +492,8 @@ __device__ void qr_solve_4x3(const float Ain[12], const float bin[4], float x[3]
 __global__ void __launch_bounds__(64) k_vision(const float *__restrict__ orient, const float *__restrict__ conf,
                                                const float *__restrict__ dims, const gv_bbox *__restrict__ bboxes,
                                                int32_t nb, gv_cam_params cam, VisionOut *__restrict__ out,
-                                               gv_lshape_pose *__restrict__ poses_cam, float *__restrict__ sets)
+                                               gv_lshape_pose *__restrict__ poses_cam, float *__restrict__ sets,
+                                               VisionOut *__restrict__ out_dev)
 {
   const int bi = blockIdx.x;
   if (bi >= nb) return;
@@ -608,6 +609,7 @@ __global__ void __launch_bounds__(64) k_vision(const float *__restrict__ orient,
     o.dims[0] = len; o.dims[1] = wid; o.dims[2] = hgt;
     o.valid = valid;
     out[bi] = o;
+    if (out_dev) out_dev[bi] = o;   // a GV_TICK_KEEP_DETS tick only: the record once more, in device memory (k_tick_dets reads it)
     gv_lshape_pose p;
     p.px = o.loc[0]; p.py = o.loc[1]; p.pz = o.loc[2];
     p.qx = 0; p.qy = 0; p.qz = 0; p.qw = 1;
@@ -619,10 +621,11 @@ __global__ void __launch_bounds__(64) k_vision(const float *__restrict__ orient,
 }
 
 void launch_vision(const float *orient, const float *conf, const float *dims, const gv_bbox *bboxes, int32_t nb,
-                   const gv_cam_params &cam, VisionOut *out, gv_lshape_pose *poses_cam, float *sets, hipStream_t s)
+                   const gv_cam_params &cam, VisionOut *out, gv_lshape_pose *poses_cam, float *sets, VisionOut *out_dev,
+                   hipStream_t s)
 {
   if (nb <= 0) return;
-  hipLaunchKernelGGL(k_vision, dim3(nb), dim3(64), 0, s, orient, conf, dims, bboxes, nb, cam, out, poses_cam, sets);
+  hipLaunchKernelGGL(k_vision, dim3(nb), dim3(64), 0, s, orient, conf, dims, bboxes, nb, cam, out, poses_cam, sets, out_dev);
 }
 
 // --------------------------------------------------------- ray march (X2) --

@@ -7,6 +7,7 @@
 #include "gv_types.hpp"
 #include "gv_dyn.hpp"
 #include "gv_track.hpp"
+#include "gv_pose_math.hpp"
 
 namespace gv {
 
@@ -71,10 +72,11 @@ void launch_rects_from_points(const double *pts_xyz, const gv_bbox *bboxes, int3
 
 // vision-orientation geometry, one wavefront per bbox; also emits camera-frame
 // gv_lshape_pose (position + dims only; the quaternion is filled by the host).  sets: nullptr in the product; the
-// test hook gv_test_vision_sets passes nb * 64 * 4 floats (loc0, loc1, loc2, err of every lane) + nb int32 (winner)
+// test hook gv_test_vision_sets passes nb * 64 * 4 floats (loc0, loc1, loc2, err of every lane) + nb int32 (winner).
+// out_dev: nullptr, or (a GV_TICK_KEEP_DETS tick, X15) device memory for a second copy of `out`, which is usually pinned
 void launch_vision(const float *orient, const float *conf, const float *dims, const gv_bbox *bboxes,
                    int32_t nb, const gv_cam_params &cam, VisionOut *out, gv_lshape_pose *poses_cam, float *sets,
-                   hipStream_t s);
+                   VisionOut *out_dev, hipStream_t s);
 
 void launch_ray_compact(const int32_t *hits, const uint8_t *clip_end, const GridParams &g,
                         uint32_t *list, uint32_t *count, hipStream_t s);
@@ -274,8 +276,25 @@ struct TrackArgs {
   gv_track *tracks;             // kTrackSlots records or null (likewise; 8-byte aligned)
   DynObject *feed_objs;         // kTrackSlots rows of X13's object table or null (device)
   int32_t *feed_n;              // their count, beside them; null with feed_objs
+  const int32_t *n_dev;         // [EXTENSION] X15: null, or the count of a tick's detection list (device); read instead of n
 };
 void launch_track_update(const TrackArgs &a, hipStream_t s);
+struct RansacState;
+// [EXTENSION] X15 the tick's detection list (gv_track.hip, k_tick_dets; the arithmetic is gv_pose_math.hpp's): the valid
+// candidates of a tick's pose branch in order, in the base frame, into `out`.  One workgroup.
+struct TickDetsArgs {
+  int32_t mode;                 // kTickDetsNone: an empty list; kTickDetsVision: candidates are vout; kTickDetsPca: cam + valid
+  int32_t n_cand;               // 0 .. kTickDetCandidates
+  const VisionOut *vout;        // vision: n_cand records (device)
+  const gv_lshape_pose *cam;    // PCA: n_cand camera-frame poses (device)
+  const uint8_t *valid;         // PCA: n_cand flags (device)
+  const RansacState *st;        // PCA: the ground plane's state (device): decides "empty segmented cloud"
+  uint64_t n_cloud;             // PCA: points of the cloud the tick read
+  gv_transform tf_bc;           // base <- camera
+  TickDetList *out;             // device
+};
+enum : int32_t { kTickDetsNone = 0, kTickDetsVision = 1, kTickDetsPca = 2 };
+void launch_tick_dets(const TickDetsArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)
@@ -561,6 +580,7 @@ struct PcaRectArgs {
   RansacState *st_copy;     // optional, 8-byte aligned: *st rides home in the same block (64-bit words)
   gv_lshape_pose *poses_dev;   // optional, device memory: a second copy with a NaN length where valid[b] == 0 (no pose:
                                // its corners fail getIndex, so k_rects_from_poses gives no cells)
+  uint8_t *valid_dev;          // optional, device memory: a second copy of `valid` (X15: k_tick_dets reads it)
 };
 void launch_pca_rect(const PcaRectArgs &a, const CallDone &done, hipStream_t s);
 

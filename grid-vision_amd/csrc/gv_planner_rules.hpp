@@ -144,6 +144,14 @@ inline bool track_update_ok(const gv_lshape_pose *dets, int32_t n, double dt, co
   return n >= 0 && n <= kTrackSlots && (n == 0 || dets) && std::isfinite(dt) && dt >= 0.0 && (!motion || transform_finite(*motion));
 }
 
+// gv_track_update*'s flag word: known bits only; [EXTENSION] X15 GV_TRACK_TICK_DETS names its own detections, so it goes
+// with no dets, n == 0 and not with GV_TRACK_DEVICE_DETS
+inline bool track_update_flags_ok(uint32_t flags, const gv_lshape_pose *dets, int32_t n)
+{
+  if ((flags & ~(uint32_t)(GV_TRACK_DEVICE_DETS | GV_TRACK_FEED_DYNAMIC | GV_TRACK_TICK_DETS)) != 0) return false;
+  return !(flags & GV_TRACK_TICK_DETS) || (!dets && n == 0 && !(flags & GV_TRACK_DEVICE_DETS));
+}
+
 // gv_set_tracks' rules into a state block; false (st untouched) when they do not hold
 inline bool track_state_from(const gv_track *tracks, int32_t n, uint32_t next_id, TrackState &st)
 {

@@ -70,6 +70,15 @@ typedef struct gv_test_sector_plan_t {
 } gv_test_sector_plan_t;
 int gv_test_sector_plan(int32_t nx, int32_t ny, int32_t cx, int32_t cy, int64_t n_points, gv_test_sector_plan_t *plan,
                         int32_t *wg /* 7 * wg_cap */, int64_t wg_cap);
+/* [EXTENSION] X15.  gv_test_tick_dets: a synchronous read-back (it waits for gv_stream(h)) of the detection list the last
+ * GV_TICK_KEEP_DETS tick left on the device: the 128 records as they lie there, *n = records used, *n_total = poses found.
+ * GV_ERR_STATE when the last tick enqueued did not carry the flag.  No kernel of its own.
+ * gv_test_tick_dets_host: host only, no handle and no device: the selection and the camera->base transform of k_tick_dets
+ * (csrc/gv_pose_math.hpp: the same text) over n_cand camera-frame poses and their valid flags; empty != 0 is the "empty
+ * segmented cloud" outcome (tests/test_tick_track_host.py, tests/test_gpu_tick_track.py). */
+int gv_test_tick_dets(gv_handle h, gv_lshape_pose *out /* 128 */, int32_t *n, int32_t *n_total);
+int gv_test_tick_dets_host(const gv_lshape_pose *cam, const uint8_t *valid, int32_t n_cand, int32_t empty, const gv_transform *tf_bc,
+                           gv_lshape_pose *out /* 128 */, int32_t *n, int32_t *n_total);
 #ifdef __cplusplus
 }
 #endif

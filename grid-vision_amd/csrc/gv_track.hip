@@ -31,6 +31,7 @@
 //   slot below 128, and are used as indices only when >= 0; a rank is below its total, and every total is at most
 //   128 = the rows of `tracks`, of the object table and of unm_list.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+// Behind it: [EXTENSION] X15 k_tick_dets, which leaves a tick's detection list where k_track_update reads it.
 #include "gv_device.hpp"
 #include "gv_track.hpp"
 
@@ -72,7 +73,7 @@ __global__ void __launch_bounds__(kThreads) k_track_update(TrackArgs a)
 
   const int tid = (int)threadIdx.x, i = tid & (kTrackSlots - 1);
   const bool row = tid < kTrackSlots;
-  const int n = max(0, min(a.n, kTrackSlots));
+  const int n = max(0, min(a.n_dev ? *a.n_dev : a.n, kTrackSlots));   // n_dev: a tick's list (X15), whose count the host never learns
   const uint32_t next_id = a.fresh ? 1u : a.state->next_id;
 
   // ---- steps 1 to 3
@@ -243,6 +244,84 @@ __global__ void __launch_bounds__(kThreads) k_track_update(TrackArgs a)
       }
     }
   }
+}
+
+// ---- [EXTENSION] X15 the tick's detection list (GV_TICK_KEEP_DETS) ----
+// One workgroup of four wavefronts walks the candidates in chunks of 256, thread t of a chunk owning candidate c0 + t.
+// A candidate that tick_det_take keeps gets its rank by an ordered compaction: the wavefront's ballot gives the kept
+// lanes below it, four LDS words the kept candidates of the wavefronts before it, `base` those of the chunks before.  The
+// owner of a kept candidate of rank < 128 builds the camera-frame pose, moves it to the base frame (gv_pose_math.hpp:
+// the host's text) and stores the record's 80 bytes as five 16-byte vector stores; ranks from 128 on are only counted.
+// The records behind the last one are zeroed, so every byte of the list is written by every launch.
+// Bounds: c < n_cand <= kTickDetCandidates indexes vout / cam / valid; rank < kTickDets indexes out->p; the zeroing
+// runs over [n, kTickDets).  cnt_s is double-buffered by the chunk's parity: one barrier per chunk.
+namespace {
+constexpr int kDetThreads = 256;
+
+__device__ __forceinline__ void store_pose(gv_lshape_pose *dst, const gv_lshape_pose &p)
+{
+  static_assert(sizeof(gv_lshape_pose) == 80, "five double2");
+  double2 *d = reinterpret_cast<double2 *>(dst);
+  d[0] = make_double2(p.px, p.py);
+  d[1] = make_double2(p.pz, p.qx);
+  d[2] = make_double2(p.qy, p.qz);
+  d[3] = make_double2(p.qw, p.length);
+  d[4] = make_double2(p.width, p.height);
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kDetThreads) k_tick_dets(TickDetsArgs a)
+{
+  __shared__ int32_t cnt_s[2][kDetThreads / 64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n_cand = a.mode == kTickDetsNone ? 0 : max(0, min(a.n_cand, kTickDetCandidates));
+  bool empty = false;
+  if (a.mode == kTickDetsPca) {
+    const RansacState st = *a.st;
+    empty = tick_dets_empty(st.best_count, st.n_inliers, a.n_cloud);
+  }
+  int base = 0;
+  for (int c0 = 0, it = 0; c0 < n_cand; c0 += kDetThreads, ++it) {
+    const int c = c0 + tid;
+    int32_t valid = 0;
+    if (c < n_cand) valid = a.mode == kTickDetsVision ? a.vout[c].valid : (int32_t)a.valid[c];
+    const bool take = c < n_cand && tick_det_take(empty, valid);
+    const unsigned long long b = __ballot(take);
+    if (lane == 0) cnt_s[it & 1][wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kDetThreads / 64; ++w) {
+      const int k = cnt_s[it & 1][w];
+      before += w < wave ? k : 0;
+      total += k;
+    }
+    const int rank = base + before + __popcll(b & ((1ull << lane) - 1ull));
+    if (take && rank < kTickDets) {
+      gv_lshape_pose p;
+      if (a.mode == kTickDetsVision) {
+        const VisionOut vo = a.vout[c];
+        double sp, cp;
+        sincos((double)(-vo.orient) * 0.5, &sp, &cp);
+        p = tick_vision_pose(vo, cp, sp);
+      } else
+        p = a.cam[c];
+      store_pose(a.out->p + rank, tick_det_record(a.tf_bc, p));
+    }
+    base += total;
+  }
+  const int n = min(base, kTickDets);
+  for (int i = n * 5 + tid; i < kTickDets * 5; i += kDetThreads) reinterpret_cast<double2 *>(a.out->p)[i] = make_double2(0.0, 0.0);
+  if (tid == 0) {
+    a.out->n = n;
+    a.out->n_total = base;
+    a.out->pad[0] = a.out->pad[1] = 0;
+  }
+}
+
+void launch_tick_dets(const TickDetsArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_tick_dets, dim3(1), dim3(kDetThreads), 0, s, a);
 }
 
 void launch_track_update(const TrackArgs &a, hipStream_t s)

@@ -29,6 +29,8 @@ FRAME_VISION_ORIENT = 1 << 5
 TICK_VISION_ORIENT = 1 << 0
 TICK_LIDAR_BIN = 1 << 1
 TICK_LIDAR_RAYMARCH = 1 << 2
+TICK_KEEP_DETS = 1 << 3     # [EXTENSION] X15: the tick leaves its detection list on the device
+TICK_DETS = 128             # records of that list
 
 INFLATE_KEEP_DIST2 = 1 << 0
 INFLATE_OCCUPANCY_SCALE = 1 << 1
@@ -59,6 +61,7 @@ MOVING_OBJECT_DTYPE = np.dtype([("pose", LSHAPE_DTYPE), ("vx", np.float64), ("vy
 TRACK_SLOTS = 128
 TRACK_DEVICE_DETS = 1 << 0
 TRACK_FEED_DYNAMIC = 1 << 1
+TRACK_TICK_DETS = 1 << 2    # [EXTENSION] X15: the detections are the last tick's list
 TRACK_DTYPE = np.dtype([("id", np.uint32), ("slot", np.int32), ("hits", np.int32), ("misses", np.int32), ("age", np.int32),
                         ("det", np.int32)] + [(n, np.float64) for n in ("x", "y", "vx", "vy", "qx", "qy", "qz", "qw", "length",
                                                                          "width", "p00", "p01", "p11")])   # gv_track
@@ -412,6 +415,22 @@ def shard_band_rows(rank, world, ny):
     if rc:
         raise GVError(rc, "gv_shard_band_rows")
     return y0.value, y1.value
+
+
+def tick_dets_host(cam, valid, tf_bc, empty=False):
+    """test hook (csrc/gv_test_hooks.h): the detection list k_tick_dets makes of the camera-frame poses `cam`
+    (LSHAPE_DTYPE) and their valid flags under base<-camera tf_bc (a Transform or its seven values), from the same text
+    compiled for the host: (the 128 records, n, n_total) (host only; needs no GPU)"""
+    cam = np.ascontiguousarray(cam, LSHAPE_DTYPE).reshape(-1)
+    valid = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+    assert len(cam) == len(valid)
+    tf = tf_bc if isinstance(tf_bc, Transform) else make_tf(tf_bc)
+    out, n, nt = np.zeros(TICK_DETS, LSHAPE_DTYPE), C.c_int32(-1), C.c_int32(-1)
+    rc = load().gv_test_tick_dets_host(_ptr(cam) if len(cam) else None, _ptr(valid) if len(cam) else None, C.c_int32(len(cam)),
+                                       C.c_int32(1 if empty else 0), C.byref(tf), _ptr(out), C.byref(n), C.byref(nt))
+    if rc:
+        raise GVError(rc, "gv_test_tick_dets_host")
+    return out, n.value, nt.value
 
 
 def shard_plan(nx, ny, world):
@@ -1105,12 +1124,13 @@ class GridVisionHIP:
         self._ck(self._lib.gv_get_tracks(self._h, _ptr(out), C.c_int32(TRACK_SLOTS), C.byref(n), C.byref(nid)), "gv_get_tracks")
         return out[:n.value].copy(), nid.value
 
-    def track_update_async(self, dets, dt, motion=None, feed=False, info=None, tracks=None, device_ptr=None, n=None):
+    def track_update_async(self, dets, dt, motion=None, feed=False, info=None, tracks=None, device_ptr=None, n=None, from_tick=False):
         """enqueue one update on stream(): dets an LSHAPE_DTYPE array, free on return (with
         device_ptr and n: n records at that device address), motion None, a Transform or its seven values, feed: the
         exported tracks become the moving objects of the scoring calls that follow; info None or a TRACK_INFO_DTYPE
-        array of 1, tracks None or a TRACK_DTYPE array of 128, both complete after synchronize()"""
-        flags = TRACK_FEED_DYNAMIC if feed else 0
+        array of 1, tracks None or a TRACK_DTYPE array of 128, both complete after synchronize().  from_tick: the
+        detections are the list of the last tick_enqueue(keep_dets=True), read on the device (dets must then be None)"""
+        flags = (TRACK_FEED_DYNAMIC if feed else 0) | (TRACK_TICK_DETS if from_tick else 0)
         if device_ptr is not None:
             src, cnt, flags = C.c_void_p(int(device_ptr)), int(n), flags | TRACK_DEVICE_DETS
         else:
@@ -1121,12 +1141,13 @@ class GridVisionHIP:
         self._ck(self._lib.gv_track_update_async(self._h, src, C.c_int32(cnt), C.c_double(dt), C.byref(m) if m is not None else None,
                                                  C.c_uint32(flags), _ptr(info), _ptr(tracks)), "gv_track_update_async")
 
-    def track_update(self, dets, dt, motion=None, feed=False):
-        """one update, waited for: returns (info, tracks), the TRACK_INFO_DTYPE record and the live TRACK_DTYPE records"""
+    def track_update(self, dets, dt, motion=None, feed=False, from_tick=False):
+        """one update, waited for: returns (info, tracks), the TRACK_INFO_DTYPE record and the live TRACK_DTYPE records.
+        from_tick: as in track_update_async"""
         z, m = _detections(dets), _motion(motion)
         info, tracks = np.zeros(1, TRACK_INFO_DTYPE), np.zeros(TRACK_SLOTS, TRACK_DTYPE)
         self._ck(self._lib.gv_track_update(self._h, _ptr(z) if len(z) else None, C.c_int32(len(z)), C.c_double(dt),
-                                           C.byref(m) if m is not None else None, C.c_uint32(TRACK_FEED_DYNAMIC if feed else 0),
+                                           C.byref(m) if m is not None else None, C.c_uint32((TRACK_FEED_DYNAMIC if feed else 0) | (TRACK_TICK_DETS if from_tick else 0)),
                                            _ptr(info), _ptr(tracks)), "gv_track_update")
         return info[0], tracks[:int(info[0]["n_tracks"])].copy()
 
@@ -1411,11 +1432,14 @@ class GridVisionHIP:
         return a.value, b.value
 
     # ---- the node's tick (timerCallback from filterBBoxes on, one host wait)
-    def tick_enqueue(self, bboxes, k_near=4, net=None, vision=False, lidar_bin=False, lidar_raymarch=False, grid_out=None):
-        """net: (orient, conf, dims) of the DYNAMIC boxes in filter_bboxes order (vision=True); grid_out: PinnedI8 array"""
+    def tick_enqueue(self, bboxes, k_near=4, net=None, vision=False, lidar_bin=False, lidar_raymarch=False, grid_out=None,
+                     keep_dets=False):
+        """net: (orient, conf, dims) of the DYNAMIC boxes in filter_bboxes order (vision=True); grid_out: PinnedI8 array;
+        keep_dets: the tick leaves its detection list on the device for track_update*(from_tick=True)"""
         b = np.ascontiguousarray(bboxes if bboxes is not None else np.zeros(0, BBOX_DTYPE), dtype=BBOX_DTYPE)
         d = TickDesc()
         d.flags = (TICK_VISION_ORIENT if vision else 0) | (TICK_LIDAR_BIN if lidar_bin else 0) | (TICK_LIDAR_RAYMARCH if lidar_raymarch else 0)
+        d.flags |= TICK_KEEP_DETS if keep_dets else 0
         d.bboxes, d.n_bboxes = (b.ctypes.data if len(b) else None), len(b)
         keep = [b]
         if net is not None:
@@ -1445,6 +1469,13 @@ class GridVisionHIP:
     def tick(self, bboxes, **kw):
         self.tick_enqueue(bboxes, **kw)
         return self.tick_wait()
+
+    def tick_dets(self):
+        """test hook (csrc/gv_test_hooks.h): (the 128 records, n, n_total) of the detection list the last
+        tick_enqueue(keep_dets=True) left on the device; waits for stream()"""
+        out, n, nt = np.zeros(TICK_DETS, LSHAPE_DTYPE), C.c_int32(-1), C.c_int32(-1)
+        self._ck(self._lib.gv_test_tick_dets(self._h, _ptr(out), C.byref(n), C.byref(nt)), "gv_test_tick_dets")
+        return out, n.value, nt.value
 
     # ---- multi-GPU (RCCL inside the library)
     @staticmethod

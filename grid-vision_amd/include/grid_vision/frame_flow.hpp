@@ -55,6 +55,12 @@ struct FlowParams {
   // is what it was.
   bool track_objects = false;
   gv_track_config track{2.0, 2.0, 0.3, 5.0, 0.3, 2, 3, 0};
+  // [EXTENSION] X15: with track_objects, where the fused tick runs, the tick leaves its detection list on the device
+  // (GV_TICK_KEEP_DETS) and the tracker's update is enqueued from it (GV_TRACK_TICK_DETS) BEFORE the tick's wait: the
+  // detections never come up to the host on their way into the tracker.  Every other branch (the call-by-call flow,
+  // NoDetections, the skipped ticks, the accumulated dt and motion) is as above.  false (default): every output of the
+  // flow is what it was.
+  bool track_on_device = false;
 };
 
 // what one tick of the 50 ms timer (grid_vision_node.cpp:49-50) has to work with
@@ -133,22 +139,25 @@ public:
 
   TickResult tick(const TickInput &in)
   {
-    TickResult r = tickMap(in);
     if (p_.track_objects) {
       // what the tracker is owed: the time and the motion of every tick since its last update, the skipped ones included
-      // (moveMap has run for each of them)
+      // (moveMap runs for each of them)
       track_dt_ += in.dt;
       if (p_.ego_motion && in.motion) {
         track_motion_ = have_track_motion_ ? compose_motion(track_motion_, *in.motion) : *in.motion;
         have_track_motion_ = true;
       }
-      if (r.branch != TickBranch::MissingInputs && r.branch != TickBranch::NoTransform) {
+    }
+    tracked_on_device_ = false;
+    TickResult r = tickMap(in);
+    if (p_.track_objects && r.branch != TickBranch::MissingInputs && r.branch != TickBranch::NoTransform) {
+      if (!tracked_on_device_) {   // (X15: the fused tick has enqueued the update from its list already)
         const std::vector<LShapePose> dets(r.bboxes_pose.begin(),
                                            r.bboxes_pose.begin() + (std::ptrdiff_t)std::min<size_t>(r.bboxes_pose.size(), 128));
         grid_.trackUpdateAsync(dets, track_dt_, have_track_motion_ ? &track_motion_ : nullptr, true);   // dets is free on return
-        track_dt_ = 0.0;
-        have_track_motion_ = false;
       }
+      track_dt_ = 0.0;
+      have_track_motion_ = false;
     }
     return r;
   }
@@ -238,9 +247,15 @@ private:
         n_net = (int32_t)r.dynamic_bboxes.size();
     }
     if (p_.lidar_binning && ctx_.cloudSize() > 0) flags |= GV_TICK_LIDAR_BIN | (p_.lidar_raymarch ? GV_TICK_LIDAR_RAYMARCH : 0u);
+    const bool on_device = p_.track_objects && p_.track_on_device;
+    if (on_device) flags |= GV_TICK_KEEP_DETS;
     ctx_.tickEnqueue(r.bboxes, flags, p_.k_near, n_net ? orient.data() : nullptr, n_net ? conf.data() : nullptr,
                      n_net ? dims.data() : nullptr, n_net, grid_out_);
     if (p_.inflate_costmap) grid_.inflate();   // between enqueue and wait: it inflates the tick's grid
+    if (on_device) {   // X15: the tracker reads the tick's list where the tick leaves it, behind the tick and before its wait
+      grid_.trackUpdateFromTickAsync(track_dt_, have_track_motion_ ? &track_motion_ : nullptr, true);
+      tracked_on_device_ = true;
+    }
     GridVisionContext::TickOutput t = ctx_.tickWait();
     r.depth_vec = std::move(t.depths);
     r.cam_points = std::move(t.base_points);
@@ -277,6 +292,7 @@ private:
   double track_dt_ = 0.0;                // X14: time and motion since the tracker's last update
   gv_transform track_motion_{};
   bool have_track_motion_ = false;
+  bool tracked_on_device_ = false;       // X15: this tick's update was enqueued from the tick's list
 };
 
 inline const char *branch_name(TickBranch b)

@@ -372,6 +372,14 @@ public:
                                     nullptr, nullptr),
               ctx_.handle(), "gv_track_update_async");
   }
+  // [EXTENSION] X15: the detections are the list the last tickEnqueue with GV_TICK_KEEP_DETS leaves on the device
+  // (GV_TRACK_TICK_DETS), read in place behind the tick; the tick may still be pending
+  void trackUpdateFromTickAsync(double dt, const gv_transform *motion, bool feed)
+  {
+    gv::check(gv_track_update_async(ctx_.handle(), nullptr, 0, dt, motion, GV_TRACK_TICK_DETS | (feed ? GV_TRACK_FEED_DYNAMIC : 0u),
+                                    nullptr, nullptr),
+              ctx_.handle(), "gv_track_update_async");
+  }
   gv_track_info trackUpdate(const std::vector<LShapePose> &dets, double dt, const gv_transform *motion, bool feed,
                             std::vector<gv_track> *tracks = nullptr)
   {

@@ -1010,6 +1010,12 @@ int gv_control_select_dyn(const gv_critic_weights *w, const gv_traj_score *traj,
  *   GV_ERR_BAD_ARG for a null handle, n outside 0..128, null dets with n > 0, dt not finite or < 0, a non-finite field
  *   of motion, or unknown flags; GV_ERR_STATE without a configuration.  gv_track_update is the same call followed by
  *   the wait.
+ *   [EXTENSION] X15: with GV_TRACK_TICK_DETS the detections are the list of the most recently enqueued tick
+ *   (GV_TICK_KEEP_DETS: the poses of grid_vision_node.cpp:204 / :227), read in place on the device behind the tick,
+ *   pending or already waited for; the kernel reads their number there and the host never learns it.  dets must be
+ *   NULL and n 0, and GV_TRACK_DEVICE_DETS must not be set with it: GV_ERR_BAD_ARG otherwise.  GV_ERR_STATE when no
+ *   tick was enqueued or the last one enqueued did not carry GV_TICK_KEEP_DETS.  Everything else is as above; two
+ *   updates from one list see the same list twice, and a later gv_tick_enqueue is ordered behind them.
  * gv_track_step is host only and takes no handle: the same arithmetic text compiled for the host.  tracks (room for
  *   128), *n_tracks and *next_id are in/out, under gv_set_tracks' rules on the way in and gv_get_tracks' order on the
  *   way out; info may be NULL; objs (room for 128) and n_objs may be NULL together.  Its objs, given to
@@ -1042,7 +1048,8 @@ typedef struct {
 } gv_track_info;        /* 40 bytes */
 enum {
   GV_TRACK_DEVICE_DETS  = 1 << 0,   /* dets is device memory, read in place                  */
-  GV_TRACK_FEED_DYNAMIC = 1 << 1    /* the exported tracks become X13's moving-object set    */
+  GV_TRACK_FEED_DYNAMIC = 1 << 1,   /* the exported tracks become X13's moving-object set    */
+  GV_TRACK_TICK_DETS    = 1 << 2    /* [EXTENSION] X15: the detections are the last tick's list */
 };
 int gv_set_track_config(gv_handle h, const gv_track_config *cfg);   /* NULL = off, the state after gv_create */
 int gv_set_tracks(gv_handle h, const gv_track *tracks, int32_t n, uint32_t next_id);
@@ -1133,8 +1140,20 @@ int gv_get_ray_stats(gv_handle h, uint64_t *n_rays, uint64_t *n_visits);
 enum {
   GV_TICK_VISION_ORIENT  = 1 << 0,  /* use_vision_orientation (config/grid_vision_cfg.yaml:24) */
   GV_TICK_LIDAR_BIN      = 1 << 1,  /* [EXTENSION] the map update also bins the resident cloud (X1) ...  */
-  GV_TICK_LIDAR_RAYMARCH = 1 << 2   /* [EXTENSION] ... and marks free space (X2); tile-path grids only   */
+  GV_TICK_LIDAR_RAYMARCH = 1 << 2,  /* [EXTENSION] ... and marks free space (X2); tile-path grids only   */
+  GV_TICK_KEEP_DETS      = 1 << 3   /* [EXTENSION] X15: the tick leaves its detection list on the device (below) */
 };
+/* [EXTENSION] X15 the tick's detection list.  With GV_TICK_KEEP_DETS the tick's batch ends, inside what gv_tick_wait
+ * waits for, with one more kernel that leaves in device memory of the handle's own exactly what gv_tick_wait returns in
+ * poses[0 .. min(n_poses, 128)): the dynamic objects' base-frame poses after transformLShapeObjects
+ * (grid_vision_node.cpp:204 for the orientation network, :227 for computeBBoxPose), 128 records with zero bytes behind
+ * the last one, their number and n_poses itself.  The list is empty where gv_tick_wait returns no poses (no dynamic
+ * boxes, n_net == 0, fewer than three points, pca_empty: the kernel decides that from the ground plane's state on the
+ * device).  The selection and the camera->base arithmetic are the host's text compiled for the device and give its bytes;
+ * only the orientation network's quaternion starts from the device's fp64 sincos of -orient/2 instead of the host's and
+ * may differ from gv_tick_wait's by a few units of 2^-53.  Without the flag a tick enqueues what it always
+ * did.  gv_track_update* with GV_TRACK_TICK_DETS reads the list in place: tick -> tracker -> X13 -> gv_mppi_cycle_async
+ * is then one batch on gv_stream(h) with one wait, and the host never sees the detections. */
 typedef struct {
   uint32_t flags;
   const gv_bbox *bboxes;             /* what extract_bboxes returned (:138-139): static and dynamic mixed */

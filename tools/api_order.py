@@ -15,9 +15,10 @@ python3 tools/api_order.py shard  runs the sharded frame on a fresh handle with 
 GV_QUEUE_PROBE=0 itself): process_frame_sharded plain, with KEEP_COUNTS, and with everything it can keep plus boxes and
 poses; six frames in flight; the stage timing; the three-rank emulation; comm_destroy and one plain frame.  RCCL's own HIP
 calls are in both builds' traces alike.
-python3 tools/api_order.py compare a_hip_api_trace.csv b_hip_api_trace.csv [--no-alloc] [--no-query]  prints the first
-differences; --no-alloc leaves hipMalloc and hipFree out of both lists (a change of who owns which buffer moves only
-those), --no-query hipStreamQuery (the result block's wait asks the stream once per 4096 spins: how often is timing)."""
+python3 tools/api_order.py compare a_hip_api_trace.csv b_hip_api_trace.csv [--no-alloc] [--no-query] [--no-register]  prints
+the first differences; --no-alloc leaves hipMalloc and hipFree out of both lists (a change of who owns which buffer moves
+only those), --no-query hipStreamQuery (the result block's wait asks the stream once per 4096 spins: how often is timing),
+--no-register the __hipRegister* calls of the library's load (a build with one kernel more registers one function more)."""
 import csv, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -258,6 +259,8 @@ if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "compare":
         skip = ("hipMalloc", "hipFree") * ("--no-alloc" in sys.argv[4:]) + ("hipStreamQuery",) * ("--no-query" in sys.argv[4:])
         a, b = names(sys.argv[2], skip), names(sys.argv[3], skip)
+        if "--no-register" in sys.argv[4:]:
+            a, b = ([n for n in l if not n.startswith("__hipRegister")] for l in (a, b))
         diff = [(i, p, q) for i, (p, q) in enumerate(zip(a, b)) if p != q]
         print(f"{len(a)} and {len(b)} HIP API calls, {len(diff)} positions differ" + ("" if diff or len(a) != len(b) else ": identical order"))
         for i, p, q in diff[:20]:
