@@ -667,9 +667,11 @@ int begin_cloud_upload(gv_context *h, size_t n, int &target)
   h->quiet_frames = 0;   // the upload stream is in use: the frames stay off it for a while
   CloudSet &c = h->cloud[target];
   const bool tick_reads = h->tick.pending && h->tick.cloud == target;
+  const bool match_reads = (h->match.clouds >> target & 1u) != 0;   // X16: a gv_match_scan* enqueued since reads this set
   if (n > c.cap) {
     if (c.release_slot >= 0) GV_HIP(hipEventSynchronize(h->ev_fin[c.release_slot]));
     if (tick_reads) GV_HIP(hipEventSynchronize(h->tick.done));   // the tick's kernels read the block freed here
+    if (match_reads) GV_HIP(hipEventSynchronize(h->match.read));
     GV_HIP(hipEventSynchronize(c.ready));
     c.cap = 0;
     const size_t want = (n + n / 8 + 1024 + 3) & ~(size_t)3;   // the arrays sit at a stride of (n + 3) & ~3 floats
@@ -687,6 +689,10 @@ int begin_cloud_upload(gv_context *h, size_t n, int &target)
   if (c.release_slot >= 0 && hipEventQuery(h->ev_fin[c.release_slot]) != hipSuccess)
     GV_HIP(hipStreamWaitEvent(h->stream_copy, h->ev_fin[c.release_slot], 0));
   if (tick_reads) GV_HIP(hipStreamWaitEvent(h->stream_copy, h->tick.done, 0));   // on the device: the upload stays asynchronous
+  if (match_reads) {   // the event of the last call: behind every earlier call's point pass on the public stream
+    GV_HIP(hipStreamWaitEvent(h->stream_copy, h->match.read, 0));
+    h->match.clouds &= ~(1u << target);
+  }
   c.release_slot = -1;
   return GV_OK;
 }

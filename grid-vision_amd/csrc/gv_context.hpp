@@ -458,6 +458,25 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<gv_track_info> d_info;
     DevBuf<gv_track> d_tracks;
   } trk;
+  // [EXTENSION] X16 scan-to-costmap matching (gv_set_match_config / gv_match_scan*, gv_api_match.hip).  The
+  // configuration is handle state and travels in the kernel arguments with the guess and the rotation table.  `pts`
+  // (the used points' base-frame x, y) and `head` (the counter of used points, then the score volume) are the scratch
+  // of one call, made by the first call that needs them and used on the public stream only: a call's memset and
+  // kernels run behind those of the call before it.  d_result follows TrajScore's rules.  `read` marks the point pass
+  // of the last call, the one kernel that reads the cloud; it is recorded again by every call on the one in-order
+  // stream, so whoever waits for it is behind every earlier call's point pass too.  `clouds` has bit s set when a call
+  // has read cloud set s since the set was last uploaded into or the streams were last drained: any number of calls
+  // may be in flight over the three sets, and an upload into a set whose bit is set waits for `read` and clears that
+  // bit alone (begin_cloud_upload).  gv_reset keeps all of it.
+  struct Match {
+    bool set = false;
+    gv_match_config cfg{};
+    DevBuf<float2> pts;
+    DevBuf<uint32_t> head;
+    DevBuf<gv_match_result> d_result;
+    Event read;
+    uint32_t clouds = 0;
+  } match;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
   // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in

@@ -7,6 +7,7 @@
 #include "gv_types.hpp"
 #include "gv_dyn.hpp"
 #include "gv_track.hpp"
+#include "gv_match.hpp"
 #include "gv_pose_math.hpp"
 
 namespace gv {
@@ -295,6 +296,28 @@ struct TickDetsArgs {
 };
 enum : int32_t { kTickDetsNone = 0, kTickDetsVision = 1, kTickDetsPca = 2 };
 void launch_tick_dets(const TickDetsArgs &a, hipStream_t s);
+// [EXTENSION] X16 scan-to-costmap matching (gv_match.hip; the arithmetic is gv_match.hpp's).  The configuration, the
+// guess and the host-built rotation table travel by value: a call already enqueued keeps what it was enqueued with.
+// `head` is one zeroed block per call: word 0 counts the used points, the volume starts at word kMatchHeadWords.
+constexpr int32_t kMatchHeadWords = 4;
+struct MatchArgs {
+  GridParams g;
+  MatchParams p;
+  Mat34f m_base;
+  HeightBand band;
+  const float *x, *y, *z;       // the resident cloud (device)
+  uint32_t n;                   // its points
+  uint32_t n_sel;               // ceil(n / stride): the selected ones
+  float2 *pts;                  // n_sel pairs (device): the used points' (bx, by), in any order
+  uint32_t *head;               // kMatchHeadWords + NT*NY*NX words (device), zero when the point pass starts
+  const uint8_t *cost;          // the resident costmap
+  gv_match_result *result;      // one record (device memory, or the device view of pinned host memory; 8-byte aligned)
+  uint32_t *scores_out;         // null, or the device view of a pinned destination of the volume
+  float rot[2 * kMatchMaxSide]; // (c_t, s_t), NT pairs
+};
+void launch_match_points(const MatchArgs &a, hipStream_t s);
+void launch_match_score(const MatchArgs &a, hipStream_t s);
+void launch_match_select(const MatchArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

@@ -70,6 +70,19 @@ TRACK_INFO_DTYPE = np.dtype([(n, np.int32) for n in ("n_tracks", "n_confirmed", 
                             [("next_id", np.uint32), ("reserved", np.uint32)])   # gv_track_info
 assert TRACK_DTYPE.itemsize == 128 and TRACK_INFO_DTYPE.itemsize == 40
 
+# [EXTENSION] X16 scan-to-costmap matching (include/gridvision_hip_match.h)
+MATCH_USE_BAND = 1 << 0      # MatchConfig.flags
+MATCH_KEEP_SCORES = 1 << 0   # a call's flags
+MATCH_MAX_HALF = 32
+MATCH_RESULT_DTYPE = np.dtype([("best_t", np.int32), ("best_j", np.int32), ("best_i", np.int32), ("valid", np.int32),
+                               ("n_used", np.uint32), ("best_score", np.uint32), ("guess_score", np.uint32),
+                               ("reserved", np.uint32), ("x", np.float64), ("y", np.float64), ("yaw", np.float64),
+                               ("reserved2", np.uint64)])   # gv_match_result
+assert MATCH_RESULT_DTYPE.itemsize == 64
+# every symbol include/gridvision_hip_match.h declares (a header of its own: ABI_SYMBOLS stays gridvision_hip.h's)
+MATCH_SYMBOLS = ["gv_set_match_config", "gv_match_scan_async", "gv_match_scan", "gv_match_scan_host", "gv_match_rotations",
+                 "gv_match_motion"]
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -257,6 +270,32 @@ class TrackConfig(C.Structure):
     def of(cls, gate=2.0, sigma_accel=1.0, sigma_meas=0.2, sigma_v0=5.0, min_speed=0.0, confirm_hits=2, max_misses=3, flags=0):
         return cls(float(gate), float(sigma_accel), float(sigma_meas), float(sigma_v0), float(min_speed), int(confirm_hits),
                    int(max_misses), int(flags))
+
+
+class MatchConfig(C.Structure):
+    """gv_match_config: the window's half-widths in cells (wx, wy) and yaw steps (wt), the yaw step, every stride-th
+    point of the cloud, the used points a valid match needs, MATCH_USE_BAND"""
+    _fields_ = [("wx", C.c_int32), ("wy", C.c_int32), ("wt", C.c_int32), ("stride", C.c_int32), ("yaw_step", C.c_double),
+                ("min_points", C.c_int32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, wx=8, wy=8, wt=4, yaw_step=0.01, stride=1, min_points=1, use_band=False, flags=0):
+        return cls(int(wx), int(wy), int(wt), int(stride), float(yaw_step), int(min_points),
+                   int(flags) | (MATCH_USE_BAND if use_band else 0))
+
+    @property
+    def shape(self):
+        """(NT, NY, NX) of the score volume"""
+        return 2 * self.wt + 1, 2 * self.wy + 1, 2 * self.wx + 1
+
+
+class MatchGuess(C.Structure):
+    """gv_match_guess: the pose of the current base frame in the grid's frame"""
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double)]
+
+
+def _guess(guess):
+    return guess if isinstance(guess, MatchGuess) else MatchGuess(*[float(v) for v in guess])
 
 
 def moving_objects(rows):
@@ -618,6 +657,45 @@ def track_step(cfg, tracks, next_id, dets, dt, motion=None):
     return buf[:n_t.value].copy(), nid.value, info[0], objs[:n_o.value].copy()
 
 
+def match_rotations(cfg, guess):
+    """the float32 (NT, 2) table of (cos, sin) of a MatchConfig's yaw candidates around a guess (host only)"""
+    table = np.zeros((2 * MATCH_MAX_HALF + 1, 2), np.float32)
+    q = _guess(guess)
+    rc = load().gv_match_rotations(C.byref(cfg), C.byref(q), _ptr(table))
+    if rc:
+        raise GVError(rc, "gv_match_rotations")
+    return table[:cfg.shape[0]].copy()
+
+
+def match_motion(result):
+    """the Transform (motion of grid_move and track_update) of a MATCH_RESULT_DTYPE record (host only)"""
+    r = np.ascontiguousarray(result, MATCH_RESULT_DTYPE).reshape(-1)[:1]
+    out = Transform()
+    rc = load().gv_match_motion(_ptr(r), C.byref(out))
+    if rc:
+        raise GVError(rc, "gv_match_motion")
+    return out
+
+
+def match_scan_host(grid_x, grid_y, resolution, cost, x, y, z, base_lidar, cfg, guess, band=None, keep_scores=False):
+    """gv_match_scan_host, the library's host twin of match_scan (needs no GPU): cost the uint8 costmap of G bytes in
+    data order, x / y / z the lidar-frame cloud, base_lidar the seven values of base_from_lidar, band None or (z_ground,
+    z_max).  Returns the MATCH_RESULT_DTYPE record, and with keep_scores also the uint32 (NT, NY, NX) volume."""
+    cost = np.ascontiguousarray(cost, np.uint8).reshape(-1)
+    x, y, z = _f32(x), _f32(y), _f32(z)
+    tf, q = make_tf(base_lidar), _guess(guess)
+    hb = HeightBand(float(band[0]), float(band[1]), 0) if band is not None else None
+    res = np.zeros(1, MATCH_RESULT_DTYPE)
+    vol = np.zeros(cfg.shape, np.uint32) if keep_scores else None
+    rc = load().gv_match_scan_host(C.c_uint8(grid_x), C.c_uint8(grid_y), C.c_double(resolution), _ptr(cost), _ptr(x), _ptr(y),
+                                   _ptr(z), C.c_size_t(len(x)), C.byref(tf), C.byref(hb) if hb is not None else None,
+                                   C.byref(cfg), C.byref(q), C.c_uint32(MATCH_KEEP_SCORES if keep_scores else 0), _ptr(res),
+                                   _ptr(vol))
+    if rc:
+        raise GVError(rc, "gv_match_scan_host")
+    return (res[0], vol) if keep_scores else res[0]
+
+
 def control_select_dyn(weights, traj, nav, dyn, cfg, keep_totals=False):
     """control_select with the DYN_SCORE_DTYPE records of a DynConfig as the third critic (cfg None: control_select)"""
     traj = np.ascontiguousarray(traj, TRAJ_SCORE_DTYPE)
@@ -761,6 +839,7 @@ class GridVisionHIP:
         self._motion = None           # the MotionModel in force (set_motion_model)
         self._pending_controls = []   # host controls of rollout_async calls, kept alive until the stream is waited for
         self._nominal_c = 0           # controls per step of the resident MPPI nominal (mppi_set_nominal)
+        self._match_cfg = None        # a copy of the MatchConfig in force (set_match_config): the volume's shape
 
     # ---- plumbing
     def _ck(self, rc, where):
@@ -1150,6 +1229,36 @@ class GridVisionHIP:
                                            C.byref(m) if m is not None else None, C.c_uint32((TRACK_FEED_DYNAMIC if feed else 0) | (TRACK_TICK_DETS if from_tick else 0)),
                                            _ptr(info), _ptr(tracks)), "gv_track_update")
         return info[0], tracks[:int(info[0]["n_tracks"])].copy()
+
+    # ---- [EXTENSION] scan-to-costmap matching
+    def set_match_config(self, cfg):
+        """the MatchConfig of the match_scan() calls that follow; None turns it off"""
+        self._ck(self._lib.gv_set_match_config(self._h, C.byref(cfg) if cfg is not None else None), "gv_set_match_config")
+        self._match_cfg = MatchConfig.from_buffer_copy(cfg) if cfg is not None else None
+
+    def match_scan_async(self, guess, result, scores=None):
+        """enqueue on stream(): guess a MatchGuess or (x, y, yaw), result a MATCH_RESULT_DTYPE array of 1, scores None
+        or a uint32 array of NT * NY * NX (the whole volume is then kept); pinned arrays are written in place by the
+        device; both complete after synchronize()"""
+        q = _guess(guess)
+        assert result.dtype == MATCH_RESULT_DTYPE and result.size >= 1
+        if scores is not None:
+            cfg = getattr(self, "_match_cfg", None)
+            assert scores.dtype == np.uint32 and scores.flags.c_contiguous
+            assert cfg is None or scores.size >= int(np.prod(cfg.shape)), "scores holds NT * NY * NX values"
+        self._ck(self._lib.gv_match_scan_async(self._h, C.byref(q), C.c_uint32(MATCH_KEEP_SCORES if scores is not None else 0),
+                                               _ptr(result), _ptr(scores)), "gv_match_scan_async")
+
+    def match_scan(self, guess, keep_scores=False):
+        """one match, waited for: the MATCH_RESULT_DTYPE record, and with keep_scores also the uint32 (NT, NY, NX)
+        volume of every candidate's score"""
+        q = _guess(guess)
+        res = np.zeros(1, MATCH_RESULT_DTYPE)
+        cfg = getattr(self, "_match_cfg", None)
+        vol = np.zeros(cfg.shape if cfg is not None else (1, 1, 1), np.uint32) if keep_scores else None
+        self._ck(self._lib.gv_match_scan(self._h, C.byref(q), C.c_uint32(MATCH_KEEP_SCORES if keep_scores else 0), _ptr(res),
+                                         _ptr(vol)), "gv_match_scan")
+        return (res[0], vol) if keep_scores else res[0]
 
     # ---- [EXTENSION] goal / path distance field over the resident costmap
     def set_nav_config(self, obstacle_cost=253, cost_weight=0):

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../../include/gridvision_hip.h"
+#include "../../../include/gridvision_hip_match.h"
 
 namespace gv {
 
@@ -408,6 +409,52 @@ public:
     if (objs) *objs = std::move(o);
     return info;
   }
+  // [EXTENSION] X16 scan-to-costmap matching (gridvision_hip_match.h): configure once, then matchScan() correlates the
+  // resident cloud with the costmap of the last inflate() around a guess and returns the best pose; matchMotion() is
+  // that pose as the motion of gridMove() and trackUpdate().  scores, when given, receives the NT * NY * NX volume.
+  void setMatchConfig(const gv_match_config &c)
+  {
+    gv::check(gv_set_match_config(ctx_.handle(), &c), ctx_.handle(), "gv_set_match_config");
+    match_scores_ = (size_t)(2 * c.wt + 1) * (size_t)(2 * c.wy + 1) * (size_t)(2 * c.wx + 1);
+  }
+  void clearMatchConfig()
+  {
+    gv::check(gv_set_match_config(ctx_.handle(), nullptr), ctx_.handle(), "gv_set_match_config");
+    match_scores_ = 0;
+  }
+  gv_match_result matchScan(const gv_match_guess &guess, std::vector<uint32_t> *scores = nullptr)
+  {
+    gv_match_result r{};
+    if (scores) scores->assign(match_scores_ ? match_scores_ : 1, 0u);
+    gv::check(gv_match_scan(ctx_.handle(), &guess, scores ? (uint32_t)GV_MATCH_KEEP_SCORES : 0u, &r, scores ? scores->data() : nullptr),
+              ctx_.handle(), "gv_match_scan");
+    return r;
+  }
+  // result (and scores, NT * NY * NX values, or null) stay the caller's until the context's stream has been waited for
+  void matchScanAsync(const gv_match_guess &guess, gv_match_result *result, uint32_t *scores = nullptr)
+  {
+    gv::check(gv_match_scan_async(ctx_.handle(), &guess, scores ? (uint32_t)GV_MATCH_KEEP_SCORES : 0u, result, scores), ctx_.handle(),
+              "gv_match_scan_async");
+  }
+  static gv_transform matchMotion(const gv_match_result &r)
+  {
+    gv_transform m{};
+    gv::check(gv_match_motion(&r, &m), nullptr, "gv_match_motion");
+    return m;
+  }
+  // the host twin (no handle)
+  static gv_match_result matchScanHost(uint8_t grid_x, uint8_t grid_y, double resolution, const std::vector<uint8_t> &cost,
+                                       const std::vector<float> &x, const std::vector<float> &y, const std::vector<float> &z,
+                                       const gv_transform &base_from_lidar, const gv_height_band *band, const gv_match_config &c,
+                                       const gv_match_guess &guess, std::vector<uint32_t> *scores = nullptr)
+  {
+    gv_match_result r{};
+    if (scores) scores->assign((size_t)(2 * c.wt + 1) * (size_t)(2 * c.wy + 1) * (size_t)(2 * c.wx + 1), 0u);
+    gv::check(gv_match_scan_host(grid_x, grid_y, resolution, cost.data(), x.data(), y.data(), z.data(), x.size(), &base_from_lidar, band,
+                                 &c, &guess, scores ? (uint32_t)GV_MATCH_KEEP_SCORES : 0u, &r, scores ? scores->data() : nullptr),
+              nullptr, "gv_match_scan_host");
+    return r;
+  }
   // the host twins (no handle): the chain over controls[K][P][C] in place, e.g. K = 1 for the command to execute; the
   // control costs; the sequential average with them
   static void mppiConstrain(const gv_mppi_limits &l, const gv_motion_model &m, std::vector<float> &controls, int32_t K, int32_t P)
@@ -450,6 +497,7 @@ private:
   GridVisionContext &ctx_;
   size_t cells_ = 0;
   size_t nominal_floats_ = 0;   // P * C of the nominal given to setMppiNominal
+  size_t match_scores_ = 0;     // NT * NY * NX of the configuration given to setMatchConfig
 };
 
 namespace cloud_detections {

@@ -25,6 +25,9 @@
  *   - grid layers use the reference's storage order: grid_map's column-major
  *     Eigen::MatrixXf(size0,size1) with row = x index, i.e. linear = iy*nx+ix;
  *   - [EXTENSION] marks what north_star asks for and the reference lacks.
+ *
+ * [EXTENSION] X16, scan-to-costmap matching, has a header of its own beside this one, gridvision_hip_match.h, which
+ * includes this one; the library exports its functions as well.
  */
 #ifndef GRIDVISION_HIP_H_
 #define GRIDVISION_HIP_H_
