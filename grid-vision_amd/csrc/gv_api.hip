@@ -471,6 +471,7 @@ int gv_reset(gv_handle h)
   h->layers_in_step = true;   // 0.0 / 0.5 / 50: what the grid pass derives from the prior
   h->infl.have_cost = h->infl.have_dist2 = false;   // the costmap was a snapshot of the grid that is gone
   h->nav.have_field = false;                        // ... and so was the distance field over it
+  h->path.have = false;                             // ... and the paths walked down that field
   return GV_OK;
   GV_CATCH
 }

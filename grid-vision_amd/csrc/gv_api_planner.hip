@@ -191,6 +191,87 @@ int enqueue_control_scores(gv_context *h, const gv_critic_weights &w, gv_control
   return GV_OK;
 }
 
+// What gv_nav_field and gv_nav_field_from_path do alike before their seeds: the refusals, the buffers (room for
+// `seed_room` host seeds in the staging block), the kernel arguments of this grid, costmap and configuration, and the
+// flags and the seed counter zeroed on the public stream.  The field counts as absent until nav_field_relax has converged.
+int nav_field_begin(gv_context *h, const char *call, size_t seed_room, NavArgs &a)
+{
+  gv_context::NavField &f = h->nav;
+  int rc = refuse_state(h, call, f.set ? nullptr : "no configuration set (gv_set_nav_config)", kNeedCostmap,
+                        "there is no whole costmap");
+  if (rc || (rc = set_device_only(h))) return rc;
+  constexpr int kBatchMax = gv_context::NavField::kBatchMax;
+  static_assert((1 + kBatchMax) * sizeof(uint32_t) <= kNavSeedOff, "the counters fit in front of the seeds");
+  const int32_t G = h->g.G;
+  const int32_t tiles_x = (h->g.nx + kNavTile - 1) / kNavTile, tiles_y = (h->g.ny + kNavTile - 1) / kNavTile;
+  const size_t n_tiles = (size_t)tiles_x * (size_t)tiles_y;
+  if ((rc = f.field.reserve(h, ((size_t)G + 3) / 4 * 4))) return rc;
+  if ((rc = f.flags.reserve(h, 2 * n_tiles))) return rc;
+  if ((rc = f.counters.reserve(h, 1 + kBatchMax))) return rc;
+  if (seed_room && (rc = f.d_seeds.reserve(h, seed_room))) return rc;
+  if ((rc = f.stage.reserve(h, kNavSeedOff + seed_room * sizeof(int32_t), hipHostMallocDefault))) return rc;
+  if (!f.done) GV_HIP(f.done.create(hipEventDisableTiming));
+  f.have_field = false;   // until this call has converged
+
+  a = NavArgs{};
+  a.nx = h->g.nx; a.ny = h->g.ny; a.G = G;
+  a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+  a.step = NavStep{f.cfg.obstacle_cost, f.cfg.cost_weight};
+  a.pass_cap = h->tune.nav_pass_cap;
+  a.cost = h->infl.cost;
+  a.field = f.field;
+  a.flags_out = f.flags;          // round 0 reads the first half
+  a.counter = f.counters;         // [0]: seeds used
+  GV_HIP(hipMemsetAsync(f.flags, 0, 2 * n_tiles * sizeof(uint32_t), h->stream));
+  GV_HIP(hipMemsetAsync(f.counters, 0, sizeof(uint32_t), h->stream));
+  return GV_OK;
+}
+
+// The relaxation behind the seeds: rounds in batches of 4, 8, .. kBatchMax launches; a batch ends with its counters
+// copied into the pinned block and one event wait, and the loop stops after the first round whose counter is 0 (the
+// rounds behind it in the batch found no active tile and did nothing).
+int nav_field_relax(gv_context *h, const char *call, NavArgs &a, gv_nav_info *info)
+{
+  gv_context::NavField &f = h->nav;
+  constexpr int kBatchMax = gv_context::NavField::kBatchMax;
+  const size_t n_tiles = (size_t)a.tiles_x * (size_t)a.tiles_y;
+  const volatile uint32_t *landed = reinterpret_cast<const volatile uint32_t *>(f.stage.get());
+  const int64_t max_rounds = (int64_t)a.G + 2;
+  int64_t rounds = 0;
+  int batch = 4;
+  for (bool converged = false; !converged;) {
+    if (rounds >= max_rounds) return state_error(h, call, "no convergence within G + 2 rounds");
+    const int nb = (int)std::min<int64_t>(batch, max_rounds - rounds);
+    GV_HIP(hipMemsetAsync(f.counters.get() + 1, 0, (size_t)nb * sizeof(uint32_t), h->stream));
+    for (int i = 0; i < nb; ++i) {
+      const int64_t r = rounds + i;
+      a.flags_in = f.flags.get() + (size_t)(r & 1) * n_tiles;
+      a.flags_out = f.flags.get() + (size_t)((r + 1) & 1) * n_tiles;
+      a.counter = f.counters.get() + 1 + i;
+      launch_nav_relax(a, h->stream);
+    }
+    GV_HIP(hipGetLastError());
+    GV_HIP(hipMemcpyAsync(f.stage.get(), f.counters, (size_t)(1 + nb) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    GV_HIP(hipEventRecord(f.done, h->stream));
+    GV_HIP(hipEventSynchronize(f.done));
+    int used = nb;
+    for (int i = 0; i < nb; ++i)
+      if (landed[1 + i] == 0u) {
+        used = i + 1;
+        converged = true;
+        break;
+      }
+    rounds += used;
+    batch = std::min(batch * 2, kBatchMax);
+  }
+  f.have_field = true;
+  if (info) {
+    info->n_seeds_used = (int32_t)landed[0];
+    info->rounds = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+  }
+  return GV_OK;
+}
+
 }  // namespace gv_internal
 
 extern "C" {
@@ -324,92 +405,28 @@ int gv_set_nav_config(gv_handle h, const gv_nav_config *cfg)
 
 // Everything goes on the public stream, behind what was enqueued before (a pending tick's grid pass and inflate
 // included).  Seeds become field entries here on the host (the exact getIndex); whether a seed's cell is blocked only
-// the device knows, so k_nav_seeds drops those and counts the rest.  Then rounds in batches of 4, 8, .. kBatchMax
-// launches; a batch ends with its counters copied into the pinned block and one event wait, and the loop stops after
-// the first round whose counter is 0 (the rounds behind it in the batch found no active tile and did nothing).
+// the device knows, so k_nav_seeds drops those and counts the rest.  Then the rounds (nav_field_relax).
 int gv_nav_field(gv_handle h, const float *seeds_xy, int32_t S, gv_nav_info *info)
 {
   if (!h) return GV_ERR_BAD_ARG;
   GV_TRY
   if (!seeds_xy || S < 1 || S > 65536) return GV_ERR_BAD_ARG;
   gv_context::NavField &f = h->nav;
-  int rc = refuse_state(h, "gv_nav_field", f.set ? nullptr : "no configuration set (gv_set_nav_config)", kNeedCostmap,
-                        "there is no whole costmap");
-  if (rc || (rc = set_device_only(h))) return rc;
-  constexpr int kBatchMax = gv_context::NavField::kBatchMax;
-  constexpr size_t kSeedOff = 512;   // bytes of the pinned block in front of the seeds: the counters land there
-  static_assert((1 + kBatchMax) * sizeof(uint32_t) <= kSeedOff, "the counters fit in front of the seeds");
-  const int32_t G = h->g.G;
-  const int32_t tiles_x = (h->g.nx + kNavTile - 1) / kNavTile, tiles_y = (h->g.ny + kNavTile - 1) / kNavTile;
-  const size_t n_tiles = (size_t)tiles_x * (size_t)tiles_y;
-  if ((rc = f.field.reserve(h, ((size_t)G + 3) / 4 * 4))) return rc;
-  if ((rc = f.flags.reserve(h, 2 * n_tiles))) return rc;
-  if ((rc = f.counters.reserve(h, 1 + kBatchMax))) return rc;
-  if ((rc = f.d_seeds.reserve(h, (size_t)S))) return rc;
-  if ((rc = f.stage.reserve(h, kSeedOff + (size_t)S * sizeof(int32_t), hipHostMallocDefault))) return rc;
-  if (!f.done) GV_HIP(f.done.create(hipEventDisableTiming));
-  f.have_field = false;   // until this call has converged
-
-  int32_t *cells = reinterpret_cast<int32_t *>(f.stage.get() + kSeedOff);
+  NavArgs a{};
+  if (int rc = nav_field_begin(h, "gv_nav_field", (size_t)S, a)) return rc;
+  int32_t *cells = reinterpret_cast<int32_t *>(f.stage.get() + kNavSeedOff);
   int32_t n = 0;
   for (int32_t i = 0; i < S; ++i) {
     const int32_t e = host::nav_seed_entry(h->g, seeds_xy[2 * i], seeds_xy[2 * i + 1]);
     if (e >= 0) cells[n++] = e;
   }
-  const volatile uint32_t *landed = reinterpret_cast<const volatile uint32_t *>(f.stage.get());
-
-  NavArgs a{};
-  a.nx = h->g.nx; a.ny = h->g.ny; a.G = G;
-  a.tiles_x = tiles_x; a.tiles_y = tiles_y;
-  a.step = NavStep{f.cfg.obstacle_cost, f.cfg.cost_weight};
-  a.pass_cap = h->tune.nav_pass_cap;
-  a.cost = h->infl.cost;
-  a.field = f.field;
   a.seeds = f.d_seeds;
   a.n_seeds = n;
-  a.flags_out = f.flags;          // round 0 reads the first half
-  a.counter = f.counters;         // [0]: seeds used
-  GV_HIP(hipMemsetAsync(f.flags, 0, 2 * n_tiles * sizeof(uint32_t), h->stream));
-  GV_HIP(hipMemsetAsync(f.counters, 0, sizeof(uint32_t), h->stream));
   if (n > 0) GV_HIP(hipMemcpyAsync(f.d_seeds, cells, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   launch_nav_init(a, h->stream);
   launch_nav_seeds(a, h->stream);
   GV_HIP(hipGetLastError());
-
-  const int64_t max_rounds = (int64_t)G + 2;
-  int64_t rounds = 0;
-  int batch = 4;
-  for (bool converged = false; !converged;) {
-    if (rounds >= max_rounds) return state_error(h, "gv_nav_field", "no convergence within G + 2 rounds");
-    const int nb = (int)std::min<int64_t>(batch, max_rounds - rounds);
-    GV_HIP(hipMemsetAsync(f.counters.get() + 1, 0, (size_t)nb * sizeof(uint32_t), h->stream));
-    for (int i = 0; i < nb; ++i) {
-      const int64_t r = rounds + i;
-      a.flags_in = f.flags.get() + (size_t)(r & 1) * n_tiles;
-      a.flags_out = f.flags.get() + (size_t)((r + 1) & 1) * n_tiles;
-      a.counter = f.counters.get() + 1 + i;
-      launch_nav_relax(a, h->stream);
-    }
-    GV_HIP(hipGetLastError());
-    GV_HIP(hipMemcpyAsync(f.stage.get(), f.counters, (size_t)(1 + nb) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    GV_HIP(hipEventRecord(f.done, h->stream));
-    GV_HIP(hipEventSynchronize(f.done));
-    int used = nb;
-    for (int i = 0; i < nb; ++i)
-      if (landed[1 + i] == 0u) {
-        used = i + 1;
-        converged = true;
-        break;
-      }
-    rounds += used;
-    batch = std::min(batch * 2, kBatchMax);
-  }
-  f.have_field = true;
-  if (info) {
-    info->n_seeds_used = (int32_t)landed[0];
-    info->rounds = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
-  }
-  return GV_OK;
+  return nav_field_relax(h, "gv_nav_field", a, info);
   GV_CATCH
 }
 

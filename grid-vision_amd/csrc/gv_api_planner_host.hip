@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "gv_mppi.hpp"
+#include "gv_navpath.hpp"
 #include "gv_planner_rules.hpp"
 
 using namespace gv;
@@ -59,6 +60,50 @@ int gv_nav_step_table(const gv_nav_config *cfg, uint32_t table[256])
 {
   if (!cfg || !table || !host::nav_config_valid(*cfg)) return GV_ERR_BAD_ARG;
   host::nav_step_table(*cfg, table);
+  return GV_OK;
+}
+
+// ---- X17: path_next (gv_navpath.hpp) over a plain array, one start after the other, one step after the other
+int gv_nav_path_host(uint8_t grid_x, uint8_t grid_y, double resolution, const uint32_t *field, const float *starts_xy, int32_t S,
+                     int32_t cap, uint32_t flags, gv_nav_path_info *info, int32_t *entries, float *paths_xy)
+{
+  if (!field || !starts_xy || !info || !path_call_ok(S, cap, flags)) return GV_ERR_BAD_ARG;
+  GridParams g{};
+  if (!host::grid_params(grid_x, grid_y, resolution, g)) return GV_ERR_BAD_ARG;
+  const int32_t nx = g.nx;
+  const int32_t ny = g.ny;
+  const auto at = [field, nx, ny](int32_t x, int32_t y) {   // any array of G values; path_next also asks one cell off the map
+    return x >= 0 && x < nx && y >= 0 && y < ny ? field[(size_t)y * (size_t)nx + (size_t)x] : GV_NAV_BLOCKED;
+  };
+  const bool diagonal = (flags & GV_PATH_DIAGONAL) != 0u;
+  for (int32_t s = 0; s < S; ++s) {
+    const int32_t e0 = host::nav_seed_entry(g, starts_xy[2 * s], starts_xy[2 * s + 1]);
+    uint32_t v = e0 >= 0 ? field[e0] : GV_NAV_BLOCKED;
+    gv_nav_path_info rec = path_record_begin(e0, v);
+    if (rec.status == GV_PATH_REACHED) {   // a start that walks
+      int32_t y = e0 / nx, x = e0 - y * nx;
+      const size_t first = (size_t)s * (size_t)cap;
+      int32_t n = 0, n_diag = 0;
+      for (;;) {
+        if (entries) entries[first + (size_t)n] = y * nx + x;
+        if (paths_xy) {
+          paths_xy[2 * (first + (size_t)n)] = path_centre(g.pos_x, g.off_x, g.res, g.nx, x);
+          paths_xy[2 * (first + (size_t)n) + 1] = path_centre(g.pos_y, g.off_y, g.res, g.ny, y);
+        }
+        ++n;
+        if (v == 0u) break;                                   // rec.status is GV_PATH_REACHED
+        if (n == cap) { rec.status = GV_PATH_TRUNCATED; break; }
+        bool diag = false;
+        if (!path_next(at, nx, g.ny, diagonal, x, y, v, diag)) { rec.status = GV_PATH_STUCK; break; }
+        n_diag += diag ? 1 : 0;
+      }
+      rec.n_cells = n;
+      rec.end_value = v;
+      rec.end_entry = y * nx + x;
+      rec.n_diagonal = n_diag;
+    }
+    info[s] = rec;
+  }
   return GV_OK;
 }
 

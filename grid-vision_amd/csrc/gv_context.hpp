@@ -379,6 +379,21 @@ struct __attribute__((visibility("hidden"))) gv_context {
     Event done;                             // public stream: a batch's counters have landed
     DevBuf<gv_nav_score> d_scores;          // the sampler: the landing place of records bound for pageable memory
   } nav;
+  // [EXTENSION] X17 paths walked down that field (gv_nav_path* / gv_nav_field_from_path, gv_api_path.hip).  The resident
+  // paths of the last call -- entries[S][cap], xy[S][cap][2] and the S records -- are in buffers of their own, made by
+  // the first call and grown by a larger one, so a later gv_nav_field or gv_nav_field_from_path leaves them alone;
+  // gv_reset invalidates them with the field.  The start cells go to `d_starts` through `up`'s staging slots.  All of
+  // it is used on the public stream only: a call's copy and kernel run behind those of the call before it, and the
+  // buffers double as the landing places of results bound for pageable memory.
+  struct NavPath {
+    DevBuf<int32_t> entries;
+    DevBuf<float> xy;
+    DevBuf<gv_nav_path_info> info;
+    DevBuf<int32_t> d_starts;
+    StageSlots up;
+    int32_t S = 0, cap = 0;                 // of the resident paths
+    bool have = false;                      // a path call since gv_create / gv_reset
+  } path;
   // [EXTENSION] X10 rollout and control step (gv_set_motion_model / gv_rollout* / gv_control_step*).  The motion model is
   // handle configuration, copied into the kernel arguments of every rollout at enqueue.  `poses` is the resident
   // rollout, a buffer of its own (d_poses below is the staging copy of host poses, which every scoring call
@@ -650,6 +665,9 @@ int stage_upload(gv_context *h, gv_context::StageSlots &s, const void *src, size
 int upload_slot(gv_context *h, gv_context::UploadSlots &u, const void *src, size_t bytes, size_t cap);
 int wait_scored(gv_context *h, int rc, int32_t K);
 int enqueue_control_scores(gv_context *h, const gv_critic_weights &w, gv_control_result *result, uint64_t *totals);
+constexpr size_t kNavSeedOff = 512;   // bytes of NavField::stage in front of the seeds: the counters land there
+int nav_field_begin(gv_context *h, const char *call, size_t seed_room, NavArgs &a);
+int nav_field_relax(gv_context *h, const char *call, NavArgs &a, gv_nav_info *info);
 
 // Where a kernel writes n results bound for `dst`: dst's own device view when it is pinned host memory aligned to
 // `align` bytes, else `landing`, which copy_back empties into dst on the public stream behind the kernel.

@@ -8,6 +8,7 @@
 #include "gv_dyn.hpp"
 #include "gv_track.hpp"
 #include "gv_match.hpp"
+#include "gv_navpath.hpp"
 #include "gv_pose_math.hpp"
 
 namespace gv {
@@ -170,6 +171,23 @@ struct NavScoreArgs {
   gv_nav_score *scores;         // K records (device memory, or the device view of pinned host memory; 8-byte aligned)
 };
 void launch_score_nav(const NavScoreArgs &a, hipStream_t s);
+// [EXTENSION] X17 path extraction from that field (gv_navpath.hip; the arithmetic is gv_navpath.hpp's): a wavefront
+// per start walks the field downhill and leaves entries[S][cap], xy[S][cap][2] and S records in the handle's buffers.
+struct PathArgs {
+  GridParams g;
+  const uint32_t *field;        // G
+  const int32_t *starts;        // S data-order entries, -1: off the map (device)
+  int32_t S, cap;
+  uint32_t diagonal;            // GV_PATH_DIAGONAL of the call
+  int32_t *entries;             // S * cap (resident)
+  float *xy;                    // S * cap * 2 (resident)
+  gv_nav_path_info *info;       // S (resident)
+  float *xy_out;                // the device view of a pinned paths_xy, or null: written as well
+  gv_nav_path_info *info_out;   // the device view of a pinned info, or null: written as well
+};
+void launch_nav_path(const PathArgs &a, hipStream_t s);
+// the seeds of gv_nav_field_from_path: launch_nav_seeds with the cells of a resident path, n_cells read from its record
+void launch_nav_seeds_path(const NavArgs &a, const gv_nav_path_info *rec, int32_t cap, hipStream_t s);
 // [EXTENSION] X10 rollout and control step (gv_rollout.hip; the arithmetic is gv_motion.hpp's).  The motion model, the
 // start and the weights travel by value: a call already enqueued keeps what it was enqueued with.
 struct RolloutArgs {

@@ -83,6 +83,20 @@ assert MATCH_RESULT_DTYPE.itemsize == 64
 MATCH_SYMBOLS = ["gv_set_match_config", "gv_match_scan_async", "gv_match_scan", "gv_match_scan_host", "gv_match_rotations",
                  "gv_match_motion"]
 
+# [EXTENSION] X17 path extraction from the distance field (include/gridvision_hip_path.h)
+PATH_DIAGONAL = 1 << 0       # a call's flags
+PATH_REACHED, PATH_TRUNCATED, PATH_OFF_MAP, PATH_BLOCKED, PATH_UNREACHABLE, PATH_STUCK = range(6)   # gv_nav_path_info.status
+PATH_MAX_STARTS = 256
+PATH_MAX_CAP = 65536
+PATH_MAX_CELLS = 1 << 20     # S * cap
+NAV_PATH_INFO_DTYPE = np.dtype([("status", np.int32), ("n_cells", np.int32), ("start_value", np.uint32), ("end_value", np.uint32),
+                                ("start_entry", np.int32), ("end_entry", np.int32), ("n_diagonal", np.int32),
+                                ("reserved", np.uint32)])   # gv_nav_path_info
+assert NAV_PATH_INFO_DTYPE.itemsize == 32
+# every symbol include/gridvision_hip_path.h declares
+PATH_SYMBOLS = ["gv_nav_path_async", "gv_nav_path", "gv_nav_path_host", "gv_get_nav_path", "gv_device_nav_path",
+                "gv_nav_field_from_path"]
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -696,6 +710,30 @@ def match_scan_host(grid_x, grid_y, resolution, cost, x, y, z, base_lidar, cfg, 
     return (res[0], vol) if keep_scores else res[0]
 
 
+def _starts(starts):
+    s = _f32(starts).reshape(-1, 2)
+    assert len(s) >= 1, "starts is (S, 2)"
+    return s
+
+
+def nav_path_host(grid_x, grid_y, resolution, field, starts, cap, flags=0, keep_xy=True):
+    """gv_nav_path_host, the library's host twin of nav_path (needs no GPU): field ANY uint32 array of G values in data
+    order, starts (S, 2) float32 in the grid's frame.  Returns (info NAV_PATH_INFO_DTYPE (S,), entries int32 (S, cap),
+    xy float32 (S, cap, 2) or None); slots past n_cells are zero."""
+    field = np.ascontiguousarray(field, np.uint32).reshape(-1)
+    s = _starts(starts)
+    S, cap = len(s), int(cap)
+    room = max(S * cap, 1) if 1 <= cap <= PATH_MAX_CAP and S * cap <= PATH_MAX_CELLS else 1
+    info = np.zeros(S, NAV_PATH_INFO_DTYPE)
+    entries = np.zeros(room, np.int32)
+    xy = np.zeros(2 * room, np.float32) if keep_xy else None
+    rc = load().gv_nav_path_host(C.c_uint8(grid_x), C.c_uint8(grid_y), C.c_double(resolution), _ptr(field), _ptr(s), C.c_int32(S),
+                                 C.c_int32(cap), C.c_uint32(flags), _ptr(info), _ptr(entries), _ptr(xy))
+    if rc:
+        raise GVError(rc, "gv_nav_path_host")
+    return info, entries.reshape(S, cap), xy.reshape(S, cap, 2) if keep_xy else None
+
+
 def control_select_dyn(weights, traj, nav, dyn, cfg, keep_totals=False):
     """control_select with the DYN_SCORE_DTYPE records of a DynConfig as the third critic (cfg None: control_select)"""
     traj = np.ascontiguousarray(traj, TRAJ_SCORE_DTYPE)
@@ -1305,6 +1343,52 @@ class GridVisionHIP:
         self._ck(self._lib.gv_score_nav(self._h, src, C.c_int32(K), C.c_int32(P), C.c_uint32(flags), _ptr(scores)),
                  "gv_score_nav")
         return scores
+
+    # ---- [EXTENSION] paths down the distance field
+    def nav_path_async(self, starts, cap, info, paths_xy=None, flags=0):
+        """enqueue on stream(): starts (S, 2) float32 (copied before the call returns), info a NAV_PATH_INFO_DTYPE array
+        of S, paths_xy None (the paths stay resident only) or a float32 array of S * cap * 2; pinned arrays are written
+        in place by the device; both complete after synchronize()"""
+        s = _starts(starts)
+        assert info.dtype == NAV_PATH_INFO_DTYPE and info.size >= len(s)
+        assert paths_xy is None or (paths_xy.dtype == np.float32 and paths_xy.size >= len(s) * int(cap) * 2)
+        self._ck(self._lib.gv_nav_path_async(self._h, _ptr(s), C.c_int32(len(s)), C.c_int32(cap), C.c_uint32(flags), _ptr(info),
+                                             _ptr(paths_xy)), "gv_nav_path_async")
+
+    def nav_path(self, starts, cap, flags=0, keep_xy=True):
+        """walk the field of the last nav_field() downhill from starts (S, 2) float32, at most cap cells each, waited
+        for.  Returns (info NAV_PATH_INFO_DTYPE (S,), xy float32 (S, cap, 2) or None with keep_xy=False: the paths
+        then stay resident only, for nav_path_get and nav_field_from_path)."""
+        s = _starts(starts)
+        info = np.zeros(len(s), NAV_PATH_INFO_DTYPE)
+        ok = 1 <= int(cap) <= PATH_MAX_CAP and len(s) * int(cap) <= PATH_MAX_CELLS
+        xy = np.zeros((len(s), int(cap), 2) if ok else (1,), np.float32) if keep_xy else None
+        self._ck(self._lib.gv_nav_path(self._h, _ptr(s), C.c_int32(len(s)), C.c_int32(cap), C.c_uint32(flags), _ptr(info),
+                                       _ptr(xy)), "gv_nav_path")
+        return info, xy
+
+    def device_nav_path(self):
+        """dict(entries, xy, info: device addresses; S, cap) of the resident paths (read-only)"""
+        e, x, i, S, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        self._ck(self._lib.gv_device_nav_path(self._h, C.byref(e), C.byref(x), C.byref(i), C.byref(S), C.byref(cap)),
+                 "gv_device_nav_path")
+        return dict(entries=e.value, xy=x.value, info=i.value, S=S.value, cap=cap.value)
+
+    def nav_path_get(self, s, cap_out=None):
+        """resident path s read back: (info record, entries int32 (n,), xy float32 (n, 2)), n = min(n_cells, cap_out)"""
+        cap_out = self.device_nav_path()["cap"] if cap_out is None else int(cap_out)
+        info = np.zeros(1, NAV_PATH_INFO_DTYPE)
+        entries, xy = np.zeros(max(cap_out, 1), np.int32), np.zeros((max(cap_out, 1), 2), np.float32)
+        self._ck(self._lib.gv_get_nav_path(self._h, C.c_int32(s), _ptr(entries), _ptr(xy), C.c_int32(cap_out), _ptr(info)),
+                 "gv_get_nav_path")
+        n = min(int(info[0]["n_cells"]), cap_out)
+        return info[0], entries[:n].copy(), xy[:n].copy()
+
+    def nav_field_from_path(self, s):
+        """nav_field() seeded by every cell of resident path s, on the device.  Returns dict(n_seeds_used, rounds)."""
+        info = NavInfo()
+        self._ck(self._lib.gv_nav_field_from_path(self._h, C.c_int32(s), C.byref(info)), "gv_nav_field_from_path")
+        return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
 
     # ---- [EXTENSION] rollout and control step over the resident rollout
     def set_motion_model(self, model, dt=None):

@@ -1258,4 +1258,5 @@ int gv_comm_band(gv_handle h, int64_t *begin, int64_t *end);
 #ifdef __cplusplus
 }
 #endif
+#include "gridvision_hip_path.h"
 #endif /* GRIDVISION_HIP_H_ */
