@@ -492,6 +492,24 @@ struct __attribute__((visibility("hidden"))) gv_context {
     Event read;
     uint32_t clouds = 0;
   } match;
+  // [EXTENSION] X18 wide-window matching by branch and bound (gv_set_search_config / gv_match_search*,
+  // gv_api_search.hip).  The configuration is handle state, independent of Match's, and travels in the kernel arguments.
+  // The buffers are the scratch of one call, made by the first call that needs them, grown by a larger one and used on
+  // the public stream only: `pts` and `head` as Match's (head: the counters, the pre-slots, the bounds), `rows` and
+  // `pool` the costmap pooled along x and then along y (pooled per call: a call reads the costmap of the inflate before
+  // it), `list` the survivors and `slots` their exact scores, n_blocks * S * S words at the worst.  d_result and d_stats
+  // follow TrajScore's rules; d_stats also takes the stats nobody asked for.  The cloud's readers are marked in
+  // Match::read and Match::clouds: one event and one mask for both matchers.  gv_reset keeps all of it.
+  struct Search {
+    bool set = false;
+    gv_search_config cfg{};
+    DevBuf<float2> pts;
+    DevBuf<uint32_t> head;
+    DevBuf<uint8_t> rows, pool;
+    DevBuf<uint32_t> list, slots;
+    DevBuf<gv_match_result> d_result;
+    DevBuf<gv_search_stats> d_stats;
+  } search;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
   // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in

@@ -9,6 +9,7 @@
 #include "gv_track.hpp"
 #include "gv_match.hpp"
 #include "gv_navpath.hpp"
+#include "gv_search.hpp"
 #include "gv_pose_math.hpp"
 
 namespace gv {
@@ -336,6 +337,43 @@ struct MatchArgs {
 void launch_match_points(const MatchArgs &a, hipStream_t s);
 void launch_match_score(const MatchArgs &a, hipStream_t s);
 void launch_match_select(const MatchArgs &a, hipStream_t s);
+// [EXTENSION] X18 wide-window matching by branch and bound (gv_search.hip; the arithmetic is gv_search.hpp's and
+// gv_match.hpp's).  The point pass is X16's, given a MatchArgs over this call's `head` and `pts`.  `head` is one zeroed
+// block per call: the counters below, the two pre-slots (the seed block's exact scores, then the centre block's), then
+// the bounds B[n_blocks].
+enum : int32_t {
+  kSearchUsed = 0,        // n_used (the point pass counts here)
+  kSearchSurvivors = 1,   // n_survivors
+  kSearchScored = 2,      // n_scored
+  kSearchLower = 3,       // L
+  kSearchSeedKey = 4,     // uint64: the largest search_seed_key
+  kSearchBoundSum = 6,    // uint64
+  kSearchBestKey = 8,     // uint64: the largest match_key over the survivors' candidates
+  kSearchPre = 16,        // 2 * kSearchMaxS2 words
+  kSearchBounds = kSearchPre + 2 * kSearchMaxS2,
+};
+struct SearchArgs {
+  GridParams g;
+  SearchParams sp;
+  uint32_t n_sel;               // ceil(n / stride): the bound on the used points
+  uint32_t n_blocks;
+  const float2 *pts;            // the used points' (bx, by) (device)
+  uint32_t *head;               // kSearchBounds + n_blocks words (device), zero when the point pass starts
+  const uint8_t *cost;          // the resident costmap
+  uint8_t *rows;                // ny rows of nx + S - 1: the costmap pooled along x
+  uint8_t *pool;                // M: (ny + S - 1) rows of nx + S - 1 (search_pool_at)
+  uint32_t *list;               // n_blocks words: the survivors' block indices, in any order
+  uint32_t *slots;              // n_blocks * S * S words: slot k holds the exact scores of list[k]'s block
+  gv_match_result *result;      // one record (device memory, or the device view of pinned host memory)
+  gv_search_stats *stats;       // likewise
+  float rot[2 * kMatchMaxSide]; // (c_t, s_t), NT pairs
+};
+void launch_search_pool(const SearchArgs &a, hipStream_t s);
+void launch_search_bound(const SearchArgs &a, hipStream_t s);
+void launch_search_seed(const SearchArgs &a, hipStream_t s);
+void launch_search_fine(const SearchArgs &a, bool pre, hipStream_t s);   // pre: the seed's and the centre's block
+void launch_search_prune(const SearchArgs &a, hipStream_t s);
+void launch_search_select(const SearchArgs &a, hipStream_t s);
 // bytes (a multiple of 16) from device memory to pinned, device-visible host memory by `blocks` workgroups
 void launch_publish_grid(const int8_t *src, int8_t *dst_host, size_t bytes, int blocks, hipStream_t s);
 void launch_hold(unsigned long long ticks_100mhz, hipStream_t s);   // one idle wavefront for that long (queue probe)

@@ -97,6 +97,16 @@ assert NAV_PATH_INFO_DTYPE.itemsize == 32
 PATH_SYMBOLS = ["gv_nav_path_async", "gv_nav_path", "gv_nav_path_host", "gv_get_nav_path", "gv_device_nav_path",
                 "gv_nav_field_from_path"]
 
+# [EXTENSION] X18 wide-window matching by branch and bound (include/gridvision_hip_search.h)
+SEARCH_USE_BAND = 1 << 0     # SearchConfig.flags
+SEARCH_MAX_HALF = 128
+SEARCH_STATS_DTYPE = np.dtype([("n_blocks", np.uint32), ("n_survivors", np.uint32), ("n_scored", np.uint32),
+                               ("seed_block", np.uint32), ("lower_score", np.uint32), ("bound_max", np.uint32),
+                               ("bound_sum", np.uint64)])   # gv_search_stats
+assert SEARCH_STATS_DTYPE.itemsize == 32
+# every symbol include/gridvision_hip_search.h declares
+SEARCH_SYMBOLS = ["gv_set_search_config", "gv_match_search_async", "gv_match_search", "gv_match_search_host"]
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -300,6 +310,23 @@ class MatchConfig(C.Structure):
     @property
     def shape(self):
         """(NT, NY, NX) of the score volume"""
+        return 2 * self.wt + 1, 2 * self.wy + 1, 2 * self.wx + 1
+
+
+class SearchConfig(C.Structure):
+    """gv_search_config: MatchConfig's fields with half-widths up to SEARCH_MAX_HALF, and block_log2 (blocks of S x S
+    shifts, S = 1 << block_log2, 1..4)"""
+    _fields_ = [("wx", C.c_int32), ("wy", C.c_int32), ("wt", C.c_int32), ("stride", C.c_int32), ("yaw_step", C.c_double),
+                ("min_points", C.c_int32), ("flags", C.c_uint32), ("block_log2", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def of(cls, wx=64, wy=64, wt=4, yaw_step=0.01, stride=1, min_points=1, use_band=False, flags=0, block_log2=3, reserved=0):
+        return cls(int(wx), int(wy), int(wt), int(stride), float(yaw_step), int(min_points),
+                   int(flags) | (SEARCH_USE_BAND if use_band else 0), int(block_log2), int(reserved))
+
+    @property
+    def shape(self):
+        """(NT, NY, NX) of the window"""
         return 2 * self.wt + 1, 2 * self.wy + 1, 2 * self.wx + 1
 
 
@@ -708,6 +735,22 @@ def match_scan_host(grid_x, grid_y, resolution, cost, x, y, z, base_lidar, cfg, 
     if rc:
         raise GVError(rc, "gv_match_scan_host")
     return (res[0], vol) if keep_scores else res[0]
+
+
+def match_search_host(grid_x, grid_y, resolution, cost, x, y, z, base_lidar, cfg, guess, band=None):
+    """gv_match_search_host, the library's host twin of match_search (needs no GPU), with match_scan_host's arguments and
+    a SearchConfig.  Returns (the MATCH_RESULT_DTYPE record, the SEARCH_STATS_DTYPE record)."""
+    cost = np.ascontiguousarray(cost, np.uint8).reshape(-1)
+    x, y, z = _f32(x), _f32(y), _f32(z)
+    tf, q = make_tf(base_lidar), _guess(guess)
+    hb = HeightBand(float(band[0]), float(band[1]), 0) if band is not None else None
+    res, stats = np.zeros(1, MATCH_RESULT_DTYPE), np.zeros(1, SEARCH_STATS_DTYPE)
+    rc = load().gv_match_search_host(C.c_uint8(grid_x), C.c_uint8(grid_y), C.c_double(resolution), _ptr(cost), _ptr(x), _ptr(y),
+                                     _ptr(z), C.c_size_t(len(x)), C.byref(tf), C.byref(hb) if hb is not None else None,
+                                     C.byref(cfg), C.byref(q), C.c_uint32(0), _ptr(res), _ptr(stats))
+    if rc:
+        raise GVError(rc, "gv_match_search_host")
+    return res[0], stats[0]
 
 
 def _starts(starts):
@@ -1297,6 +1340,29 @@ class GridVisionHIP:
         self._ck(self._lib.gv_match_scan(self._h, C.byref(q), C.c_uint32(MATCH_KEEP_SCORES if keep_scores else 0), _ptr(res),
                                          _ptr(vol)), "gv_match_scan")
         return (res[0], vol) if keep_scores else res[0]
+
+    # ---- [EXTENSION] wide-window matching by branch and bound
+    def set_search_config(self, cfg):
+        """the SearchConfig of the match_search() calls that follow; None turns it off"""
+        self._ck(self._lib.gv_set_search_config(self._h, C.byref(cfg) if cfg is not None else None), "gv_set_search_config")
+
+    def match_search_async(self, guess, result, stats=None):
+        """enqueue on stream(): guess a MatchGuess or (x, y, yaw), result a MATCH_RESULT_DTYPE array of 1, stats None or
+        a SEARCH_STATS_DTYPE array of 1; pinned arrays are written in place by the device; both complete after
+        synchronize()"""
+        q = _guess(guess)
+        assert result.dtype == MATCH_RESULT_DTYPE and result.size >= 1
+        assert stats is None or (stats.dtype == SEARCH_STATS_DTYPE and stats.size >= 1)
+        self._ck(self._lib.gv_match_search_async(self._h, C.byref(q), C.c_uint32(0), _ptr(result), _ptr(stats)),
+                 "gv_match_search_async")
+
+    def match_search(self, guess, keep_stats=True):
+        """one search, waited for: (the MATCH_RESULT_DTYPE record, the SEARCH_STATS_DTYPE record), or the record alone"""
+        q = _guess(guess)
+        res = np.zeros(1, MATCH_RESULT_DTYPE)
+        stats = np.zeros(1, SEARCH_STATS_DTYPE) if keep_stats else None
+        self._ck(self._lib.gv_match_search(self._h, C.byref(q), C.c_uint32(0), _ptr(res), _ptr(stats)), "gv_match_search")
+        return (res[0], stats[0]) if keep_stats else res[0]
 
     # ---- [EXTENSION] goal / path distance field over the resident costmap
     def set_nav_config(self, obstacle_cost=253, cost_weight=0):
