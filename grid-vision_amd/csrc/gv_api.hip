@@ -882,6 +882,34 @@ int gv_get_miss(gv_handle h, int32_t *out)
   return copy_out(h, out, h->scratch_i32, (size_t)h->g.G * sizeof(int32_t));
 }
 
+// test hook (gv_test_hooks.h): the four end bitmaps of the last frame's buffer set as the tile pass left them, copied out
+int gv_test_end_bitmaps(gv_handle h, uint32_t *hitN, uint32_t *clipN, uint32_t *hitT, uint32_t *clipT, int32_t *nxw,
+                        int32_t *nyw, int32_t *nx_pad, int32_t *ny_pad)
+{
+  if (!h) return GV_ERR_BAD_ARG;
+  const bool arrays = hitN && clipN && hitT && clipT;
+  if (!arrays && (hitN || clipN || hitT || clipT)) return GV_ERR_BAD_ARG;   // all four or none
+  if (!arrays && !(nxw && nyw && nx_pad && ny_pad)) return GV_ERR_BAD_ARG;
+  GV_TRY
+  if (!sector_path(h)) return state_error(h, "gv_test_end_bitmaps", "the handle is not on the tile path");
+  if (!h->last.miss) return state_error(h, "gv_test_end_bitmaps", "no binned frame has run");
+  if (nxw) *nxw = h->nxw;
+  if (nyw) *nyw = h->nyw;
+  if (nx_pad) *nx_pad = h->nx_pad;
+  if (ny_pad) *ny_pad = h->ny_pad;
+  if (!arrays) return GV_OK;
+  const FrameSet &f = h->fs[h->last.set];
+  int rc = use_device(h);
+  if (rc) return rc;
+  GV_HIP(hipMemcpyAsync(hitN, f.hitN, h->bmN_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipMemcpyAsync(clipN, f.clipN, h->bmN_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipMemcpyAsync(hitT, f.hitT, h->bmT_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipMemcpyAsync(clipT, f.clipT, h->bmT_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  GV_HIP(hipStreamSynchronize(h->stream));
+  return GV_OK;
+  GV_CATCH
+}
+
 int gv_get_cell_idx(gv_handle h, int32_t *out)
 {
   if (!h || !out) return GV_ERR_BAD_ARG;

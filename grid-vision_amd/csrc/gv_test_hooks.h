@@ -79,6 +79,14 @@ int gv_test_sector_plan(int32_t nx, int32_t ny, int32_t cx, int32_t cy, int64_t 
 int gv_test_tick_dets(gv_handle h, gv_lshape_pose *out /* 128 */, int32_t *n, int32_t *n_total);
 int gv_test_tick_dets_host(const gv_lshape_pose *cam, const uint8_t *valid, int32_t n_cand, int32_t empty, const gv_transform *tf_bc,
                            gv_lshape_pose *out /* 128 */, int32_t *n, int32_t *n_total);
+/* gv_test_end_bitmaps: a synchronous copy of the four end bitmaps the tile pass (k_bin_tiles) wrote for the ray stage, of
+ * the buffer set of the last frame, as the last synchronous gv_process_frame on the tile path left them.  Words, not cells:
+ *   N (hitN, clipN): *nxw * *ny_pad words, bit x & 31 of word (x >> 5) * ny_pad + y;
+ *   T (hitT, clipT): *nyw * *nx_pad words, bit y & 31 of word (y >> 5) * nx_pad + x.
+ * All four array pointers null and the four size pointers set: the sizes only.  GV_ERR_STATE when the handle is not on the
+ * tile path or no binned frame has run.  No kernel of its own (tests/test_gpu_tile_pass.py). */
+int gv_test_end_bitmaps(gv_handle h, uint32_t *hitN, uint32_t *clipN, uint32_t *hitT, uint32_t *clipT,
+                        int32_t *nxw, int32_t *nyw, int32_t *nx_pad, int32_t *ny_pad);
 #ifdef __cplusplus
 }
 #endif

@@ -1736,6 +1736,19 @@ class GridVisionHIP:
         self._ck(self._lib.gv_test_tick_dets(self._h, _ptr(out), C.byref(n), C.byref(nt)), "gv_test_tick_dets")
         return out, n.value, nt.value
 
+    def test_end_bitmaps(self):
+        """test hook (csrc/gv_test_hooks.h): the raw words of the four end bitmaps the tile pass of the last synchronous
+        process_frame wrote, and their geometry: (hitN, clipN, hitT, clipT, (nxw, nyw, nx_pad, ny_pad)).  N arrays hold
+        nxw * ny_pad words, T arrays nyw * nx_pad; decoding them is the caller's business."""
+        g = [C.c_int32() for _ in range(4)]
+        self._ck(self._lib.gv_test_end_bitmaps(self._h, None, None, None, None, *[C.byref(v) for v in g]), "gv_test_end_bitmaps")
+        nxw, nyw, nx_pad, ny_pad = (v.value for v in g)
+        hn, cn = np.empty(nxw * ny_pad, np.uint32), np.empty(nxw * ny_pad, np.uint32)
+        ht, ct = np.empty(nyw * nx_pad, np.uint32), np.empty(nyw * nx_pad, np.uint32)
+        self._ck(self._lib.gv_test_end_bitmaps(self._h, _ptr(hn), _ptr(cn), _ptr(ht), _ptr(ct), *[C.byref(v) for v in g]),
+                 "gv_test_end_bitmaps")
+        return hn, cn, ht, ct, (nxw, nyw, nx_pad, ny_pad)
+
     # ---- multi-GPU (RCCL inside the library)
     @staticmethod
     def comm_unique_id() -> bytes:

@@ -70,3 +70,29 @@ def test_cmake_configures_and_builds_the_library(tmp_path):
     declared = set(re.findall(r"\b(gv_[a-z0-9_]+)\s*\(", txt))
     assert declared and declared <= exported, sorted(declared - exported)
     assert os.path.exists(os.path.join(bdir, "viz_demo"))   # the host-only example is part of the default build
+
+
+def test_test_hooks_are_exported_and_stay_outside_the_abi():
+    """csrc/gv_test_hooks.h: every hook it declares is exported by the library the suite loads, every gv_test_* the
+    library exports is declared there, and none of them is a public entry point (no public header, no *_SYMBOLS list).
+    gv_test_end_bitmaps (tests/test_gpu_tile_pass.py) is one of them."""
+    import gvamd
+    from gvamd import build as gvbuild
+    hooks_txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(PKG, "csrc", "gv_test_hooks.h")).read(), flags=re.S)
+    hooks = set(re.findall(r"\b(gv_test_[a-z0-9_]+)\s*\(", hooks_txt))
+    assert "gv_test_end_bitmaps" in hooks and "gv_test_tick_dets" in hooks
+    lib = gvamd.load()
+    assert not [f for f in hooks if not hasattr(lib, f)]
+    nm = subprocess.run(["nm", "-D", "--defined-only", gvbuild.LIB], capture_output=True, text=True).stdout
+    assert set(re.findall(r" T (gv_test_[a-z0-9_]+)", nm)) == hooks
+    public = set()
+    for name in os.listdir(os.path.join(ROOT, "include")):
+        public |= set(re.findall(r"\bgv_[a-z0-9_]+", open(os.path.join(ROOT, "include", name)).read()))
+    lists = set()
+    for attr in dir(gvamd):
+        if attr.endswith("_SYMBOLS"):
+            lists |= set(getattr(gvamd, attr))
+    assert not hooks & public and not hooks & lists
+    assert re.search(r"int gv_test_end_bitmaps\(gv_handle h, uint32_t \*hitN, uint32_t \*clipN, uint32_t \*hitT, uint32_t \*clipT,\s*"
+                     r"int32_t \*nxw, int32_t \*nyw, int32_t \*nx_pad, int32_t \*ny_pad\);", hooks_txt)
+    assert lib.gv_test_end_bitmaps(None, None, None, None, None, None, None, None, None) == 1   # GV_ERR_BAD_ARG, no device touched
