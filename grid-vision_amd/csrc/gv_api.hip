@@ -47,7 +47,7 @@ int drain(gv_context *h)
   for (auto &c : h->cloud) { c.seen = ~0u; c.release_slot = -1; }   // every upload landed, every reader finished
   for (auto &d : h->det) { d.seen = ~0u; d.release_slot = -1; d.readers = 0; }
   h->sh.forget_frames();
-  h->match.clouds = 0u;
+  h->scan_readers.clouds = 0u;
   return GV_OK;
 }
 

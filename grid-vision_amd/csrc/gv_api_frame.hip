@@ -458,16 +458,23 @@ int enqueue_grid_pass(gv_context *h, GridPassJob &job)
   return GV_OK;
 }
 
-// Stream k (0 public, 1 / 2 the lanes) reads cloud C / detection set D: ordered after their uploads
-// (once per upload and stream)
-int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k)
+// Stream k (0 public, 1 / 2 the lanes) reads cloud C: ordered after its upload (once per upload and stream).  The
+// frames' wait and the scan matchers' (gv_api_match.hip, k = 0).
+int wait_cloud(gv_context *h, CloudSet &C, int k)
 {
-  hipStream_t s = h->streams[k];
   if (!(C.seen >> k & 1u)) {
-    GV_HIP(hipStreamWaitEvent(s, C.ready, 0));
+    GV_HIP(hipStreamWaitEvent(h->streams[k], C.ready, 0));
     C.seen |= 1u << k;
     h->sb[k].lane_clean = false;
   }
+  return GV_OK;
+}
+
+// ... and detection set D likewise
+int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k)
+{
+  hipStream_t s = h->streams[k];
+  if (int rc = wait_cloud(h, C, k)) return rc;
   if (!(D.seen >> k & 1u)) {
     GV_HIP(hipStreamWaitEvent(s, D.ready, 0));
     D.seen |= 1u << k;
@@ -667,11 +674,11 @@ int begin_cloud_upload(gv_context *h, size_t n, int &target)
   h->quiet_frames = 0;   // the upload stream is in use: the frames stay off it for a while
   CloudSet &c = h->cloud[target];
   const bool tick_reads = h->tick.pending && h->tick.cloud == target;
-  const bool match_reads = (h->match.clouds >> target & 1u) != 0;   // X16: a gv_match_scan* enqueued since reads this set
+  const bool match_reads = (h->scan_readers.clouds >> target & 1u) != 0;   // a gv_match_scan* / gv_match_search* enqueued since reads this set
   if (n > c.cap) {
     if (c.release_slot >= 0) GV_HIP(hipEventSynchronize(h->ev_fin[c.release_slot]));
     if (tick_reads) GV_HIP(hipEventSynchronize(h->tick.done));   // the tick's kernels read the block freed here
-    if (match_reads) GV_HIP(hipEventSynchronize(h->match.read));
+    if (match_reads) GV_HIP(hipEventSynchronize(h->scan_readers.read));
     GV_HIP(hipEventSynchronize(c.ready));
     c.cap = 0;
     const size_t want = (n + n / 8 + 1024 + 3) & ~(size_t)3;   // the arrays sit at a stride of (n + 3) & ~3 floats
@@ -690,8 +697,8 @@ int begin_cloud_upload(gv_context *h, size_t n, int &target)
     GV_HIP(hipStreamWaitEvent(h->stream_copy, h->ev_fin[c.release_slot], 0));
   if (tick_reads) GV_HIP(hipStreamWaitEvent(h->stream_copy, h->tick.done, 0));   // on the device: the upload stays asynchronous
   if (match_reads) {   // the event of the last call: behind every earlier call's point pass on the public stream
-    GV_HIP(hipStreamWaitEvent(h->stream_copy, h->match.read, 0));
-    h->match.clouds &= ~(1u << target);
+    GV_HIP(hipStreamWaitEvent(h->stream_copy, h->scan_readers.read, 0));
+    h->scan_readers.clouds &= ~(1u << target);
   }
   c.release_slot = -1;
   return GV_OK;

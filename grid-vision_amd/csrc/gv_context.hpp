@@ -477,29 +477,21 @@ struct __attribute__((visibility("hidden"))) gv_context {
   // configuration is handle state and travels in the kernel arguments with the guess and the rotation table.  `pts`
   // (the used points' base-frame x, y) and `head` (the counter of used points, then the score volume) are the scratch
   // of one call, made by the first call that needs them and used on the public stream only: a call's memset and
-  // kernels run behind those of the call before it.  d_result follows TrajScore's rules.  `read` marks the point pass
-  // of the last call, the one kernel that reads the cloud; it is recorded again by every call on the one in-order
-  // stream, so whoever waits for it is behind every earlier call's point pass too.  `clouds` has bit s set when a call
-  // has read cloud set s since the set was last uploaded into or the streams were last drained: any number of calls
-  // may be in flight over the three sets, and an upload into a set whose bit is set waits for `read` and clears that
-  // bit alone (begin_cloud_upload).  gv_reset keeps all of it.
+  // kernels run behind those of the call before it.  d_result follows TrajScore's rules.  gv_reset keeps all of it.
   struct Match {
     bool set = false;
     gv_match_config cfg{};
     DevBuf<float2> pts;
     DevBuf<uint32_t> head;
     DevBuf<gv_match_result> d_result;
-    Event read;
-    uint32_t clouds = 0;
   } match;
   // [EXTENSION] X18 wide-window matching by branch and bound (gv_set_search_config / gv_match_search*,
-  // gv_api_search.hip).  The configuration is handle state, independent of Match's, and travels in the kernel arguments.
+  // gv_api_match.hip).  The configuration is handle state, independent of Match's, and travels in the kernel arguments.
   // The buffers are the scratch of one call, made by the first call that needs them, grown by a larger one and used on
   // the public stream only: `pts` and `head` as Match's (head: the counters, the pre-slots, the bounds), `rows` and
   // `pool` the costmap pooled along x and then along y (pooled per call: a call reads the costmap of the inflate before
   // it), `list` the survivors and `slots` their exact scores, n_blocks * S * S words at the worst.  d_result and d_stats
-  // follow TrajScore's rules; d_stats also takes the stats nobody asked for.  The cloud's readers are marked in
-  // Match::read and Match::clouds: one event and one mask for both matchers.  gv_reset keeps all of it.
+  // follow TrajScore's rules; d_stats also takes the stats nobody asked for.  gv_reset keeps all of it.
   struct Search {
     bool set = false;
     gv_search_config cfg{};
@@ -510,6 +502,17 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<gv_match_result> d_result;
     DevBuf<gv_search_stats> d_stats;
   } search;
+  // The scan readers of the cloud sets: one event and one mask for both matchers (enqueue_scan_read, gv_api_match.hip).
+  // `read` marks the point pass of the last gv_match_scan* or gv_match_search* call, the one kernel of either that
+  // reads the cloud; it is recorded again by every call on the one in-order stream, so whoever waits for it is behind
+  // every earlier call's point pass too.  `clouds` has bit s set when a call has read cloud set s since the set was last
+  // uploaded into or the streams were last drained: any number of calls may be in flight over the three sets, and an
+  // upload into a set whose bit is set waits for `read` and clears that bit alone (begin_cloud_upload).  gv_reset
+  // keeps both.
+  struct ScanReaders {
+    Event read;
+    uint32_t clouds = 0;
+  } scan_readers;
   // The device copy of a sampler's host poses (K * P * 3 floats), one for gv_score_trajectories* and gv_score_nav*.
   // Both enqueue on the public stream only, so a call's copy into it runs behind the kernel of the call before it;
   // and it grows by DevBuf::reserve, hipFree + hipMalloc, where hipFree waits for the device: the block a kernel in
@@ -671,6 +674,7 @@ int check_frame_flags(const gv_context *h, uint32_t fl);
 int enqueue_binning(gv_context *h, const BinningJob &job);
 int enqueue_sectors(gv_context *h, SectorsJob &job);
 int enqueue_grid_pass(gv_context *h, GridPassJob &job);
+int wait_cloud(gv_context *h, CloudSet &C, int k);
 int wait_inputs(gv_context *h, CloudSet &C, DetSet &D, int k);
 // gv_api_shard.hip
 void comm_destroy(gv_context *h);

@@ -318,27 +318,36 @@ void launch_tick_dets(const TickDetsArgs &a, hipStream_t s);
 // [EXTENSION] X16 scan-to-costmap matching (gv_match.hip; the arithmetic is gv_match.hpp's).  The configuration, the
 // guess and the host-built rotation table travel by value: a call already enqueued keeps what it was enqueued with.
 // `head` is one zeroed block per call: word 0 counts the used points, the volume starts at word kMatchHeadWords.
-constexpr int32_t kMatchHeadWords = 4;
-struct MatchArgs {
-  GridParams g;
-  MatchParams p;
+// The point pass (k_match_points) is the one kernel that reads the cloud, and both matchers run it: it has an argument
+// block of its own, over the calling matcher's `pts` and the counter word of its `head`.
+struct MatchPointsArgs {
   Mat34f m_base;
   HeightBand band;
   const float *x, *y, *z;       // the resident cloud (device)
   uint32_t n;                   // its points
-  uint32_t n_sel;               // ceil(n / stride): the selected ones
+  uint32_t n_sel;               // ceil(n / stride): the selected ones, point sel * stride each
+  int32_t stride;
+  uint32_t use_band;
   float2 *pts;                  // n_sel pairs (device): the used points' (bx, by), in any order
+  uint32_t *used;               // their count (device), zero when the pass starts
+};
+void launch_match_points(const MatchPointsArgs &a, hipStream_t s);
+constexpr int32_t kMatchHeadWords = 4;
+struct MatchArgs {
+  GridParams g;
+  MatchParams p;
+  uint32_t n_sel;               // ceil(n / stride): the bound on the used points
+  const float2 *pts;            // the used points' (bx, by) (device)
   uint32_t *head;               // kMatchHeadWords + NT*NY*NX words (device), zero when the point pass starts
   const uint8_t *cost;          // the resident costmap
   gv_match_result *result;      // one record (device memory, or the device view of pinned host memory; 8-byte aligned)
   uint32_t *scores_out;         // null, or the device view of a pinned destination of the volume
   float rot[2 * kMatchMaxSide]; // (c_t, s_t), NT pairs
 };
-void launch_match_points(const MatchArgs &a, hipStream_t s);
 void launch_match_score(const MatchArgs &a, hipStream_t s);
 void launch_match_select(const MatchArgs &a, hipStream_t s);
 // [EXTENSION] X18 wide-window matching by branch and bound (gv_search.hip; the arithmetic is gv_search.hpp's and
-// gv_match.hpp's).  The point pass is X16's, given a MatchArgs over this call's `head` and `pts`.  `head` is one zeroed
+// gv_match.hpp's).  The point pass is X16's, given a MatchPointsArgs over this call's `head` and `pts`.  `head` is one zeroed
 // block per call: the counters below, the two pre-slots (the seed block's exact scores, then the centre block's), then
 // the bounds B[n_blocks].
 enum : int32_t {

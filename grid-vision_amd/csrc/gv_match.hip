@@ -32,31 +32,24 @@ namespace gv {
 namespace {
 constexpr int kThreads = 256;
 constexpr int kSelThreads = 1024;
-
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int o)
-{
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
 }  // namespace
 
-__global__ void __launch_bounds__(kThreads) k_match_points(MatchArgs a)
+__global__ void __launch_bounds__(kThreads) k_match_points(MatchPointsArgs a)
 {
   const uint32_t sel = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
   const int lane = (int)threadIdx.x & 63;
   bool used = false;
   float bx = 0.0f, by = 0.0f, bz = 0.0f;
   if (sel < a.n_sel) {
-    const size_t i = (size_t)sel * (size_t)a.p.stride;   // (n_sel - 1) * stride < n
+    const size_t i = (size_t)sel * (size_t)a.stride;   // (n_sel - 1) * stride < n
     match_base_point(a.m_base, a.x[i], a.y[i], a.z[i], bx, by, bz);
-    used = match_used(bx, by, bz, a.p.use_band, a.band);
+    used = match_used(bx, by, bz, a.use_band, a.band);
   }
   const unsigned long long m = __ballot(used);
   if (m == 0ull) return;
   const int leader = __ffsll((long long)m) - 1;
   uint32_t base = 0u;
-  if (lane == leader) base = atomicAdd(&a.head[0], (uint32_t)__popcll(m));
+  if (lane == leader) base = atomicAdd(a.used, (uint32_t)__popcll(m));
   base = (uint32_t)__shfl((int)base, leader, 64);
   if (used) a.pts[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = make_float2(bx, by);   // < n_used <= n_sel
 }
@@ -146,11 +139,7 @@ __global__ void __launch_bounds__(kSelThreads) k_match_select(MatchArgs a)
     const uint64_t key = match_key(v, t - a.p.wt, r / NX - a.p.wy, r % NX - a.p.wx, lin);
     best = key > best ? key : best;
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t other = shfl_xor64(best, o);
-    best = other > best ? other : best;
-  }
+  best = wave_max64(best);
   if ((tid & 63) == 0) best_s[tid >> 6] = best;
   __syncthreads();
   if (tid == 0) {
@@ -160,7 +149,7 @@ __global__ void __launch_bounds__(kSelThreads) k_match_select(MatchArgs a)
   }
 }
 
-void launch_match_points(const MatchArgs &a, hipStream_t s)
+void launch_match_points(const MatchPointsArgs &a, hipStream_t s)
 {
   hipLaunchKernelGGL(k_match_points, dim3((a.n_sel + kThreads - 1) / kThreads), dim3(kThreads), 0, s, a);
 }

@@ -1,6 +1,6 @@
 // gv_match.hpp -- [EXTENSION] X16 scan-to-costmap matching (gv_match_scan*): the arithmetic of the definition in
 // include/gridvision_hip_match.h, one text for the kernels (gv_match.hip) and for the host twin (gv_match_scan_host,
-// gv_api_match.hip), as gv_track.hpp is for the tracker.  Plain C++ under GV_HD; every translation unit that includes
+// gv_api_match_host.hip), as gv_track.hpp is for the tracker.  Plain C++ under GV_HD; every translation unit that includes
 // it is built with -ffp-contract=off, so each operation below is rounded on its own, on the host and on the device.
 #pragma once
 

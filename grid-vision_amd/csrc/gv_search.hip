@@ -3,7 +3,7 @@
 // host twin).
 //
 // On the public stream, behind one memset of the call's block (the counters, the two pre-slots, the bounds) and X16's
-// point pass (k_match_points, unchanged):
+// point pass (k_match_points, over its own argument block):
 //   k_search_pool_rows / k_search_pool_cols
 //                    the separable sliding S x S maximum of the costmap: first along x into `rows`, then along y into
 //                    M, aprons of S - 1 cells below index 0 included.  M is in cell order (search_pool_at).  A lane a
@@ -35,27 +35,6 @@ constexpr int kThreads = 256;
 constexpr int kFineGrid = 2048;      // workgroups of the fine pass: 8 a CU
 constexpr int kReduceGrid = 256;     // workgroups of the seed and select reductions, at most
 
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int o)
-{
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_max64(uint64_t v)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t other = shfl_xor64(v, o);
-    v = other > v ? other : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += shfl_xor64(v, o);
-  return v;
-}
 __device__ __forceinline__ uint64_t *head64(uint32_t *head, int word) { return reinterpret_cast<uint64_t *>(head + word); }   // word even: 8-byte aligned
 
 __device__ __forceinline__ float2 rot_of(int t)

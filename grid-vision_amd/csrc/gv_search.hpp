@@ -1,7 +1,7 @@
 // gv_search.hpp -- [EXTENSION] X18 wide-window scan matching by branch and bound (gv_match_search*): the arithmetic of
 // the definition in include/gridvision_hip_search.h that X16's text (gv_match.hpp) does not already give -- the block
 // geometry, the pooled costmap's layout and value, the seed's key, the survivor predicate and the stats -- one text for
-// the kernels (gv_search.hip) and for the host twin (gv_match_search_host, gv_api_search.hip).  Plain C++ under GV_HD;
+// the kernels (gv_search.hip) and for the host twin (gv_match_search_host, gv_api_match_host.hip).  Plain C++ under GV_HD;
 // built with -ffp-contract=off like its siblings.
 #pragma once
 

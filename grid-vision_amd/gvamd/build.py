@@ -16,8 +16,8 @@ LIB = os.path.join(PKG, "libgridvision_hip.so")
 SOURCES = ["gv_api.hip", "gv_api_frame.hip", "gv_api_shard.hip", "gv_api_pose.hip", "gv_api_planner.hip", "gv_api_control.hip",
            "gv_api_planner_host.hip", "gv_kernels.hip", "gv_binning.hip", "gv_raysector.hip", "gv_shard.hip", "gv_knn_pca.hip", "gv_cloudops.hip", "gv_gridmove.hip",
            "gv_inflate.hip", "gv_trajscore.hip", "gv_navfield.hip", "gv_rollout.hip", "gv_mppi.hip", "gv_dynscore.hip",
-           "gv_track.hip", "gv_api_match.hip", "gv_match.hip", "gv_api_path.hip", "gv_navpath.hip",
-           "gv_api_search.hip", "gv_search.hip"]
+           "gv_track.hip", "gv_api_match.hip", "gv_api_match_host.hip", "gv_match.hip", "gv_api_path.hip", "gv_navpath.hip",
+           "gv_search.hip"]
 # -ffp-contract=off: cell indices must be bit-exact with the reference's separate
 # multiply/add roundings; no fast-math anywhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",

@@ -207,6 +207,80 @@ def test_uploads_behind_enqueued_matches(gvamd):
             p.close()
 
 
+def test_uploads_behind_both_matchers(gvamd):
+    """The two matchers share one reader event and one mask over the cloud sets.  Two heavy scans (65^3 candidates over
+    20 000 points) and two heavy searches keep the public stream busy, then four light calls -- scan, search, scan, search
+    -- each behind an upload of its own small cloud into a pinned record of its own, then the heavy cloud once more, and
+    one synchronize at the end: every upload into a set waits for the last point pass of either matcher that read it.
+    Every record (and every search's stats) equals the host twin's bytes for the cloud its call was enqueued behind.
+    The issue's 129 x 129 x 9 heavy search is narrowed to 129 x 129 x 3: its twin took 6.0 s on one core beside the heavy
+    scan's 3.6 s, at three yaw candidates 1.8 s."""
+    c = mc.by_name("d_rect")
+    h = _handle(gvamd, c["grid"])
+    cost = _plant(h, c["mask"], mc.SOFT)
+    h.set_transforms(base_lidar=c["tf"])
+    h.set_height_band(None)
+    grid, guess = mc.GRIDS[c["grid"]], c["guess"]
+    heavy_scan, heavy_search = gvamd.MatchConfig(32, 32, 32, 1, 0.01, 1, 0), gvamd.SearchConfig(64, 64, 1, 1, 0.01, 1, 0, 2, 0)
+    light_scan, light_search = lib_cfg(gvamd, c["cfg"]), gvamd.SearchConfig(9, 6, 1, 1, 0.02, 1, 0, 2, 0)
+    hx, hy, hz = mc._scatter(20000, 55)
+    for _ in range(3):                       # every cloud set holds 20 000 points: no upload below grows one
+        h.upload_xyz(hx, hy, hz)
+    lights = [mc._scatter(n, 60 + n) for n in (300, 367, 433, 500)]
+
+    def twin(cfg, x, y, z):
+        if isinstance(cfg, gvamd.SearchConfig):
+            rec, stats = gvamd.match_search_host(*grid, cost, x, y, z, c["tf"], cfg, guess)
+            return np.asarray(rec).tobytes(), np.asarray(stats).tobytes()
+        return np.asarray(gvamd.match_scan_host(*grid, cost, x, y, z, c["tf"], cfg, guess)).tobytes(), None
+
+    def enqueue(cfg, p):
+        if isinstance(cfg, gvamd.SearchConfig):
+            h.set_search_config(cfg)
+            h.match_search_async(guess, p.rec, p.stats)
+        else:
+            h.set_match_config(cfg)
+            h.match_scan_async(guess, p.rec)
+
+    class Pin(_Pinned):
+        def __init__(self):
+            super().__init__(gvamd, 1)
+            self.s = gvamd.PinnedI8(32)
+            self.stats = self.s.array.view(gvamd.SEARCH_STATS_DTYPE)
+
+        def close(self):
+            self.stats = None
+            self.s.close()
+            super().close()
+
+    calls = [(heavy_scan, (hx, hy, hz)), (heavy_scan, (hx, hy, hz)), (heavy_search, (hx, hy, hz)), (heavy_search, (hx, hy, hz))]
+    calls += [(cfg, pts) for cfg, pts in zip((light_scan, light_search, light_scan, light_search), lights)]
+    pins = [Pin() for _ in calls]
+    try:
+        for p in pins:
+            p.rec.view(np.int32)[:] = 7
+            p.stats.view(np.int32)[:] = 7
+        for k, ((cfg, pts), p) in enumerate(zip(calls, pins)):
+            if k >= 4:
+                h.upload_xyz(*pts)
+            enqueue(cfg, p)
+        h.upload_xyz(hx, hy, hz)             # and one more round of the rotation behind the light calls
+        h.synchronize()
+        want = {}
+        for k, ((cfg, pts), p) in enumerate(zip(calls, pins)):
+            key = (bytes(cfg), pts[0].tobytes())
+            if key not in want:
+                want[key] = twin(cfg, *pts)
+            rec, stats = want[key]
+            assert p.rec.tobytes() == rec, (k, p.rec)
+            assert stats is None or p.stats.tobytes() == stats, (k, p.stats)
+        assert len({p.rec.tobytes() for p in pins}) == 6                 # two heavy kinds, four light clouds
+        assert all(int(p.rec["n_used"][0]) == len(pts[0]) and int(p.rec["best_score"][0]) > 0 for (_, pts), p in zip(calls, pins))
+    finally:
+        for p in pins:
+            p.close()
+
+
 def test_match_during_a_pending_tick(gvamd):
     """tick_enqueue, inflate, match, tick_wait: the match reads the tick's grid, not the grid before it"""
     from gvamd import synth

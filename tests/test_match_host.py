@@ -285,3 +285,126 @@ def test_error_table(gvamd):
     assert lib.gv_match_rotations(None, C.byref(q), p(np.zeros(130, np.float32))) == GV_ERR_BAD_ARG
     assert lib.gv_match_rotations(C.byref(good), None, p(np.zeros(130, np.float32))) == GV_ERR_BAD_ARG
     assert lib.gv_match_rotations(C.byref(good), C.byref(q), None) == GV_ERR_BAD_ARG
+
+
+SANITIZED_MAIN = r"""
+// gv_match_scan_host with GV_MATCH_KEEP_SCORES under AddressSanitizer and UBSan: reads one scene and a list of
+// configurations from the file the test wrote, prints the 64 bytes of every record and its volume in hex
+#include <cstdio>
+#include <cstring>
+#include <vector>
+#include "gridvision_hip_match.h"
+int main(int argc, char **argv)
+{
+  if (argc != 2) return 2;
+  FILE *f = std::fopen(argv[1], "rb");
+  if (!f) return 2;
+  int32_t head[5];
+  double real[11];
+  float zs[2];
+  if (std::fread(head, sizeof(head), 1, f) != 1 || std::fread(real, sizeof(real), 1, f) != 1 || std::fread(zs, sizeof(zs), 1, f) != 1) return 2;
+  const int32_t n = head[2], n_cfg = head[3];
+  const int nx = (int)(head[0] / real[0] + 0.5), ny = (int)(head[1] / real[0] + 0.5);
+  std::vector<uint8_t> cost((size_t)nx * ny);                // exactly the bytes the call may read
+  std::vector<float> x((size_t)n), y((size_t)n), z((size_t)n);
+  std::vector<gv_match_config> cfg((size_t)n_cfg);
+  if (std::fread(cost.data(), 1, cost.size(), f) != cost.size()) return 2;
+  for (auto *v : {&x, &y, &z})
+    if (n && std::fread(v->data(), sizeof(float), (size_t)n, f) != (size_t)n) return 2;
+  if (std::fread(cfg.data(), sizeof(gv_match_config), (size_t)n_cfg, f) != (size_t)n_cfg) return 2;
+  std::fclose(f);
+  const gv_transform tf{real[1], real[2], real[3], real[4], real[5], real[6], real[7]};
+  const gv_match_guess q{real[8], real[9], real[10]};
+  gv_height_band band;
+  std::memset(&band, 0, sizeof(band));
+  band.z_ground = zs[0];
+  band.z_max = zs[1];
+  for (const gv_match_config &c : cfg) {
+    gv_match_result r;
+    std::memset(&r, 0xAB, sizeof(r));
+    std::vector<uint32_t> vol((size_t)(2 * c.wt + 1) * (size_t)(2 * c.wy + 1) * (size_t)(2 * c.wx + 1), 0xABABABABu);   // exactly the volume
+    const int rc = gv_match_scan_host((uint8_t)head[0], (uint8_t)head[1], real[0], cost.data(), x.data(), y.data(), z.data(), (size_t)n,
+                                      &tf, head[4] ? &band : nullptr, &c, &q, GV_MATCH_KEEP_SCORES, &r, vol.data());
+    if (rc) { std::printf("rc %d\n", rc); return 3; }
+    const unsigned char *b = (const unsigned char *)&r, *d = (const unsigned char *)vol.data();
+    for (size_t i = 0; i < sizeof(r); ++i) std::printf("%02x", b[i]);
+    for (size_t i = 0; i < vol.size() * sizeof(uint32_t); ++i) std::printf("%02x", d[i]);
+    std::printf("\n");
+  }
+  return 0;
+}
+"""
+
+
+def test_host_twin_under_sanitizers(gvamd, tmp_path):
+    """gv_api_match_host.hip's gv_match_scan_host compiled by g++ with -fsanitize=address,undefined into a stand-alone
+    program with its own main (nothing is loaded into Python), the costmap and the volume in heap blocks of exactly their
+    sizes: every case of family c (the edge and off-map cells of the 50 x 30 grid) and one case each of families a and e
+    under their own configurations (held to match_ref, record and volume), and over family c's scene the widest windows
+    along each axis, 65 x 65 x 1, 1 x 1 x 65 and 65 x 1 x 3 (held to the library's twin through the binding)"""
+    src, exe = str(tmp_path / "san.cpp"), str(tmp_path / "san")
+    with open(src, "w") as f:
+        f.write(SANITIZED_MAIN)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "include"), src, "-x", "c++",
+                           os.path.join(ROOT, "grid-vision_amd", "csrc", "gv_api_match_host.hip"), "-o", exe])
+    wide = ((32, 32, 0), (0, 0, 32), (32, 0, 1))
+    runs = [(c, [c["cfg"]] + [c["cfg"]._replace(wx=wx, wy=wy, wt=wt) for wx, wy, wt in wide]) for c in mc.family_c()]
+    runs += [(mc.by_name("a_small_+3-2+2"), None), (mc.by_name("e_band_on"), None)]
+    for c, cfgs in runs:
+        cfgs = cfgs or [c["cfg"]]
+        geo = mc.geo_of(c["grid"])
+        cost = mc.cost_of(c["mask"], c["inflation"], geo.res)
+        assert cost.size == geo.nx * geo.ny
+        gx, gy, res = mc.GRIDS[c["grid"]]
+        path = str(tmp_path / (c["name"] + ".bin"))
+        with open(path, "wb") as f:
+            f.write(np.array([gx, gy, len(c["x"]), len(cfgs), c["band"] is not None], np.int32).tobytes())
+            f.write(np.array([res, *c["tf"], *c["guess"]], np.float64).tobytes())
+            f.write(np.array(c["band"] or (0.0, 0.0), np.float32).tobytes())
+            f.write(cost.tobytes())
+            for a in (c["x"], c["y"], c["z"]):
+                f.write(np.ascontiguousarray(a, np.float32).tobytes())
+            for k in cfgs:
+                f.write(bytes(lib_cfg(gvamd, k)))
+        out = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0 and not out.stderr, (c["name"], out.stdout[-500:], out.stderr[-4000:])
+        lines = out.stdout.split()
+        assert len(lines) == len(cfgs)
+        want_r, want_v = mc.want(c)
+        assert lines[0] == (want_r.tobytes() + want_v.tobytes()).hex(), c["name"]
+        for k, line in zip(cfgs, lines):
+            rec, vol = gvamd.match_scan_host(gx, gy, res, cost, c["x"], c["y"], c["z"], c["tf"], lib_cfg(gvamd, k), c["guess"], band=c["band"],
+                                             keep_scores=True)
+            assert vol.shape == (2 * k.wt + 1, 2 * k.wy + 1, 2 * k.wx + 1)
+            assert line == (np.asarray(rec).tobytes() + vol.tobytes()).hex(), (c["name"], k)
+
+
+def test_one_text_for_both_matchers(gvamd, tmp_path):
+    """What the two matchers share lives once: gv_match_rules.hpp and gv_api_match_host.hip are plain C++ that g++ alone
+    compiles given only the public include directory (no HIP header, no handle, no __HIPCC__ split), gv_api_search.hip
+    is gone, both build recipes name the files, and the library exports what it exported: the four *_SYMBOLS lists and
+    the test hooks, nothing else of the C ABI's namespace."""
+    csrc = os.path.join(ROOT, "grid-vision_amd", "csrc")
+    inc = "-I" + os.path.join(ROOT, "include")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-ffp-contract=off", inc, "-x", "c++", "-c",
+                           os.path.join(csrc, "gv_api_match_host.hip"), "-o", str(tmp_path / "host.o")])
+    one = str(tmp_path / "rules.cpp")
+    with open(one, "w") as f:
+        f.write('#include "%s"\n' % os.path.join(csrc, "gv_match_rules.hpp"))
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", inc, "-c", one, "-o", str(tmp_path / "rules.o")])
+    for name in ("gv_match_rules.hpp", "gv_api_match_host.hip"):
+        txt = open(os.path.join(csrc, name)).read()
+        assert "__HIPCC__" not in txt and "hip_runtime" not in txt and "gv_context.hpp" not in txt, name
+    assert not os.path.exists(os.path.join(csrc, "gv_api_search.hip"))
+    from gvamd import build as b
+    cmake = open(os.path.join(ROOT, "CMakeLists.txt")).read()
+    for s in ("gv_api_match.hip", "gv_api_match_host.hip", "gv_match.hip", "gv_search.hip"):
+        assert s in b.SOURCES and s in cmake and os.path.exists(os.path.join(csrc, s)), s
+    assert "gv_api_search.hip" not in b.SOURCES and "gv_api_search.hip" not in cmake
+    hooks_txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(csrc, "gv_test_hooks.h")).read(), flags=re.S)
+    hooks = set(re.findall(r"\b(gv_test_[a-z0-9_]+)\s*\(", hooks_txt))
+    nm = subprocess.run(["nm", "-D", "--defined-only", b.LIB], capture_output=True, text=True, check=True).stdout
+    exported = re.findall(r" [A-Za-z] (gv_[A-Za-z0-9_]+)$", nm, flags=re.M)
+    want = gvamd.ABI_SYMBOLS + gvamd.MATCH_SYMBOLS + gvamd.SEARCH_SYMBOLS + gvamd.PATH_SYMBOLS + sorted(hooks)
+    assert len(want) == len(set(want)) and sorted(exported) == sorted(want), sorted(set(exported) ^ set(want))

@@ -338,7 +338,7 @@ int main(int argc, char **argv)
 
 
 def test_host_twin_under_sanitizers(gvamd, tmp_path):
-    """gv_api_search.hip's host twin compiled by g++ with -fsanitize=address,undefined into a stand-alone program with its
+    """gv_api_match_host.hip's host twin compiled by g++ with -fsanitize=address,undefined into a stand-alone program with its
     own main (nothing is loaded into Python) and run on the border cases: each case's own configuration (held to
     search_ref) and, over the same scene, the 257 x 257 window and the narrowest ones at every block size (held to the
     library's twin)"""
@@ -346,7 +346,7 @@ def test_host_twin_under_sanitizers(gvamd, tmp_path):
     with open(src, "w") as f:
         f.write(SANITIZED_MAIN)
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I" + os.path.join(ROOT, "include"), src, "-x", "c++", os.path.join(CSRC, "gv_api_search.hip"), "-o", exe])
+                           "-I" + os.path.join(ROOT, "include"), src, "-x", "c++", os.path.join(CSRC, "gv_api_match_host.hip"), "-o", exe])
     for c in sc.borders():
         geo = mc.geo_of(c["grid"])
         cost = mc.cost_of(c["mask"], c["inflation"], geo.res)
