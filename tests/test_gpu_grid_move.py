@@ -3,11 +3,18 @@ packed int8 in OccupancyGrid.data order) by the whole-cell resample S its planne
 numpy gather bit for bit -- the cell centre and source point in fp64 in include/gridvision_hip.h's operation order,
 grid_map getIndex of the source, the constructor state (0.0, 0.5, 50) off the map -- using the cos / sin / tx / ty the
 call reports.  Then the oracle end to end with moves between its updates, the ordering against pipelined frames and a
-pending tick (the twin-handle pattern of test_gpu_tick.py), stable layer pointers, the residue reset and bad input."""
+pending tick (the twin-handle pattern of test_gpu_tick.py), stable layer pointers, the residue reset and bad input.
+Last, the scenes of tests/grid_move_cases.py (proved on the CPU by tests/test_grid_move_cases_host.py): grids that take
+k_grid_move1, partial row blocks and k_copy_segments' byte tail, quarter turns whose every source lies on a cell border
+so that get_index_fast's exact division decides, and planted layers -- log-odds distinct in every cell by bits, NaNs and
+infinities among them -- on which any wrong source index shows."""
 import numpy as np
 import pytest
 
+import grid_move_cases as gc
+import grid_move_ref as R
 import oracle_lib as ol
+from grid_move_ref import np_move   # (tests/test_gpu_grid_skip.py imports it from here)
 from gvamd import synth
 from test_gpu_parity import _ground_scene, check_grid, make_handle
 
@@ -54,32 +61,6 @@ def _state(h):
 def _same(a, b, tag):
     for k, (x, y) in enumerate(zip(a, b)):
         assert x.tobytes() == y.tobytes(), (tag, ("log_odds", "occupancy", "int8")[k])
-
-
-def np_move(state, nx, ny, res, pos_x, pos_y, info):
-    """the resample of gv_grid_move, in numpy: fp64 centres and sources in the header's order, getIndex, gather"""
-    lo, occ, i8 = state
-    len_x, len_y = nx * res, ny * res
-    off_x, off_y = 0.5 * len_x, 0.5 * len_y
-    c, s, tx, ty = info["cos_yaw"], info["sin_yaw"], info["tx"], info["ty"]
-    cx = (pos_x + off_x) - (np.arange(nx, dtype=np.float64) + 0.5) * res
-    cy = (pos_y + off_y) - (np.arange(ny, dtype=np.float64) + 0.5) * res
-    CX, CY = np.broadcast_to(cx[None, :], (ny, nx)), np.broadcast_to(cy[:, None], (ny, nx))
-    sx = (c * CX - s * CY) + tx
-    sy = (s * CX + c * CY) + ty
-    ux, uy = -((sx - pos_x) - off_x), -((sy - pos_y) - off_y)
-    inside = (ux >= 0.0) & (uy >= 0.0) & (ux < len_x) & (uy < len_y)
-    with np.errstate(invalid="ignore"):
-        jx = np.where(inside, -(((sx - off_x) - pos_x) / res), 0.0).astype(np.int64)
-        jy = np.where(inside, -(((sy - off_y) - pos_y) / res), 0.0).astype(np.int64)
-    inside &= (jx >= 0) & (jy >= 0) & (jx < nx) & (jy < ny)
-    src = np.where(inside, jy * nx + jx, 0).reshape(-1)
-    inside = inside.reshape(-1)
-    cell_i8 = i8[::-1]   # OccupancyGrid.data[G-1-c] -> cell order
-    out_lo = np.where(inside, lo[src], np.float32(0.0)).astype(np.float32)
-    out_occ = np.where(inside, occ[src], np.float32(0.5)).astype(np.float32)
-    out_i8 = np.where(inside, cell_i8[src], np.int8(50)).astype(np.int8)[::-1].copy()
-    return out_lo, out_occ, out_i8
 
 
 def _geom(h, res):
@@ -253,3 +234,74 @@ def test_pointers_residue_reset_and_bad_motion(gvamd):
     assert info["applied"] and info["tx"] == pytest.approx(0.1) and info["res_x"] == pytest.approx(-0.04)
     _same(_state(h), np_move(before, *_geom(h, 0.1), info), "after rejected calls")
     h.close()
+
+
+# ------------------------------------------------------------------------ the scenes of tests/grid_move_cases.py --
+@pytest.fixture(scope="module")
+def handles(gvamd):
+    """one handle per grid, made on first use; every scene plants all three layers anew"""
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            g = gc.GRID[name]
+            cache[name] = h = gvamd.GridVisionHIP(*g.args)
+            assert (h.nx, h.ny, h.G, h.pos_x, h.pos_y) == (g.nx, g.ny, g.nx * g.ny, g.pos_x, g.pos_y)
+        return cache[name]
+    yield get
+    for h in cache.values():
+        h.close()
+
+
+def _check_move(h, res, before, info, tag):
+    """all three layers by bytes against np_move of the readback; returns the state after the move"""
+    geom = _geom(h, res)
+    got, want = _state(h), np_move(before, *geom, info)
+    assert not R.same(got, want), (tag, R.first_difference(got, want, h.nx, R.np_sources(*geom, info)[0]))
+    return got
+
+
+@pytest.mark.parametrize("key", gc.SCENES, ids="-".join)
+def test_scene_equals_np_move_by_bytes(handles, key):
+    g, m = gc.scene(key)
+    res = g.args[2]
+    h = handles(key[0])
+    before = gc.plant(h, g)   # checked on the readback: distinct log-odds words, int8 and occupancy unlike any neighbour's
+    info = h.grid_move(m.tf)
+    assert info["applied"]
+    got = _check_move(h, res, before, info, key)
+    if m.cells:
+        assert (info["cos_yaw"], info["sin_yaw"], info["tx"], info["ty"]) == (1.0, 0.0, res * m.cells[0], res * m.cells[1])
+        assert not R.same(got, R.slice_move(before, h.nx, h.ny, *m.cells)), key
+    if gc.is_border(key):   # with what this call reports, every in-map source is on a cell border on both axes
+        sx, sy = R.np_sources(*_geom(h, res), info)[1:]
+        inside, fx, _, fy, _ = R.fast_quotients(*_geom(h, res), sx, sy)
+        assert inside.sum() >= 50 and (np.abs(fx - np.rint(fx))[inside] < 1e-6).all() and (np.abs(fy - np.rint(fy))[inside] < 1e-6).all()
+    if m.name == "far_away":
+        assert not got[0].any() and (got[1] == 0.5).all() and (got[2] == 50).all()
+
+
+@pytest.mark.parametrize("name", ["25x10@0.2", "167x67@0.3"])
+def test_four_quarter_turns_in_a_row(handles, name):
+    g = gc.GRID[name]
+    h = handles(name)
+    st = gc.plant(h, g)
+    for k in range(4):
+        info = h.grid_move((0.0, 0.0, gc.Q[0], gc.Q[1], 0.0, 0.0, 0.0))
+        assert info["applied"] and abs(info["sin_yaw"]) == 1.0
+        st = _check_move(h, g.args[2], st, info, (name, k))
+        assert np.isnan(st[0]).any() and np.isinf(st[0]).any(), k   # non-finite log-odds are still aboard
+
+
+def test_layer_pointers_stay_on_an_odd_grid(handles):
+    g = gc.GRID["167x67@0.3"]
+    h = handles(g.name)
+    assert h.G % 2 == 1
+    before = gc.plant(h, g)
+    ptrs = h.device_layers()
+    for tf in ((0.0, 0.0, 0.0, 1.0, 2 * g.args[2], -g.args[2], 0.0), (0.0, 0.0, gc.Q[0], gc.Q[1], 0.0, 0.0, 0.0)):
+        info = h.grid_move(tf)
+        assert info["applied"]
+        h.synchronize()
+        assert h.device_layers() == ptrs
+        before = _check_move(h, g.args[2], before, info, tf)

@@ -11,6 +11,7 @@ import pytest
 
 import inflate_cases as ic
 import inflate_ref as ref
+from grid_move_ref import np_move
 from gvamd import synth
 from planner_util import plant_grid
 from test_gpu_parity import _ground_scene, make_handle
@@ -332,10 +333,14 @@ def test_state_rules(gvamd):
         h.reset()
         assert state_error(h.costmap) and state_error(h.obstacle_dist2)
         plant_grid(h, ic.random_mask(h.nx, h.ny, 2e-3, seed=9))
-        assert h.grid_move([0.0, 0.0, 0.0, 1.0, 3 * res, -2 * res, 0.0])["applied"]
+        planted = h.log_odds(), h.occupancy(), h.to_occupancy_grid()[0]
+        info = h.grid_move([0.0, 0.0, 0.0, 1.0, 3 * res, -2 * res, 0.0])
+        assert info["applied"]
         h.inflate()
         moved = h.to_occupancy_grid()[0]
         assert moved.tobytes() != i8b.tobytes()
+        want_moved = np_move(planted, h.nx, h.ny, res, h.pos_x, h.pos_y, info)   # nx % 4 == 2: k_grid_move1
+        assert (h.log_odds().tobytes(), h.occupancy().tobytes(), moved.tobytes()) == tuple(a.tobytes() for a in want_moved)
         assert h.costmap().tobytes() == _want(moved, h.nx, h.ny, cfg, res)[0].tobytes()
         h.set_inflation(None)
         assert state_error(h.inflate)

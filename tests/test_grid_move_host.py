@@ -18,6 +18,7 @@ CSRC = os.path.join(ROOT, "grid-vision_amd", "csrc")
 DRIVER = r"""
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include "gv_host_math.hpp"
 using namespace gv;
@@ -28,6 +29,13 @@ int main(int argc, char **argv)
                 offsetof(gv_grid_move_info, cos_yaw), offsetof(gv_grid_move_info, sin_yaw), offsetof(gv_grid_move_info, tx),
                 offsetof(gv_grid_move_info, ty), offsetof(gv_grid_move_info, res_yaw), offsetof(gv_grid_move_info, res_x),
                 offsetof(gv_grid_move_info, res_y));
+    return 0;
+  }
+  if (argc > 4 && std::strcmp(argv[1], "geometry") == 0) {   // host::grid_params of gv_create's arguments
+    GridParams p{};
+    if (!host::grid_params((uint8_t)std::atoi(argv[2]), (uint8_t)std::atoi(argv[3]), std::atof(argv[4]), p)) return 3;
+    std::printf("%d %d %d %a %a %a %a %a %a %a %a\n", p.nx, p.ny, p.G, p.res, p.pos_x, p.pos_y, p.len_x, p.len_y, p.off_x,
+                p.off_y, p.inv_res);
     return 0;
   }
   GridParams g{};
