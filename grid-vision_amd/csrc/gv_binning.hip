@@ -56,19 +56,6 @@ constexpr uint32_t kInLaneKeys = 128;         // tile pass: a segment up to this
 #define GV_STAMP(dbg, k) do { } while (0)
 #endif
 
-// inclusive add-scan over the 64 lanes as DPP modifiers of six dependent VALU adds (row_shr 1, 2, 4, 8, then
-// row_bcast:15 / :31 into the upper rows) instead of six ds_bpermute round trips
-__device__ __forceinline__ unsigned wave_incl_scan_add(unsigned v)
-{
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
-  return v;
-}
-
 // ------------------------------------------------------------- partition -----
 #define GV_KARG(field) load_karg<decltype(BinArgs::field)>(offsetof(BinArgs, field))
 template <bool RAY, bool BBOX, bool KEEPCELL>
@@ -211,10 +198,8 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
           const bool o = st == kStagedOutside;
           const unsigned long long bm = __ballot(o);
           if (bm) {
-            unsigned wbase = 0;
-            if (lane == 0) wbase = atomicAdd(&s_nout, (unsigned)__popcll(bm));
-            wbase = (unsigned)__builtin_amdgcn_readfirstlane((int)wbase);
-            if (o) outl[wbase + (unsigned)__popcll(bm & ((1ull << lane) - 1ull))] = (unsigned short)k;
+            const unsigned wbase = wave_append_all(&s_nout, bm, lane);
+            if (o) outl[wbase + wave_rank(bm, lane)] = (unsigned short)k;
           }
         }
         if (KEEPCELL && k < npts) cell_idx[base + k] = inside ? jy * g.nx + jx : -1;
@@ -323,7 +308,7 @@ __global__ void __launch_bounds__(kPartThreads, GV_PART_WPE) k_bin_partition(Bin
   const int t0 = tid * per, t1 = min(T, t0 + per);
   unsigned mine = 0;
   for (int t = t0; t < t1; ++t) mine += hist[t];
-  const unsigned incl = wave_incl_scan_add(mine);
+  const unsigned incl = wave_scan<OpAdd>(mine);
   if (lane == 63) s_wsum[wave] = incl;
   __syncthreads();
   unsigned run = incl - mine, total = 0;
@@ -406,7 +391,7 @@ __global__ void __launch_bounds__(kTileThreads) k_bin_tiles(BinTileArgs a)
       hv += (kq > 1u);
       ex += kq - 1u;
     }
-    const unsigned ih = wave_incl_scan_add(hv), ie = wave_incl_scan_add(ex);
+    const unsigned ih = wave_scan<OpAdd>(hv), ie = wave_scan<OpAdd>(ex);
     if (lane == 63) { s_scanh[wave] = ih; s_scane[wave] = ie; }
     __syncthreads();
     unsigned bh = ih - hv, be = ie - ex;
@@ -633,9 +618,9 @@ __global__ void __launch_bounds__(kTileThreads) k_bin_tiles(BinTileArgs a)
     nib <<= 4 * (tid & 7);
     // OR over the 8 lanes of a word into its first lane: lane i takes lane i + 1, + 2, + 4 of its row (DPP row_shl,
     // zero past the row end -- the 8-lane groups are row aligned)
-    nib |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)nib, 0x101, 0xF, 0xF, false);
-    nib |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)nib, 0x102, 0xF, 0xF, false);
-    nib |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)nib, 0x104, 0xF, 0xF, false);
+    nib |= dpp<0x101>(0u, nib);   // row_shl:1
+    nib |= dpp<0x102>(0u, nib);   // row_shl:2
+    nib |= dpp<0x104>(0u, nib);   // row_shl:4
     if ((tid & 7) == 0) bits[0][ly][lx >> 5] = nib;
   }
   __syncthreads();

@@ -169,32 +169,6 @@ __device__ __forceinline__ void smallest_eigenvector3_dev(const double cov[6], d
 
 constexpr int kMom = 10;   // Sx Sy Sz Qxx Qxy Qxz Qyy Qyz Qzz + the inlier count (as a double: exact)
 
-// lane i <- lane i + N inside its row of 16 (DPP row_shl:N; lanes whose source falls outside read 0.0 and hold
-// values nobody uses afterwards)
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, true);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned long long)(unsigned)lo);
-}
-
-// The tree's butterfly v[i] += v[i + off], off = 32 .. 1; lane 0 ends with the sum of the 64 values in the
-// oracle's order (tree_sum64, oracle/ransac.c).  Only lanes below `off` matter at each step, so the four
-// in-row steps are DPP shifts on the operand (no LDS traffic); the two cross-row steps go through the
-// permute network.
-__device__ __forceinline__ double wave_butterfly(double v)
-{
-  v = v + __shfl_down(v, 32);
-  v = v + __shfl_down(v, 16);
-  v = v + dpp_f64<0x108>(v);   // row_shl:8
-  v = v + dpp_f64<0x104>(v);   // row_shl:4
-  v = v + dpp_f64<0x102>(v);   // row_shl:2
-  v = v + dpp_f64<0x101>(v);   // row_shl:1
-  return v;
-}
-
 // Selection + refinement (optimizeModelCoefficients) in one pass.  Every workgroup finds the best hypothesis
 // (most inliers, first wins ties) from the counts, then accumulates the fp64 raw moments of that plane's
 // inliers by the fixed 64-ary tree of oracle/ransac.c: level 0 = 64 consecutive points reduced by the
@@ -787,25 +761,6 @@ __device__ __forceinline__ void pca_means(const long long *__restrict__ a, float
 // profiles/r04/radius_filter_ab.txt.)  The kept points' coordinates are added to their bbox's integer sums on the way
 // out (LDS table per workgroup, flushed once; consecutive points of the bucket order belong to the same box, so a
 // workgroup flushes a handful of entries).
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
-// every lane of a group of LANES consecutive lanes (8 or 16, aligned) ends with the group's sum
-template <int LANES>
-__device__ __forceinline__ int group_sum(int v)
-{
-  if constexpr (LANES == 16) {
-    v += dpp_i32<0x128>(v);   // row_ror:8
-    v += dpp_i32<0x124>(v);   // row_ror:4
-    v += dpp_i32<0x122>(v);   // row_ror:2
-    v += dpp_i32<0x121>(v);   // row_ror:1
-  } else {
-    v += dpp_i32<0x141>(v);   // row_half_mirror: lane i <-> 7 - i of its half row
-    v += dpp_i32<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_i32<0x4E>(v);    // quad_perm [2,3,0,1]
-  }
-  return v;
-}
-
 #ifndef GV_RAD_LANES
 #define GV_RAD_LANES 16
 #endif
@@ -1028,19 +983,6 @@ __global__ void __launch_bounds__(256, GV_RAD_OCC) k_radius_sorted(const CellNod
   }
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, off));
-  return v;
-}
-
 // covariance sums of the fp32-centred samples (cv::PCA: rows (z, x) minus the fp32 mean, products accumulated in
 // fp64 -- here: each product, exact in fp64, rounded once to 2^-26 m^2 and added as an integer)
 __global__ void __launch_bounds__(256) k_pca_cov(const CellNode *__restrict__ sorted, const uint32_t *__restrict__ n_sel_p,
@@ -1077,7 +1019,7 @@ __global__ void __launch_bounds__(256) k_pca_cov(const CellNode *__restrict__ so
     }
     const unsigned long long have = __ballot(id >= 0);
     if (!have) continue;
-    const int id0 = __builtin_amdgcn_readlane(id, __ffsll((long long)have) - 1);
+    const int id0 = __builtin_amdgcn_readlane(id, wave_leader(have));
     const bool uniform = __ballot(id >= 0 && id != id0) == 0ull;
     long long aa = 0, ab = 0, bb = 0;
     if (id >= 0) {
@@ -1092,7 +1034,7 @@ __global__ void __launch_bounds__(256) k_pca_cov(const CellNode *__restrict__ so
       aa = fix_prod(a, a); ab = fix_prod(a, b); bb = fix_prod(b, b);
     }
     if (uniform) {
-      aa = wave_sum_i64(aa); ab = wave_sum_i64(ab); bb = wave_sum_i64(bb);
+      aa = (long long)wave_sum64((uint64_t)aa); ab = (long long)wave_sum64((uint64_t)ab); bb = (long long)wave_sum64((uint64_t)bb);
       if (lane == 0) {
         unsigned long long *d = tab ? reinterpret_cast<unsigned long long *>(&s_acc[id0][0])
                                     : reinterpret_cast<unsigned long long *>(acc + (size_t)id0 * kAccStride + 4);
@@ -1183,7 +1125,7 @@ __global__ void __launch_bounds__(256) k_pca_extent(const CellNode *__restrict__
     }
     const unsigned long long have = __ballot(id >= 0);
     if (!have) continue;
-    const int id0 = __builtin_amdgcn_readlane(id, __ffsll((long long)have) - 1);
+    const int id0 = __builtin_amdgcn_readlane(id, wave_leader(have));
     const bool uniform = __ballot(id >= 0 && id != id0) == 0ull;
     unsigned k0 = 0u, k1 = 0u, k2 = 0u, k3 = 0u;   // zero = "nothing": the identity of the max below
     if (id >= 0) {
@@ -1194,7 +1136,7 @@ __global__ void __launch_bounds__(256) k_pca_extent(const CellNode *__restrict__
       k0 = ~kl; k1 = kl; k2 = ~kw; k3 = kw;
     }
     if (uniform) {
-      k0 = wave_max_u32(k0); k1 = wave_max_u32(k1); k2 = wave_max_u32(k2); k3 = wave_max_u32(k3);
+      k0 = wave_max(k0); k1 = wave_max(k1); k2 = wave_max(k2); k3 = wave_max(k3);
       if (lane == 0) {
         unsigned *e = tab ? &s_ext[id0][0] : ext + (size_t)id0 * kExtStride;
         atomicMax(e + 0, k0); atomicMax(e + 1, k1); atomicMax(e + 2, k2); atomicMax(e + 3, k3);

@@ -1,5 +1,5 @@
 // gv_device.hpp -- device-side arithmetic shared by the gfx950 kernels: the reference's
-// float transform, grid_map's getIndex, the pinhole projection, the X2 ray clip and the 64-bit wavefront reductions.
+// float transform, grid_map's getIndex, the pinhole projection and the X2 ray clip.
 //
 // Every translation unit that includes this is built with -ffp-contract=off: the reference
 // arithmetic keeps separate multiply/add roundings (PCL's SSE transform, grid_map's getIndex)
@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "gv_kernels.hpp"
+#include "gv_wave.hpp"   // the wavefront primitives, for every kernel file that includes this
 
 namespace gv {
 
@@ -37,30 +38,6 @@ __device__ __forceinline__ T load_karg(size_t off)
   (void)off;
   return T{};
 #endif
-}
-
-// 64-bit values across a wavefront (wave64) by two 32-bit shuffles: the butterfly exchange, and the maximum and the sum
-// every lane ends up with (the matchers' 64-bit keys, gv_match.hip and gv_search.hip)
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int o)
-{
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_max64(uint64_t v)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t other = shfl_xor64(v, o);
-    v = other > v ? other : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += shfl_xor64(v, o);
-  return v;
 }
 
 // pcl::detail::Transformer<float>::se3 (SSE2 path): x*c0 + (y*c1 + (z*c2 + c3)),

@@ -85,10 +85,8 @@ __global__ void __launch_bounds__(BIN ? 1024 : 256) k_points(PointsArgs a)
         const unsigned long long bm = __ballot(outside);
         if (bm) {
           const int lane = threadIdx.x & 63;
-          unsigned wbase = 0;
-          if (lane == 0) wbase = atomicAdd(&s_nout, (unsigned)__popcll(bm));
-          wbase = (unsigned)__builtin_amdgcn_readfirstlane((int)wbase);
-          if (outside) s_out[wbase + (unsigned)__popcll(bm & ((1ull << lane) - 1ull))] = make_float2(bx, by);
+          const unsigned wbase = wave_append_all(&s_nout, bm, lane);
+          if (outside) s_out[wbase + wave_rank(bm, lane)] = make_float2(bx, by);
         }
       }
       if (KEEPCELL && live) a.cell_idx[i] = cell;
@@ -652,8 +650,8 @@ __global__ void __launch_bounds__(256) k_ray_compact(const int32_t *__restrict__
     if (m) {
       uint32_t b = 0;
       if (lane == 0) b = atomicAdd(count, (uint32_t)__popcll(m));
-      b = __shfl(b, 0);
-      if (is_end) list[b + __popcll(m & ((1ull << lane) - 1ull))] = e;
+      b = wave_bcast(b, 0);   // (through the permute network, not wave_append_all's scalar register: as measured here)
+      if (is_end) list[b + wave_rank(m, lane)] = e;
     }
   }
 }

@@ -3,6 +3,7 @@
 // rectangle of the same reference file live in gv_cloudops.hip.
 // gfx950, wave64, built with -ffp-contract=off.
 #include "gv_kernels.hpp"
+#include "gv_wave.hpp"
 
 #include <float.h>
 #include <math.h>
@@ -59,34 +60,14 @@ void launch_project_uvd(const KnnArgs &a, hipStream_t s)
 typedef unsigned long long KnnKey;
 constexpr KnnKey kKnnNone = ~0ull;   // the d2 half is a NaN pattern: never a real candidate
 __device__ __forceinline__ KnnKey knn_key(float d2, uint32_t idx) { return ((KnnKey)__float_as_uint(d2) << 32) | (KnnKey)idx; }
-template <int CTRL>
-__device__ __forceinline__ KnnKey dpp_key(KnnKey v)
-{
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v & 0xffffffffull), CTRL, 0xF, 0xF, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xF, 0xF, false);
-  return ((KnnKey)hi << 32) | (KnnKey)lo;
-}
-// minimum over the wavefront, in every lane: rotations by 8, 4, 2, 1 inside the rows of 16 (DPP row_ror: every lane
-// ends with its row's minimum), then the two cross-row steps through the permute network
-__device__ __forceinline__ KnnKey wave_min_key(KnnKey v)
-{
-  KnnKey o;
-  o = dpp_key<0x128>(v); v = o < v ? o : v;   // row_ror:8
-  o = dpp_key<0x124>(v); v = o < v ? o : v;   // row_ror:4
-  o = dpp_key<0x122>(v); v = o < v ? o : v;   // row_ror:2
-  o = dpp_key<0x121>(v); v = o < v ? o : v;   // row_ror:1
-  o = __shfl_xor(v, 16); v = o < v ? o : v;
-  o = __shfl_xor(v, 32); v = o < v ? o : v;
-  return v;
-}
 
 // value of lane ^ J: quad permutes for J = 1, 2, ds_swizzle (bit-mask mode, xor inside 32 lanes) for 4, 8, 16, the
 // permute network for 32
 template <int J>
 __device__ __forceinline__ KnnKey xor_lane_key(KnnKey v)
 {
-  if constexpr (J == 1) return dpp_key<0xB1>(v);        // quad_perm [1,0,3,2]
-  else if constexpr (J == 2) return dpp_key<0x4E>(v);   // quad_perm [2,3,0,1]
+  if constexpr (J == 1) return dpp64<0xB1>(v);          // quad_perm [1,0,3,2]
+  else if constexpr (J == 2) return dpp64<0x4E>(v);     // quad_perm [2,3,0,1]
   else if constexpr (J == 32) return __shfl_xor(v, 32);
   else {
     constexpr int pat = (J << 10) | 0x1f;
@@ -208,7 +189,7 @@ __global__ void __launch_bounds__(kKnnThreads) k_knn_stage1(const float *__restr
       const bool ok = r <= thresh_f;
       const unsigned long long mk = __ballot(ok);
       if (mk) {
-        if (ok) buf[nbuf + __popcll(mk & ((1ull << lane) - 1ull))] = knn_key(r, i);
+        if (ok) buf[nbuf + wave_rank(mk, lane)] = knn_key(r, i);
         nbuf += (int)__popcll(mk);
         if (nbuf >= 64) merge();
       }

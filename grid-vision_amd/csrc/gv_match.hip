@@ -47,11 +47,8 @@ __global__ void __launch_bounds__(kThreads) k_match_points(MatchPointsArgs a)
   }
   const unsigned long long m = __ballot(used);
   if (m == 0ull) return;
-  const int leader = __ffsll((long long)m) - 1;
-  uint32_t base = 0u;
-  if (lane == leader) base = atomicAdd(a.used, (uint32_t)__popcll(m));
-  base = (uint32_t)__shfl((int)base, leader, 64);
-  if (used) a.pts[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = make_float2(bx, by);   // < n_used <= n_sel
+  const uint32_t base = wave_append(a.used, m, lane);
+  if (used) a.pts[base + wave_rank(m, lane)] = make_float2(bx, by);   // < n_used <= n_sel
 }
 
 template <int KACC>

@@ -260,8 +260,7 @@ __global__ void __launch_bounds__(kMppiThreads) k_mppi_control_cost(MppiCostArgs
     const int k = kb + i;
     if (k >= a.K) break;       // the same for every lane of the wavefront
     double v = mppi_cost_lane(a.qc, a.C, a.nominal, a.P, a.shift, a.controls + (size_t)k * J, lane);
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) v = v + __shfl_down(v, w, 64);   // lanes l < w hold a_l + a_(l + w)
+    v = wave_tree_sum_shfl(v);   // lane 0: the 64 values in the fixed tree's order
     if (lane == 0) {
       a.g[k] = v;
       const uint64_t t = a.totals[k];

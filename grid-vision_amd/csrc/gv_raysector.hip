@@ -19,6 +19,7 @@
 // most two) buckets its slope interval only partly covers.  Everything is
 // integer arithmetic: bit-exact against the oracle's literal march.
 #include "gv_kernels.hpp"
+#include "gv_wave.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -35,44 +36,6 @@ namespace gv {
 //   T: bits run along y, word(y>>5, x) at  (y>>5)*nx_pad + x   (x-major octants)
 // nx_pad / ny_pad are multiples of 128.  The end bitmaps are written by the binning tile pass
 // (gv_binning.hip), which also zeroes the free-cell bitmaps of the buffer set it is about to use.
-
-// ------------------------------------------------ wavefront primitives (DPP) --
-// Cross-lane steps as DPP modifiers of VALU ops (gfx9: row_shr, wave_shl:1, row_bcast:15/31)
-// instead of ds_bpermute round trips through the LDS crossbar: a 64-lane scan is six dependent
-// VALU ops (~tens of cycles) rather than six LDS latencies (~hundreds).
-template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF>
-__device__ __forceinline__ unsigned dpp_u32(unsigned old, unsigned src)
-{
-  return (unsigned)__builtin_amdgcn_update_dpp((int)old, (int)src, CTRL, ROW_MASK, BANK_MASK, false);
-}
-struct OpAdd { static constexpr unsigned id = 0u; __device__ static unsigned f(unsigned a, unsigned b) { return a + b; } };
-struct OpMax { static constexpr unsigned id = 0u; __device__ static unsigned f(unsigned a, unsigned b) { return a > b ? a : b; } };
-struct OpMin { static constexpr unsigned id = 0xFFFFFFFFu; __device__ static unsigned f(unsigned a, unsigned b) { return a < b ? a : b; } };
-// inclusive scan over the 64 lanes (lane 63 ends up with the reduction)
-template <class Op>
-__device__ __forceinline__ unsigned wave_scan(unsigned v)
-{
-  v = Op::f(v, dpp_u32<0x111>(Op::id, v));        // row_shr:1
-  v = Op::f(v, dpp_u32<0x112>(Op::id, v));        // row_shr:2
-  v = Op::f(v, dpp_u32<0x114>(Op::id, v));        // row_shr:4
-  v = Op::f(v, dpp_u32<0x118>(Op::id, v));        // row_shr:8
-  v = Op::f(v, dpp_u32<0x142, 0xA>(Op::id, v));   // row_bcast:15 -> rows 1, 3
-  v = Op::f(v, dpp_u32<0x143, 0xC>(Op::id, v));   // row_bcast:31 -> rows 2, 3
-  return v;
-}
-template <class Op>
-__device__ __forceinline__ unsigned wave_reduce(unsigned v)   // same value in every lane
-{
-  return (unsigned)__builtin_amdgcn_readlane((int)wave_scan<Op>(v), 63);
-}
-// value of lane + H (H = 1, 2, 4, 8) or `fill` past lane 63: H single-lane wave shifts
-template <int H>
-__device__ __forceinline__ unsigned wave_shift_down(unsigned v, unsigned fill)
-{
-#pragma unroll
-  for (int k = 0; k < H; ++k) v = dpp_u32<0x130>(fill, v);   // wave_shl:1
-  return v;
-}
 
 // Products of small non-negative / small signed integers (wedge offsets, sector numbers, slopes: all far below
 // 2^23): v_mul_u32_u24 / v_mul_i32_i24 issue at the full vector rate, v_mul_lo_u32 at half of it (measured,
@@ -245,9 +208,6 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
     else if (r >= Q) ++q;
     return q;
   };
-  // wavefront sum / min (no same-address LDS atomics: those serialise)
-  auto wave_sum = [](unsigned v) -> unsigned { return wave_reduce<OpAdd>(v); };
-  auto wave_min = [](unsigned v) -> unsigned { return wave_reduce<OpMin>(v); };
   // slope bucket of an end: floor((b*S - a*s) * M / a); slope 1 (last sector) -> M-1
   auto bucket_of_end = [&](int a, int b) -> int {
     const int rel = m24(b, S) - m24(a, s);
@@ -544,7 +504,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
         atomicMax(&bmax32[bk], rch);
         vis += rch;
       }
-      vis = wave_sum(vis);
+      vis = wave_reduce<OpAdd>(vis);
       if (lane == 0 && vis) s_wvis[wave] += vis;   // one owner per slot
     }
     __syncthreads();
@@ -625,10 +585,8 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
         }
         const unsigned long long bm = __ballot(live);
         if (bm) {
-          unsigned base = 0;
-          if (lane == 0) base = atomicAdd(&s_nover2, (unsigned)__popcll(bm));
-          base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-          if (live) over2[base + (unsigned)__popcll(bm & ((1ull << lane) - 1ull))] = v;
+          const unsigned base = wave_append_all(&s_nover2, bm, lane);
+          if (live) over2[base + wave_rank(bm, lane)] = v;
         }
       }
     }
@@ -644,7 +602,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
       // inside one block; coarser levels are read off s_blkmax at query time.
       // only levels Lv <= lv_max are ever queried (2^Lv >= 2i/S, i <= imax)
       if (LM <= lv_max) {
-        const unsigned mn = wave_min((m < M && !gap_group(m, 1)) ? v : 0xFFFFFFFFu);
+        const unsigned mn = wave_reduce<OpMin>((m < M && !gap_group(m, 1)) ? v : 0xFFFFFFFFu);
         if (lane == 0) s_lvlmin[LM * 8 + wave] = mn;
       }
 #pragma unroll
@@ -663,7 +621,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
         v = max(v, up);
         if (m < M) lvl[(l << LM) + m] = (unsigned short)v;
         if (l <= LM && LM - l <= lv_max) {
-          const unsigned mn = wave_min(((lane & ((1 << l) - 1)) == 0 && m < M && !gap_group(m, 1 << l)) ? v : 0xFFFFFFFFu);
+          const unsigned mn = wave_reduce<OpMin>(((lane & ((1 << l) - 1)) == 0 && m < M && !gap_group(m, 1 << l)) ? v : 0xFFFFFFFFu);
           if (lane == 0) s_lvlmin[(LM - l) * 8 + wave] = mn;
         }
       }
@@ -701,9 +659,9 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
       }
     }
     unsigned vmin = vread;   // lane 8l+7 <- min over the blocks of level LM-l
-    vmin = min(vmin, dpp_u32<0x111>(0xFFFFFFFFu, vmin));
-    vmin = min(vmin, dpp_u32<0x112>(0xFFFFFFFFu, vmin));
-    vmin = min(vmin, dpp_u32<0x114>(0xFFFFFFFFu, vmin));
+    vmin = min(vmin, dpp<0x111>(0xFFFFFFFFu, vmin));
+    vmin = min(vmin, dpp<0x112>(0xFFFFFFFFu, vmin));
+    vmin = min(vmin, dpp<0x114>(0xFFFFFFFFu, vmin));
     unsigned bm[8];
 #pragma unroll
     for (int bk = 0; bk < 8; ++bk) bm[bk] = (unsigned)__builtin_amdgcn_readlane((int)vread, 56 + bk);
@@ -749,7 +707,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
       if (failm == 0ull) {
         T0 = __builtin_amdgcn_readlane(hiL, lv_top);
       } else {
-        const int f = __ffsll((long long)failm) - 1;
+        const int f = wave_leader(failm);
         const int prev = (f > 0) ? __builtin_amdgcn_readlane(hiL, f - 1) : 0;
         const int hf = __builtin_amdgcn_readlane(hiL, f);
         const int lf = __builtin_amdgcn_readlane((int)lmv, f);
@@ -813,12 +771,12 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
         if (bm) {
           unsigned base = 0;
           if (lane == 0) base = atomicAdd(&s_nlong, (unsigned)__popcll(bm));
-          base = __shfl(base, 0);
-          const unsigned pos = base + (unsigned)__popcll(bm & ((1ull << lane) - 1ull));
+          base = wave_bcast(base, 0);   // (through the permute network, not wave_append_all's scalar register)
+          const unsigned pos = base + wave_rank(bm, lane);
           if (lng && pos < 2u * (unsigned)M) bmax32[pos] = p;   // (the bucket maxima are dead by now: 2M entries)
         }
       }
-      const unsigned r = wave_sum(st);
+      const unsigned r = wave_reduce<OpAdd>(st);
       if (lane == 0) s_wsum[wave] = r;
       __syncthreads();
       unsigned tail_steps = 0;
@@ -982,7 +940,7 @@ __global__ void __launch_bounds__(kSecThreads, GV_SECTOR_WPE) k_ray_sectors(Sect
     if (!single) {
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
-        const unsigned r = wave_sum((unsigned)__popc(ends[c]));
+        const unsigned r = wave_reduce<OpAdd>((unsigned)__popc(ends[c]));
         if (lane == 0) s_rowpart[c][wave] = r;
       }
       __syncthreads();

@@ -268,17 +268,15 @@ __global__ void __launch_bounds__(kThreads) k_search_prune(SearchArgs a)
   }
   const unsigned long long m = __ballot(keep);
   if (m == 0ull) return;
-  const int leader = __ffsll((long long)m) - 1;
-  uint32_t total = n_cand;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) total += (uint32_t)__shfl_xor((int)total, o, 64);
+  const int leader = wave_leader(m);
+  const uint32_t total = wave_sum(n_cand);
   uint32_t base = 0u;
   if (lane == leader) {
     base = atomicAdd(&a.head[kSearchSurvivors], (uint32_t)__popcll(m));
     atomicAdd(&a.head[kSearchScored], total);
   }
-  base = (uint32_t)__shfl((int)base, leader, 64);
-  if (keep) a.list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = blk;   // < n_survivors <= n_blocks
+  base = wave_bcast(base, leader);
+  if (keep) a.list[base + wave_rank(m, lane)] = blk;   // < n_survivors <= n_blocks
   // the wavefront's slots are consecutive: base .. base + popcount, S2 words each
   const size_t words = (size_t)__popcll(m) * (size_t)S2;
   uint32_t *z = a.slots + (size_t)base * (size_t)S2;

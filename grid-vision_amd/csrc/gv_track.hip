@@ -51,7 +51,7 @@ __device__ __forceinline__ int prefix128(bool flag, int tid, int32_t *cnt_s, int
 {
   const unsigned long long b = __ballot(flag);
   const int lane = tid & 63, wave = tid >> 6;
-  const int below = __popcll(b & ((1ull << lane) - 1ull));
+  const int below = (int)wave_rank(b, lane);
   if (lane == 0) cnt_s[wave] = __popcll(b);
   __syncthreads();
   const int first = cnt_s[wave & ~1];
@@ -138,9 +138,9 @@ __global__ void __launch_bounds__(kThreads) k_track_update(TrackArgs a)
         }
       }
       while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
+        const int src = wave_leader(todo);
         todo &= todo - 1;
-        const double qx = __shfl(mx, src, 64), qy = __shfl(my, src, 64);
+        const double qx = wave_bcast(mx, src), qy = wave_bcast(my, src);
         int bj = -1;
         double bd = 0.0;
         for (int j = lane; j < m; j += 64) {
@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(kDetThreads) k_tick_dets(TickDetsArgs a)
       before += w < wave ? k : 0;
       total += k;
     }
-    const int rank = base + before + __popcll(b & ((1ull << lane) - 1ull));
+    const int rank = base + before + (int)wave_rank(b, lane);
     if (take && rank < kTickDets) {
       gv_lshape_pose p;
       if (a.mode == kTickDetsVision) {

@@ -35,13 +35,6 @@ constexpr int kEdges = 16;                 // most vertices of a footprint
 constexpr int kVerts = kEdges + 1;         // LDS cells per pose: the centre and the vertices
 constexpr int kWaves = 4;                  // wavefronts per workgroup: they share a chunk's poses
 
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 }  // namespace
 
