@@ -511,7 +511,11 @@ int gv_transform_lidar_to_camera(gv_handle h, float *x_cam, float *y_cam, float 
   const size_t n = h->n;
   if ((rc = ensure_tbuf(h, n))) return rc;
   if (n) {
-    launch_transform_cloud(h->cx, h->cy, h->cz, (uint32_t)n, h->m_cam, h->tx, h->ty, h->tz, h->stream);
+    TransformCloudArgs ta;
+    ta.x = h->cx; ta.y = h->cy; ta.z = h->cz; ta.n = (uint32_t)n;
+    ta.m = h->m_cam;
+    ta.ox = h->tx; ta.oy = h->ty; ta.oz = h->tz;
+    launch_transform_cloud(ta, h->stream);
     GV_HIP(hipGetLastError());
     GV_HIP(hipMemcpyAsync(x_cam, h->tx, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     GV_HIP(hipMemcpyAsync(y_cam, h->ty, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -717,7 +721,13 @@ int gv_update_map_poses(gv_handle h, const gv_lshape_pose *poses, int32_t n)
   u.masks = false;
   if ((rc = upload_det(h, d, u))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
-  if (n) launch_rects_from_poses(d.poses, n, h->g, false, h->x_bc, h->fs[0].rects, h->stream);
+  if (n) {
+    RectsFromPosesArgs ra;
+    ra.poses = d.poses; ra.n = n; ra.g = h->g;
+    ra.from_cam = false; ra.bc = h->x_bc;
+    ra.rects = h->fs[0].rects;
+    launch_rects_from_poses(ra, h->stream);
+  }
   if ((rc = enqueue_plain_update(h, n))) return rc;
   GV_HIP(hipStreamSynchronize(h->stream));
   return GV_OK;
@@ -733,7 +743,10 @@ int gv_update_map_points(gv_handle h, const double *pts, const gv_bbox *bboxes, 
   if ((rc = upload_scratch_bboxes(h, bboxes, n, false))) return rc;
   if (n) {
     GV_HIP(hipMemcpyAsync(h->d_pts, pts, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    launch_rects_from_points(h->d_pts, h->det[2].bboxes, n, h->g, h->fs[0].rects, h->stream);
+    RectsFromPointsArgs ra;
+    ra.pts_xyz = h->d_pts; ra.bboxes = h->det[2].bboxes; ra.n = n;
+    ra.g = h->g; ra.rects = h->fs[0].rects;
+    launch_rects_from_points(ra, h->stream);
   }
   if ((rc = enqueue_plain_update(h, n))) return rc;
   GV_HIP(hipStreamSynchronize(h->stream));
@@ -873,11 +886,15 @@ int gv_get_miss(gv_handle h, int32_t *out)
   if (!h->last.miss) return GV_ERR_STATE;
   int rc = use_device(h);
   if (rc) return rc;
-  if (sector_path(h))
-    launch_miss_to_i32(h->fs[h->last.set].freeN, h->fs[h->last.set].freeT, h->g.nx, h->g.ny, h->nx_pad, h->ny_pad,
-                       h->scratch_i32, h->stream);
-  else
+  if (sector_path(h)) {
+    MissToI32Args ma;
+    ma.freeN = h->fs[h->last.set].freeN; ma.freeT = h->fs[h->last.set].freeT;
+    ma.nx = h->g.nx; ma.ny = h->g.ny; ma.nx_pad = h->nx_pad; ma.ny_pad = h->ny_pad;
+    ma.out = h->scratch_i32;
+    launch_miss_to_i32(ma, h->stream);
+  } else {
     launch_u8_to_i32(h->miss8, h->scratch_i32, (size_t)h->g.G, h->stream);
+  }
   GV_HIP(hipGetLastError());
   return copy_out(h, out, h->scratch_i32, (size_t)h->g.G * sizeof(int32_t));
 }

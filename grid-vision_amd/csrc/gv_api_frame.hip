@@ -254,14 +254,20 @@ int upload_det(gv_context *h, DetSet &d, const DetUpload &u)
   if (u.conf) put(L.conf, u.conf, (size_t)n_net * 2 * sizeof(float));
   if (u.dims) put(L.dims, u.dims, (size_t)n_net * 3 * sizeof(float));
   d.mask_words = std::max(1, (nb_test + 63) / 64);
+  BBoxPrepareArgs pa;
+  pa.bboxes = d.bboxes; pa.nb = nb_test;
+  pa.tiles_x = h->bt_tiles_x; pa.tiles_y = h->bt_tiles_y; pa.mask_words = d.mask_words;
+  pa.bbox_f = d.bbox_f; pa.tile_mask = d.tile_mask;
   if (u.fused && used) {
     // fused: ONE kernel reads the pinned staging (device visible) -- copies the block and builds the tables from the
     // staged boxes -- instead of a copy command (7 us as a blit kernel) + the table kernel behind it
-    launch_bbox_prepare(reinterpret_cast<const gv_bbox *>(d.stage + L.bboxes), u.masks ? nb_test : 0, h->bt_tiles_x, h->bt_tiles_y,
-                        d.mask_words, d.bbox_f, d.tile_mask, s, d.stage, d.block, used);
+    pa.bboxes = reinterpret_cast<const gv_bbox *>(d.stage + L.bboxes);
+    pa.nb = u.masks ? nb_test : 0;
+    pa.copy_src = d.stage; pa.copy_dst = d.block; pa.copy_bytes = used;
+    launch_bbox_prepare(pa, s);
   } else {
     if (used) GV_HIP(hipMemcpyAsync(d.block, d.stage, used, hipMemcpyHostToDevice, s));
-    if (u.masks) launch_bbox_prepare(d.bboxes, nb_test, h->bt_tiles_x, h->bt_tiles_y, d.mask_words, d.bbox_f, d.tile_mask, s);
+    if (u.masks) launch_bbox_prepare(pa, s);
   }
   GV_HIP(hipGetLastError());
   d.nb = nb_test;
@@ -291,13 +297,20 @@ int upload_scratch_bboxes(gv_context *h, const gv_bbox *b, int32_t nb, bool mask
 int32_t enqueue_rects(gv_context *h, const DetSet &D, Rect *rects, VisionOut *vout, hipStream_t s)
 {
   const bool vision = frame_flags(D.flags).vision;
+  RectsFromPosesArgs ra;
+  ra.poses = D.poses; ra.g = h->g; ra.bc = h->x_bc; ra.rects = rects;
   if (vision && D.nb > 0) {
-    launch_vision(D.orient, D.conf, D.dims, D.bboxes, D.nb, h->cam, vout, D.poses, nullptr, nullptr, s);
-    launch_rects_from_poses(D.poses, D.nb, h->g, true, h->x_bc, rects, s);
+    VisionArgs va;
+    va.orient = D.orient; va.conf = D.conf; va.dims = D.dims; va.bboxes = D.bboxes; va.nb = D.nb;
+    va.cam = h->cam; va.out = vout; va.poses_cam = D.poses;
+    launch_vision(va, s);
+    ra.n = D.nb; ra.from_cam = true;
+    launch_rects_from_poses(ra, s);
     return D.nb;
   }
   if (!vision && D.n_poses > 0) {
-    launch_rects_from_poses(D.poses, D.n_poses, h->g, false, h->x_bc, rects, s);
+    ra.n = D.n_poses; ra.from_cam = false;
+    launch_rects_from_poses(ra, s);
     return D.n_poses;
   }
   return 0;
@@ -637,9 +650,15 @@ int enqueue_frame_generic(gv_context *h, bool stage_events)
     GV_HIP(hipMemsetAsync(h->ray_count, 0, sizeof(uint32_t), s));
     GV_HIP(hipMemsetAsync(h->fs[0].stats, 0, 2 * sizeof(unsigned long long), s));
     h->last.stat_slots = 1;
-    launch_ray_compact(hits, h->clip_end, h->g, h->ray_list, h->ray_count, s);
+    RayCompactArgs rc_a;
+    rc_a.hits = hits; rc_a.clip_end = h->clip_end; rc_a.g = h->g;
+    rc_a.list = h->ray_list; rc_a.count = h->ray_count;
+    launch_ray_compact(rc_a, s);
     if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageRayCompact + 1], s));
-    launch_ray_march(h->ray_list, h->ray_count, h->g, h->org, h->miss8, h->fs[0].stats, s);
+    RayMarchArgs rm;
+    rm.list = h->ray_list; rm.count = h->ray_count; rm.g = h->g; rm.org = h->org;
+    rm.miss = h->miss8; rm.stats = h->fs[0].stats;
+    launch_ray_march(rm, s);
     if (stage_events) GV_HIP(hipEventRecord(h->ev[kStageRayMarch + 1], s));
   } else if (stage_events) {
     GV_HIP(hipEventRecord(h->ev[kStageRayCompact + 1], s));
@@ -761,7 +780,11 @@ int upload_pc2(gv_context *h, const uint8_t *data, size_t n, uint32_t point_step
   }
   if (n) {
     GV_HIP(hipMemcpyAsync(c.raw, data, bytes, hipMemcpyHostToDevice, h->stream_copy));
-    launch_deinterleave(c.raw, (uint32_t)n, point_step, off_x, off_y, off_z, c.x, c.y, c.z, h->stream_copy);
+    DeinterleaveArgs da;
+    da.data = c.raw; da.n = (uint32_t)n; da.point_step = point_step;
+    da.off_x = off_x; da.off_y = off_y; da.off_z = off_z;
+    da.x = c.x; da.y = c.y; da.z = c.z;
+    launch_deinterleave(da, h->stream_copy);
     GV_HIP(hipGetLastError());
   }
   if ((rc = end_cloud_upload(h, target, n))) return rc;

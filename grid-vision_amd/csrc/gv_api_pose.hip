@@ -49,6 +49,16 @@ static DetUpload vision_upload(const gv_bbox *bboxes, int32_t nb, const float *o
   return u;
 }
 
+// the solver over the first nb boxes of such an upload, its records into the standalone scratch (sets, out_dev: null)
+static VisionArgs scratch_vision_args(gv_context *h, const DetSet &d, int32_t nb)
+{
+  VisionArgs a;
+  a.orient = d.orient; a.conf = d.conf; a.dims = d.dims; a.bboxes = d.bboxes; a.nb = nb;
+  a.cam = h->cam;
+  a.out = h->sb[0].vout; a.poses_cam = d.poses;
+  return a;
+}
+
 int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, const float *dims,
                            const gv_bbox *bboxes, int32_t nb, gv_lshape_pose *poses_out, int32_t *n_out)
 {
@@ -61,7 +71,7 @@ int gv_vision_post_process(gv_handle h, const float *orient, const float *conf, 
   DetSet &d = h->det[2];
   if ((rc = upload_det(h, d, vision_upload(bboxes, nb, orient, conf, dims, h->stream)))) return rc;
   GV_HIP(hipEventRecord(d.ready, h->stream));
-  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, nullptr, nullptr, h->stream);
+  launch_vision(scratch_vision_args(h, d, nb), h->stream);
   GV_HIP(hipGetLastError());
   std::vector<VisionOut> vo((size_t)nb);
   GV_HIP(hipMemcpyAsync(vo.data(), h->sb[0].vout, (size_t)nb * sizeof(VisionOut), hipMemcpyDeviceToHost, h->stream));
@@ -85,7 +95,9 @@ int gv_test_vision_sets(gv_handle h, const float *orient, const float *conf, con
   GV_HIP(hipEventRecord(d.ready, h->stream));
   DevBuf<float> dsets;   // nb * 64 * (loc0, loc1, loc2, err), then nb winners
   if ((rc = dsets.reserve(h, (size_t)nb * 257))) return rc;
-  launch_vision(d.orient, d.conf, d.dims, d.bboxes, nb, h->cam, h->sb[0].vout, d.poses, dsets, nullptr, h->stream);
+  VisionArgs va = scratch_vision_args(h, d, nb);
+  va.sets = dsets;
+  launch_vision(va, h->stream);
   GV_HIP(hipGetLastError());
   GV_HIP(hipMemcpyAsync(sets, dsets, (size_t)nb * 256 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   GV_HIP(hipMemcpyAsync(winner, dsets + (size_t)nb * 256, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -597,10 +609,17 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
     da.tf_bc = h->tf_bc;
     da.out = T.dets;
   }
+  RectsFromPosesArgs ra;   // either branch's camera-frame poses -> rectangles
+  ra.poses = D.poses; ra.g = h->g; ra.from_cam = true; ra.bc = h->x_bc; ra.rects = rects;
   if (net) {   // VisionOrientation::postProcessOutputs (:190-209)
-    launch_vision(D.orient, D.conf, D.dims, D.bboxes + n_all + ns, nd, h->cam, reinterpret_cast<VisionOut *>(blk + T.off_vout),
-                  D.poses, nullptr, keep_dets ? T.dets_vout.get() : nullptr, s);
-    launch_rects_from_poses(D.poses, nd, h->g, true, h->x_bc, rects, s);
+    VisionArgs va;
+    va.orient = D.orient; va.conf = D.conf; va.dims = D.dims; va.bboxes = D.bboxes + n_all + ns; va.nb = nd;
+    va.cam = h->cam;
+    va.out = reinterpret_cast<VisionOut *>(blk + T.off_vout); va.poses_cam = D.poses;
+    va.out_dev = keep_dets ? T.dets_vout.get() : nullptr;
+    launch_vision(va, s);
+    ra.n = nd;
+    launch_rects_from_poses(ra, s);
     n_rects = nd;
     T.vision_ran = true;
     da.mode = kTickDetsVision; da.n_cand = nd; da.vout = T.dets_vout;
@@ -612,7 +631,8 @@ int gv_tick_enqueue(gv_handle h, const gv_tick_desc *d)
     if ((rc = enqueue_bbox_pose(h, n_all, true, thr_f, PoseBlock(blk + T.off_pose, n_all), none, D.poses,
                                 keep_dets ? T.dets_valid.get() : nullptr)))
       return rc;
-    launch_rects_from_poses(D.poses, n_all, h->g, true, h->x_bc, rects, s);
+    ra.n = n_all;
+    launch_rects_from_poses(ra, s);
     n_rects = n_all;
     T.pca_ran = true;
     da.mode = kTickDetsPca; da.n_cand = n_all; da.cam = D.poses; da.valid = T.dets_valid;

@@ -21,7 +21,7 @@
 //
 // Keys: bits 0..13 = cell inside the tile (ly << 7 | lx), bit 14 = clipped ray end (X2: end of
 // an out-of-map point's ray on the map border, counts as traversed), bit 15 unused.
-#include "gv_kernels.hpp"
+#include "gv_launch_frame.hpp"
 
 #include <cstdlib>
 

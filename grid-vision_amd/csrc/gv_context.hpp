@@ -14,7 +14,10 @@
 
 #include "gv_host_math.hpp"
 #include "gv_test_hooks.h"
-#include "gv_kernels.hpp"
+#include "gv_launch_frame.hpp"
+#include "gv_launch_pose.hpp"
+#include "gv_launch_planner.hpp"
+#include "gv_launch_match.hpp"
 #include "gv_resources.hpp"
 
 using namespace gv;
@@ -191,7 +194,7 @@ struct Tuning {
 };
 
 // Result block of the synchronous kNN / RANSAC / PCA calls and of the tick: pinned, coherent and device-mapped, written
-// by the call's last kernel; [0] = the sequence number of the last finished call (CallDone, gv_kernels.hpp), payload
+// by the call's last kernel; [0] = the sequence number of the last finished call (CallDone, gv_types.hpp), payload
 // from byte kHeader (gv_api_pose.hip)
 struct ResultBlock {
   static constexpr size_t kHeader = 64;
@@ -559,7 +562,7 @@ struct __attribute__((visibility("hidden"))) gv_context {
     DevBuf<long long> pca_acc;
     DevBuf<unsigned> pca_ext;
     DevBuf<unsigned> pca_ticket;
-    // cell buckets: counts, prefix, block offsets (BucketTable, gv_kernels.hpp); the counts and the ticket are zero between calls
+    // cell buckets: counts, prefix, block offsets (BucketTable, gv_launch_pose.hpp); the counts and the ticket are zero between calls
     DevBuf<uint32_t> cellcnt, cellpre, celloff;
     BucketTable buckets() const
     {

@@ -14,7 +14,7 @@
 #include <stddef.h>
 #include <math.h>
 
-#include "gv_kernels.hpp"
+#include "gv_types.hpp"
 #include "gv_wave.hpp"   // the wavefront primitives, for every kernel file that includes this
 
 namespace gv {
@@ -48,6 +48,14 @@ __device__ __forceinline__ void xform34(const Mat34f &m, float px, float py, flo
   ox = __fadd_rn(__fmul_rn(px, m.m[0]), __fadd_rn(__fmul_rn(py, m.m[1]), __fadd_rn(__fmul_rn(pz, m.m[2]), m.m[3])));
   oy = __fadd_rn(__fmul_rn(px, m.m[4]), __fadd_rn(__fmul_rn(py, m.m[5]), __fadd_rn(__fmul_rn(pz, m.m[6]), m.m[7])));
   oz = __fadd_rn(__fmul_rn(px, m.m[8]), __fadd_rn(__fmul_rn(py, m.m[9]), __fadd_rn(__fmul_rn(pz, m.m[10]), m.m[11])));
+}
+
+// |n.p + d| < thr with the oracle's operation order.  thr_f is the smallest float >= the fp64 threshold:
+// for a float f, f < thr_f <=> (double)f < thr (the reference compares the fp32 distance with the double).
+__device__ __forceinline__ bool plane_inlier_dev(const float4 &pl, float px, float py, float pz, float thr_f)
+{
+  const float d = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(pl.x, px), __fmul_rn(pl.y, py)), __fmul_rn(pl.z, pz)), pl.w);
+  return fabsf(d) < thr_f;   // NaN -> false
 }
 
 // (the exact getIndex, get_index, is gv_types.hpp's: one text for host and device)
@@ -212,6 +220,34 @@ __device__ __forceinline__ int first_bbox(const CamK &cam, const BBoxTest &t, fl
     }
   }
   return id;
+}
+
+// ---- how a call ends (CallDone, gv_types.hpp) ----
+// by ONE lane of every workgroup of the grid, after that lane's result stores (other lanes that stored: a system-scope
+// fence of their own, then a barrier, first).  The system-scope fences stay: the results go to the HOST, and stores
+// from different CUs reach it on different paths -- with only "my stores are acknowledged" (s_waitcnt vmcnt(0)) before
+// the ticket the host saw the flag ahead of another workgroup's payload in 4 calls of 10 (tools/result_block_soak.py,
+// profiles/r04/ticket_fence_ab.txt).  Tickets BETWEEN WORKGROUPS OF ONE KERNEL over device memory need no fence when
+// the data goes through agent-scope atomics (k_ransac_moments, k_pca_extent, k_cell_scan).
+__device__ __forceinline__ void call_done(const CallDone &d, unsigned n_wg)
+{
+  if (!d.flag) return;
+  __threadfence_system();
+  const unsigned t = __hip_atomic_fetch_add(d.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  if (t == n_wg - 1u) {
+    __hip_atomic_store(d.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence_system();
+    __hip_atomic_store(d.flag, d.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+// Such a ticket, by one lane of every workgroup once its stores have been acknowledged (s_waitcnt vmcnt(0) at the site):
+// true in the workgroup that arrives last, which leaves the counter zero for the next call
+__device__ __forceinline__ bool take_last_ticket(unsigned *ticket)
+{
+  const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool last = t == gridDim.x - 1u;
+  if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return last;
 }
 
 }  // namespace gv

@@ -20,6 +20,7 @@
 // below n_obj <= 128 = the LDS rows (a count read from the device, X14's fed set, is clamped to 0..128 first), table
 // entries only at (uint32_t)u with u < T <= the LDS bytes.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+#include "gv_launch_planner.hpp"
 #include "gv_device.hpp"
 #include "gv_dyn.hpp"
 

@@ -9,6 +9,7 @@
 // layers stay bit for bit what the oracle's update sequence produces.  The gather writes a scratch copy of the
 // layers and one copy kernel moves it back: the resident layer pointers (gv_device_layers) never change.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+#include "gv_launch_frame.hpp"
 #include "gv_device.hpp"
 
 #include <algorithm>

@@ -16,6 +16,7 @@
 //                    4 cells per lane where nx % 4 == 0, a cell per lane otherwise: the one difference between sizes.
 // Any nx, ny: cells past the map are computed and not stored; rows off the map hold no obstacle.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+#include "gv_launch_planner.hpp"
 #include "gv_device.hpp"
 
 namespace gv {

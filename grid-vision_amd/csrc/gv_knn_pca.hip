@@ -2,8 +2,8 @@
 // (buildKDTree + computeDepthForBoundingBoxes, src/cloud_detections.cpp:8-87).  The radius filter and the PCA
 // rectangle of the same reference file live in gv_cloudops.hip.
 // gfx950, wave64, built with -ffp-contract=off.
-#include "gv_kernels.hpp"
-#include "gv_wave.hpp"
+#include "gv_launch_pose.hpp"
+#include "gv_device.hpp"   // call_done; the wavefront primitives
 
 #include <float.h>
 #include <math.h>

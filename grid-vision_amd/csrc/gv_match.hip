@@ -25,6 +25,7 @@
 // Memory: a point rereads its window of up to 65 x 65 bytes for every yaw candidate; the costmap (4 MB at 2000 x 2000)
 // stays in L2 / Infinity Cache, neighbouring points of a scan share their windows' lines in the L1.
 // gfx950, wave64.
+#include "gv_launch_match.hpp"
 #include "gv_device.hpp"
 
 namespace gv {

@@ -40,6 +40,7 @@
 //   The word is cleared to all ones by a memset enqueued in front.  k_mppi_partial then reads x_k and m instead of the
 //   totals' difference (both arguments null without gamma: X11's text).
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+#include "gv_launch_planner.hpp"
 #include "gv_device.hpp"
 #include "gv_mppi.hpp"
 

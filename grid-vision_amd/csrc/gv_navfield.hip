@@ -46,6 +46,7 @@
 // LDS: the values in a 66 x 67 array (odd stride: the lanes of a row scan hit 32 different banks), the steps as uint16
 // (1 + 255 * 254 < 2^16) with a stride of 66 halfwords = 33 dwords, 26 KB in all.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+#include "gv_launch_planner.hpp"
 #include "gv_device.hpp"
 
 namespace gv {

@@ -35,6 +35,7 @@
 // k_nav_seeds_path: k_nav_seeds of gv_navfield.hip over the cells of a resident path, the count read from its record on
 // the device; launched for `cap` threads.
 // gfx950, wave64.
+#include "gv_launch_planner.hpp"
 #include "gv_device.hpp"
 
 namespace gv {

@@ -18,7 +18,7 @@
 // of its wedge from the table plus exact cross-multiplication tests on the (at
 // most two) buckets its slope interval only partly covers.  Everything is
 // integer arithmetic: bit-exact against the oracle's literal march.
-#include "gv_kernels.hpp"
+#include "gv_launch_frame.hpp"
 #include "gv_wave.hpp"
 
 #include <hip/hip_ext.h>
@@ -1203,10 +1203,9 @@ __global__ void __launch_bounds__(256) k_miss_to_i32(const unsigned *__restrict_
   }
 }
 
-void launch_miss_to_i32(const uint32_t *fN, const uint32_t *fT, int nx, int ny, int nx_pad, int ny_pad, int32_t *out,
-                        hipStream_t s)
+void launch_miss_to_i32(const MissToI32Args &a, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_miss_to_i32, dim3(2048), dim3(256), 0, s, fN, fT, nx, ny, nx_pad, ny_pad, out);
+  hipLaunchKernelGGL(k_miss_to_i32, dim3(2048), dim3(256), 0, s, a.freeN, a.freeT, a.nx, a.ny, a.nx_pad, a.ny_pad, a.out);
 }
 
 }  // namespace gv

@@ -27,6 +27,7 @@
 // minimum and a count: no order shows.  One 16-byte store of the result.  No ticket, no second kernel, no wait for
 // another workgroup.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+#include "gv_launch_planner.hpp"
 #include "gv_device.hpp"
 #include "gv_motion.hpp"
 

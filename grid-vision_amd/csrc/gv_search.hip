@@ -26,6 +26,7 @@
 //   k_search_record  one thread: the centre candidate joins, the record and the stats are written.
 // No kernel waits for another workgroup; only integer atomics; every store is a plain vector store from VGPRs.
 // gfx950, wave64.
+#include "gv_launch_match.hpp"
 #include "gv_device.hpp"
 
 namespace gv {

@@ -3,7 +3,7 @@
 // end bitmaps before the ray stage, free-cell bitmaps after it) are an all-to-all of equal slices
 // followed by a local OR of the `world` slices received -- these kernels are that OR, plus the
 // packing of the free-cell bitmaps by row band.  gfx950, wave64.
-#include "gv_kernels.hpp"
+#include "gv_launch_frame.hpp"
 
 #include <algorithm>
 

@@ -32,6 +32,8 @@
 //   128 = the rows of `tracks`, of the object table and of unm_list.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
 // Behind it: [EXTENSION] X15 k_tick_dets, which leaves a tick's detection list where k_track_update reads it.
+#include "gv_launch_planner.hpp"   // TrackArgs
+#include "gv_launch_pose.hpp"      // TickDetsArgs, RansacState: k_tick_dets belongs to the pose tick
 #include "gv_device.hpp"
 #include "gv_track.hpp"
 

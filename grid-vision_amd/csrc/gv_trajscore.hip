@@ -24,6 +24,7 @@
 // Every cell read is inside the map: an on-map pose has every vertex on the map and a line stays inside the bounding
 // box of its ends; the read is guarded all the same.
 // gfx950, wave64; every store below is a plain vector store from VGPRs.
+#include "gv_launch_planner.hpp"
 #include "gv_device.hpp"
 #include "gv_line.hpp"
 

@@ -1,10 +1,14 @@
 // gv_types.hpp -- POD parameter blocks shared by the host side (gv_api*.hip)
-// and the gfx950 kernels (gv_kernels.hip), passed by value as kernel arguments, and the few functions of the grid's
+// and the gfx950 kernels, passed by value as kernel arguments, and the few functions of the grid's
 // geometry that host and device evaluate from one text (GV_HD, as gv_line.hpp does).
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>   // float4 (BBoxTest)
+#endif
 
 #include "../../include/gridvision_hip.h"
 #include "gv_line.hpp"   // GV_HD
@@ -62,6 +66,16 @@ struct CamK {
   double k[9];   // row-major K
   int32_t W, H;  // image width / height
 };
+
+#if defined(__HIPCC__)   // (names a HIP vector type: the host twins that plain g++ compiles do not see it)
+// exact fp32 form of the bbox test + per-16x16-pixel-tile candidate masks (built on the device by
+// launch_bbox_prepare from the uploaded gv_bbox array)
+struct BBoxTest {
+  const float4 *bbox_f;                  // (x_min, y_min, x_max, y_max) as float thresholds
+  const unsigned long long *tile_mask;   // [tiles_y][tiles_x][mask_words]
+  int32_t tiles_x, tiles_y, mask_words;
+};
+#endif
 
 // sensor origin for the X2 ray-march
 struct RayOrigin {
@@ -145,6 +159,17 @@ struct VisionOut {
   float err;
   float dims[3];    // length, width, height (fp32 sums, :474-476)
   int32_t valid;    // 0 for classes the reference skips (:496-499)
+};
+
+// Completion of a synchronous call without a copy command or a runtime wait: the call's last kernel stores its
+// (small) results straight into pinned, device-mapped host memory, every workgroup then takes a ticket, and the
+// one whose ticket comes last publishes the call's sequence number in the block's first word -- the host spins on
+// that word (tools/micro/call_latency.hip: 8 us instead of 31 for copy + hipStreamSynchronize).  flag == nullptr:
+// plain device outputs, nothing published.  (The device side, call_done, is gv_device.hpp's.)
+struct CallDone {
+  unsigned *ticket = nullptr;   // device memory, zero between calls
+  unsigned *flag = nullptr;     // host-mapped
+  unsigned seq = 0;
 };
 
 // reference constants, include/grid_vision/occupancy_grid.hpp:25-31, occupancy_grid.cpp:182

@@ -13,11 +13,7 @@ PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libgridvision_hip.so")
-SOURCES = ["gv_api.hip", "gv_api_frame.hip", "gv_api_shard.hip", "gv_api_pose.hip", "gv_api_planner.hip", "gv_api_control.hip",
-           "gv_api_planner_host.hip", "gv_kernels.hip", "gv_binning.hip", "gv_raysector.hip", "gv_shard.hip", "gv_knn_pca.hip", "gv_cloudops.hip", "gv_gridmove.hip",
-           "gv_inflate.hip", "gv_trajscore.hip", "gv_navfield.hip", "gv_rollout.hip", "gv_mppi.hip", "gv_dynscore.hip",
-           "gv_track.hip", "gv_api_match.hip", "gv_api_match_host.hip", "gv_match.hip", "gv_api_path.hip", "gv_navpath.hip",
-           "gv_search.hip"]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))   # every .hip there is a translation unit of the library
 # -ffp-contract=off: cell indices must be bit-exact with the reference's separate
 # multiply/add roundings; no fast-math anywhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
@@ -57,7 +53,7 @@ def build(force: bool = False, lib: str = LIB, extra: list | None = None, obj_di
     if not os.path.exists(stamp) or open(stamp).read() != flags_now:
         force = True
     hdr_t = max(os.path.getmtime(h) for h in _headers())
-    srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    srcs = SOURCES
     cc = hipcc()
 
     def compile_one(src: str) -> str:

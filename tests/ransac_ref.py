@@ -1,4 +1,4 @@
-"""The RANSAC ground plane (k_ransac_count_all -> k_ransac_moments -> k_ransac_mask / k_pose_classify, gv_cloudops.hip)
+"""The RANSAC ground plane (k_ransac_count_all -> k_ransac_moments -> k_ransac_mask, gv_ransac.hip / k_pose_classify, gv_cloudops.hip)
 restated in numpy and Python floats, no C: the contract the device is held to byte for byte (tests/test_gpu_ransac.py)
 and that tests/test_ransac_host.py holds to oracle/ransac.c on every fixture.
 

@@ -155,7 +155,7 @@ def _limit(path, pattern):
 
 def test_path_table():
     import test_gpu_camera as T
-    fuse_max = _limit("gv_kernels.hpp", r"kBinBBoxLdsMax\s*=\s*(\d+)\s*\*\s*1024")
+    fuse_max = _limit("gv_launch_frame.hpp", r"kBinBBoxLdsMax\s*=\s*(\d+)\s*\*\s*1024")
     lds_max = _limit("gv_cloudops.hip", r"tab_bytes\s*<=\s*(\d+)\s*\*\s*1024")
 
     def fused(c, nb):

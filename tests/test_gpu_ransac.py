@@ -1,4 +1,4 @@
-"""The RANSAC ground plane (k_ransac_count_all -> k_ransac_moments -> k_ransac_mask, and the ground test fused into
+"""The RANSAC ground plane (k_ransac_count_all -> k_ransac_moments -> k_ransac_mask, gv_ransac.hip, and the ground test fused into
 k_pose_classify; gv_cloudops.hip) held to tests/ransac_ref.py with NO tolerance on the fixtures of tests/ransac_cases.py,
 which tests/test_ransac_host.py proves to reach their edges: through the test hook gv_test_ransac_state the winner's count
 as the counting pass left it (best_count), the sampled plane's 16 bytes, the inlier count of the moments pass (m, always

@@ -1,4 +1,4 @@
-"""The vision-orientation post-process (k_vision and qr_solve_4x3 of gv_kernels.hip) held bit for bit to the plain
+"""The vision-orientation post-process (k_vision and qr_solve_4x3 of gv_detections.hip) held bit for bit to the plain
 reference of tests/vision_ref.py, set by set: the test hook gv_test_vision_sets returns the solution and the residual
 of all 64 constraint sets of every box and the set the arg-min chose, so a wrong corner decode, a wrong pivot
 permutation or a wrong tie rule shows on the lane where it happens and not only when that lane wins.

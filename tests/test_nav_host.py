@@ -16,7 +16,7 @@ import nav_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GV_ERR_BAD_ARG = 1
-PASS_CAP = 40   # kNavPassCap of gv_kernels.hpp
+PASS_CAP = 40   # kNavPassCap of gv_launch_planner.hpp
 
 LAYOUT = r"""
 #include <stddef.h>

@@ -19,7 +19,7 @@ def test_constants_mirror_the_kernel_source():
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hpp = open(os.path.join(root, "grid-vision_amd", "csrc", "gv_kernels.hpp")).read()
+    hpp = open(os.path.join(root, "grid-vision_amd", "csrc", "gv_launch_frame.hpp")).read()
     hip = open(os.path.join(root, "grid-vision_amd", "csrc", "gv_binning.hip")).read()
 
     def const(txt, name):

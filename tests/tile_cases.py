@@ -15,7 +15,7 @@ expected result.  From a cloud's per-point oracle result it derives the key coun
 segment start w * chunk + sum of c(w, t') over t' < t, its residue r = start mod 8, whether it holds hit keys,
 clipped-end keys or both, the tile totals and k = clamp(ceil(total / 32768), 1, 8).
 
-THE CONSTANTS BELOW MIRROR csrc/gv_binning.hip AND csrc/gv_kernels.hpp AND MUST MOVE WITH THEM: bin_chunk_for, the
+THE CONSTANTS BELOW MIRROR csrc/gv_binning.hip AND csrc/gv_launch_frame.hpp AND MUST MOVE WITH THEM: bin_chunk_for, the
 tile side (kBinTile), kBinSplitKeys, kBinSplitMax, kTileThreads (descriptors per round), kInLaneKeys, the four aligned
 windows of 8 keys a lane loads first, and the tile numbering (jy >> 7) * tiles_x + (jx >> 7); clipped ends are counted
 in the tile of the border cell they end on.
@@ -34,7 +34,7 @@ import height_band_ref as ref
 import oracle_lib as ol
 import ray_cases as rc
 
-# ---- mirrors of gv_binning.hip / gv_kernels.hpp
+# ---- mirrors of gv_binning.hip / gv_launch_frame.hpp
 TILE_LOG = 7
 TILE = 1 << TILE_LOG
 SPLIT_KEYS, SPLIT_MAX = 32768, 8

@@ -1,6 +1,6 @@
 """Plain reference of the vision-orientation post-process (postProcessOutputs -> computeAlpha / computeThetaRay /
 calcLocation, src/vision_orientation.cpp:241-519) as the device runs it: k_vision and qr_solve_4x3 of
-grid-vision_amd/csrc/gv_kernels.hip, reached through gv_vision_post_process, GV_FRAME_VISION_ORIENT and
+grid-vision_amd/csrc/gv_detections.hip, reached through gv_vision_post_process, GV_FRAME_VISION_ORIENT and
 GV_TICK_VISION_ORIENT.  Test infrastructure only.
 
 Every multiply, add, subtract, divide and square root is one np.float32 operation on arrays of shape (boxes, 64), in
