@@ -87,6 +87,51 @@ int gv_test_tick_dets_host(const gv_lshape_pose *cam, const uint8_t *valid, int3
  * tile path or no binned frame has run.  No kernel of its own (tests/test_gpu_tile_pass.py). */
 int gv_test_end_bitmaps(gv_handle h, uint32_t *hitN, uint32_t *clipN, uint32_t *hitT, uint32_t *clipT,
                         int32_t *nxw, int32_t *nyw, int32_t *nx_pad, int32_t *ny_pad);
+/* gv_test_wave: one helper of csrc/gv_wave.hpp on the device, lane by lane (k_test_wave, csrc/gv_test_wave.hip: the one
+ * kernel that exists for a test).  One wavefront per 64 inputs, `threads` (64, 256 or 1024) to a workgroup: lane l of wave
+ * w reads in[w * 64 + l], runs helper `op` inside `if ((active[w] >> l) & 1)` and stores its own result to
+ * out[w * 64 + l]; an inactive lane stores GV_TEST_WAVE_INACTIVE.  No result is ever an address or an index.  Synchronous
+ * on gv_stream(h), buffers of its own, freed before it returns; 1 <= n_waves <= 4096.  *counter_out: the final value of
+ * the one uint32 counter the append ops add to (zeroed before the launch; 0 for every other op).
+ * 32-bit ops take the low word of `in` and store their result zero-extended; fp64 ops take and store the bits.  The ops:
+ *   SCAN_ADD / _MAX / _MIN, REDUCE_ADD / _MAX / _MIN   wave_scan<Op>, wave_reduce<Op>
+ *   SHIFT_DOWN_1 / _2 / _4 / _8      wave_shift_down<H>(v, fill = (unsigned)arg)
+ *   GROUP_SUM_8 / _16                group_sum<LANES>((int)v); whole aligned groups of LANES lanes may be inactive
+ *   MIN_KEY, MAX64, SUM64            wave_min_key, wave_max64, wave_sum64 over the 64 bits
+ *   SUM_I32 / _U32, MAX_I32 / _U32   wave_sum<T>, wave_max<T>
+ *   SHFL_XOR64                       shfl_xor64(v, o = arg), 1 <= arg <= 63
+ *   BUTTERFLY, TREE_SHFL             wave_butterfly, wave_tree_sum_shfl: every lane's bits (the header promises lane 0's)
+ *   DPP_F64_SHL_1 / _2 / _4 / _8     dpp_f64<row_shl:k>
+ *   RANK_LEADER                      m = __ballot(in & 1): wave_leader(m) in the high word, wave_rank(m, l) in the low one;
+ *                                    GV_TEST_WAVE_SKIPPED in the active lanes of a wave whose m is 0
+ *   BCAST_U64 / _I32 / _F64          wave_bcast<T>(v, lane = arg), 0 <= arg <= 63: unsigned long long, int, double
+ *   APPEND, APPEND_ALL               m = __ballot(in & 1); a wave whose m is 0 skips the call (GV_TEST_WAVE_SKIPPED), else
+ *                                    base = wave_append / wave_append_all(counter, m, l) and every active lane stores base
+ *                                    in the high word, base + wave_rank(m, l) in the low one
+ * GV_ERR_BAD_ARG, and nothing launched: a null pointer, n_waves, threads, op or arg out of range; an active mask other
+ * than all 64 lanes for any op but GROUP_SUM_*, RANK_LEADER, BCAST_* and APPEND* (gv_wave.hpp defines the DPP scans, the
+ * butterflies and the trees for a full wavefront only); GROUP_SUM_* with a group of LANES lanes partly active; BCAST_* with lane `arg` inactive in some wave; APPEND_ALL with lane 0 inactive
+ * in some wave (tests/test_gpu_wave.py). */
+typedef enum gv_test_wave_op {
+  GV_TEST_WAVE_SCAN_ADD = 0, GV_TEST_WAVE_SCAN_MAX, GV_TEST_WAVE_SCAN_MIN,
+  GV_TEST_WAVE_REDUCE_ADD, GV_TEST_WAVE_REDUCE_MAX, GV_TEST_WAVE_REDUCE_MIN,
+  GV_TEST_WAVE_SHIFT_DOWN_1, GV_TEST_WAVE_SHIFT_DOWN_2, GV_TEST_WAVE_SHIFT_DOWN_4, GV_TEST_WAVE_SHIFT_DOWN_8,
+  GV_TEST_WAVE_GROUP_SUM_8, GV_TEST_WAVE_GROUP_SUM_16,
+  GV_TEST_WAVE_MIN_KEY,
+  GV_TEST_WAVE_SUM_I32, GV_TEST_WAVE_SUM_U32, GV_TEST_WAVE_MAX_I32, GV_TEST_WAVE_MAX_U32,
+  GV_TEST_WAVE_MAX64, GV_TEST_WAVE_SUM64, GV_TEST_WAVE_SHFL_XOR64,
+  GV_TEST_WAVE_BUTTERFLY, GV_TEST_WAVE_TREE_SHFL,
+  GV_TEST_WAVE_DPP_F64_SHL_1, GV_TEST_WAVE_DPP_F64_SHL_2, GV_TEST_WAVE_DPP_F64_SHL_4, GV_TEST_WAVE_DPP_F64_SHL_8,
+  GV_TEST_WAVE_RANK_LEADER,
+  GV_TEST_WAVE_BCAST_U64, GV_TEST_WAVE_BCAST_I32, GV_TEST_WAVE_BCAST_F64,
+  GV_TEST_WAVE_APPEND, GV_TEST_WAVE_APPEND_ALL,
+  GV_TEST_WAVE_OPS
+} gv_test_wave_op;
+#define GV_TEST_WAVE_INACTIVE 0xA5A5A5A5A5A5A5A5ull
+#define GV_TEST_WAVE_SKIPPED 0x5A5A5A5A5A5A5A5Aull
+int gv_test_wave(gv_handle h, int32_t op, int32_t arg, int32_t threads /* 64, 256 or 1024 */,
+                 const uint64_t *in /* n_waves*64 */, const uint64_t *active /* n_waves */, int64_t n_waves,
+                 uint64_t *out /* n_waves*64 */, uint32_t *counter_out);
 #ifdef __cplusplus
 }
 #endif

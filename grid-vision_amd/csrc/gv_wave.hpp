@@ -10,6 +10,12 @@
 // Where the result lands: the xor butterflies, wave_reduce, group_sum and wave_min_key leave it in EVERY lane; wave_scan
 // leaves the reduction in lane 63 only; the fixed-order trees in lane 0 only (the other lanes hold partial sums).  The DPP
 // and the shuffle form of one step are different machine code: a kernel's choice was measured at that kernel.
+// Who must be active at the call ("ACTIVE:" at each family): a cross-lane read of a lane that EXEC has switched off is not
+// defined here -- a lane that returned early, sits in the other arm of a divergent branch, or left a loop with a
+// lane-dependent trip count.  A ragged tail is therefore predicated (`v = i < n ? x[i] : identity`) above these helpers,
+// never `if (i >= n) return;`.  Every contract below is held lane by lane by tests/test_gpu_wave.py, through the probe
+// kernel of gv_test_wave.hip; that test refuses a partial wavefront for every helper marked "all 64", and runs the others
+// under the partial masks their line allows.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +25,7 @@ namespace gv {
 
 // ---- DPP: src of the lane the control word CTRL names; a lane the row / bank masks leave out keeps `old`, a lane whose
 // source does not exist reads `old` too, or 0 with BOUND_CTRL
+// ACTIVE: the lane and its source lane; the helpers built on them say what that means for each
 template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF, bool BOUND_CTRL = false>
 __device__ __forceinline__ unsigned dpp(unsigned old, unsigned src)
 {
@@ -40,6 +47,7 @@ struct OpAdd { static constexpr unsigned id = 0u; __device__ static unsigned f(u
 struct OpMax { static constexpr unsigned id = 0u; __device__ static unsigned f(unsigned a, unsigned b) { return a > b ? a : b; } };
 struct OpMin { static constexpr unsigned id = 0xFFFFFFFFu; __device__ static unsigned f(unsigned a, unsigned b) { return a < b ? a : b; } };
 // inclusive scan over the 64 lanes (lane 63 ends up with the reduction); wave_reduce: that reduction, in every lane
+// ACTIVE: all 64 (wave_scan, wave_reduce, wave_shift_down, wave_min_key)
 template <class Op>
 __device__ __forceinline__ unsigned wave_scan(unsigned v)
 {
@@ -62,6 +70,8 @@ __device__ __forceinline__ unsigned wave_shift_down(unsigned v, unsigned fill)
   return v;
 }
 // every lane of a group of LANES consecutive lanes (8 or 16, aligned) ends with the group's sum
+// ACTIVE: all LANES lanes of the group together; other groups of the wavefront may be off (k_radius_sorted: a point's
+// lanes leave its candidate loop together, the points of a wavefront at different times)
 template <int LANES>
 __device__ __forceinline__ int group_sum(int v)
 {
@@ -93,6 +103,7 @@ __device__ __forceinline__ unsigned long long wave_min_key(unsigned long long v)
 // ---- xor butterflies: v op= (v of lane ^ o), o = 32 .. 1, by shuffles; the result in every lane.  Integer sums and maxima
 // only: the order of the operands differs from lane to lane.  (The arg-reductions and the loops that carry two reductions
 // at once are this butterfly written out at their kernels: behind a shared loop they compiled otherwise)
+// ACTIVE: all 64 (every lane is some lane's partner at every step)
 template <class T>
 __device__ __forceinline__ T wave_sum(T v)   // int or unsigned
 {
@@ -130,6 +141,7 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
 // additions, the oracle's (tree_sum64, oracle/ransac.c).  Two forms of one tree: lane 0 of both holds the same value in the
 // same rounding order; which one a kernel uses was decided by measurement at that kernel.  DPP form: only lanes below `off`
 // matter at each step, so the four in-row steps are DPP shifts (no LDS traffic); the other two go through the permute network.
+// ACTIVE: all 64 (a lane without a value contributes +0.0, as the oracle's tree pads)
 __device__ __forceinline__ double wave_butterfly(double v)
 {
   v = v + __shfl_down(v, 32);
@@ -149,6 +161,7 @@ __device__ __forceinline__ double wave_tree_sum_shfl(double v)   // shuffle form
 
 // ---- wave-aggregated append: mask = __ballot(this lane appends), not 0.  rank: the lane's place among the appending lanes;
 // leader: the first of them; bcast: lane `lane`'s v, in every lane.
+// ACTIVE: any subset of the lanes, the same at the __ballot and at the call; wave_bcast's source lane is one of them
 __device__ __forceinline__ unsigned wave_rank(unsigned long long m, int lane) { return (unsigned)__popcll(m & ((1ull << lane) - 1ull)); }
 __device__ __forceinline__ int wave_leader(unsigned long long mask) { return __ffsll((long long)mask) - 1; }
 template <class T> __device__ __forceinline__ T wave_bcast(T v, int lane) { return __shfl(v, lane, 64); }
@@ -162,6 +175,7 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t *counter, unsigned long
   return (uint32_t)wave_bcast((int)base, leader);
 }
 // The same where lane 0 is known to be active: lane 0 adds, the base comes back by readfirstlane, not the permute network.
+// ACTIVE: any subset that holds lane 0 (with lane 0 off nobody adds, and the first active lane's zero comes back)
 __device__ __forceinline__ unsigned wave_append_all(unsigned *counter, unsigned long long mask, int lane)
 {
   unsigned base = 0;

@@ -107,6 +107,16 @@ assert SEARCH_STATS_DTYPE.itemsize == 32
 # every symbol include/gridvision_hip_search.h declares
 SEARCH_SYMBOLS = ["gv_set_search_config", "gv_match_search_async", "gv_match_search", "gv_match_search_host"]
 
+# gv_test_wave_op (csrc/gv_test_hooks.h), GV_TEST_WAVE_ dropped, in the enum's order; and the hook's two sentinels
+WAVE_OPS = ["SCAN_ADD", "SCAN_MAX", "SCAN_MIN", "REDUCE_ADD", "REDUCE_MAX", "REDUCE_MIN",
+            "SHIFT_DOWN_1", "SHIFT_DOWN_2", "SHIFT_DOWN_4", "SHIFT_DOWN_8", "GROUP_SUM_8", "GROUP_SUM_16", "MIN_KEY",
+            "SUM_I32", "SUM_U32", "MAX_I32", "MAX_U32", "MAX64", "SUM64", "SHFL_XOR64", "BUTTERFLY", "TREE_SHFL",
+            "DPP_F64_SHL_1", "DPP_F64_SHL_2", "DPP_F64_SHL_4", "DPP_F64_SHL_8", "RANK_LEADER",
+            "BCAST_U64", "BCAST_I32", "BCAST_F64", "APPEND", "APPEND_ALL"]
+WAVE_INACTIVE = 0xA5A5A5A5A5A5A5A5
+WAVE_SKIPPED = 0x5A5A5A5A5A5A5A5A
+WAVE_ALL_LANES = 0xFFFFFFFFFFFFFFFF
+
 STAGES = ("detections", "points", "ray_ends", "ray_march", "finalize")
 
 # every symbol include/gridvision_hip.h declares
@@ -1748,6 +1758,20 @@ class GridVisionHIP:
         self._ck(self._lib.gv_test_end_bitmaps(self._h, _ptr(hn), _ptr(cn), _ptr(ht), _ptr(ct), *[C.byref(v) for v in g]),
                  "gv_test_end_bitmaps")
         return hn, cn, ht, ct, (nxw, nyw, nx_pad, ny_pad)
+
+    def test_wave(self, op, values, active=None, arg=0, threads=256):
+        """test hook (csrc/gv_test_hooks.h): helper `op` (a name of WAVE_OPS or its number) of csrc/gv_wave.hpp over
+        `values`, (n_waves, 64) uint64, under the lane masks `active` ((n_waves,) uint64; None: every lane).  Returns
+        (out (n_waves, 64) uint64, the append counter's final value)."""
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        assert v.ndim == 2 and v.shape[1] == 64
+        a = np.full(len(v), WAVE_ALL_LANES, np.uint64) if active is None else np.ascontiguousarray(active, dtype=np.uint64)
+        assert a.shape == (len(v),)
+        out, counter = np.zeros(v.shape, np.uint64), C.c_uint32(0xFFFFFFFF)
+        self._ck(self._lib.gv_test_wave(self._h, C.c_int32(WAVE_OPS.index(op) if isinstance(op, str) else op), C.c_int32(arg),
+                                        C.c_int32(threads), _ptr(v), _ptr(a), C.c_int64(len(v)), _ptr(out), C.byref(counter)),
+                 "gv_test_wave")
+        return out, counter.value
 
     # ---- multi-GPU (RCCL inside the library)
     @staticmethod
