@@ -1,7 +1,7 @@
-// gv_generic.hip -- gfx950 (CDNA4, wave64) kernels of the generic frame path: the points pass with its LDS hit cache,
-// the literal ray march (compact + march) and the cell-by-cell grid finalise.  Any grid shape takes this path, and so
-// does GV_RAY_IMPL=simple; the production frame on a tile-aligned grid goes through gv_binning.hip and
-// gv_raysector.hip instead.
+// gv_generic.hip -- gfx950 (CDNA4, wave64) kernels of the generic frame path: the points pass with its LDS hit cache
+// and the literal ray march (compact + march); its grid pass, cell by cell, is in gv_gridpass.hip.  Any grid shape
+// takes this path, and so does GV_RAY_IMPL=simple; the production frame on a tile-aligned grid goes through
+// gv_binning.hip and gv_raysector.hip instead.
 //
 // Built with -ffp-contract=off: the reference arithmetic keeps separate
 // multiply/add roundings (PCL's SSE transform, grid_map's getIndex), and cell
@@ -227,134 +227,6 @@ void launch_ray_march(const RayMarchArgs &a, hipStream_t s)
 {
   if (!a.org.valid) return;
   hipLaunchKernelGGL(k_ray_march, dim3(256 * 8), dim3(256), 0, s, a.list, a.count, a.g, a.org, a.miss, a.stats);
-}
-
-// ---------------------------------------------------------- grid finalise --
-// One pass over the cells (A7/A8/A9/A18 + the X2 rule):
-//   l += decay (:19/:69); l += 0.85f per covering rectangle, in object order (:175-182);
-//   hits>0 -> l += 1.2f, else miss>0 -> l += -0.4f  [EXTENSION];
-//   clamp (:21-22); occupancy = 1/(1+exp(-l)) (:25-30); int8 = (int8)(clamp01(p)*100)
-//   stored at data[G-1-cell] (toOccupancyGrid).
-__device__ __forceinline__ float sigmoid_ref(float l)
-{
-  // exp in fp64 rounded once: the correctly rounded expf (on the host it agrees on all fp32 inputs in [-3.6, 2];
-  // glibc's expf, which the oracle calls, is one ulp off on 118,468 of them, tests/test_gpu_grid_pass.py)
-  const float e = (float)exp((double)(-l));
-  return 1.0f / (1.0f + e);
-}
-
-__device__ __forceinline__ int8_t pack_i8(float p)
-{
-  float v = (p - 0.0f) / (1.0f - 0.0f);
-  if (isnan(v)) v = -1.0f;
-  else {
-    float c = v < 0.0f ? 0.0f : v;
-    c = c > 1.0f ? 1.0f : c;
-    v = 0.0f + c * 100.0f;
-  }
-  return (int8_t)v;
-}
-
-__device__ __forceinline__ float cell_update(float l, int nrect_hits, bool counts, int h, int m)
-{
-  l = l + kLogOddsDecay;
-  for (int k = 0; k < nrect_hits; ++k) l = l + kRectIncrement;
-  if (counts) {
-    if (h > 0) l = l + kLogOddsOccupied;
-    else if (m > 0) l = l + kLogOddsFree;
-  }
-  l = (l < kMinLogOdds) ? kMinLogOdds : l;
-  l = (l > kMaxLogOdds) ? kMaxLogOdds : l;
-  return l;
-}
-
-template <bool COUNTS>
-__global__ void __launch_bounds__(256) k_finalize_vec4(FinalizeArgs a)
-{
-  // requires nx % 4 == 0 and band edges % 4 == 0: the 4 cells of a thread share a row
-  const int64_t q0 = a.cell_begin >> 2, q1 = a.cell_end >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t q = q0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < q1; q += stride) {
-    const int64_t c = q << 2;
-    const int iy = (int)(c / a.g.nx), ix = (int)(c - (int64_t)iy * a.g.nx);
-    float4 l4 = *reinterpret_cast<const float4 *>(a.log_odds + c);
-    int4 h4 = make_int4(0, 0, 0, 0);
-    uint32_t m4 = 0;
-    if (COUNTS) {
-      h4 = *reinterpret_cast<const int4 *>(a.hits + c);
-      m4 = *reinterpret_cast<const uint32_t *>(a.miss + c);
-    }
-    int k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-    for (int r = 0; r < a.n_rects; ++r) {
-      const Rect R = a.rects[r];
-      if (R.valid && iy >= R.y0 && iy <= R.y1 && ix + 3 >= R.x0 && ix <= R.x1) {
-        k0 += (ix >= R.x0 && ix <= R.x1);
-        k1 += (ix + 1 >= R.x0 && ix + 1 <= R.x1);
-        k2 += (ix + 2 >= R.x0 && ix + 2 <= R.x1);
-        k3 += (ix + 3 >= R.x0 && ix + 3 <= R.x1);
-      }
-    }
-    l4.x = cell_update(l4.x, k0, COUNTS, h4.x, (int)(m4 & 0xffu));
-    l4.y = cell_update(l4.y, k1, COUNTS, h4.y, (int)((m4 >> 8) & 0xffu));
-    l4.z = cell_update(l4.z, k2, COUNTS, h4.z, (int)((m4 >> 16) & 0xffu));
-    l4.w = cell_update(l4.w, k3, COUNTS, h4.w, (int)(m4 >> 24));
-    float4 p4;
-    p4.x = sigmoid_ref(l4.x); p4.y = sigmoid_ref(l4.y); p4.z = sigmoid_ref(l4.z); p4.w = sigmoid_ref(l4.w);
-    *reinterpret_cast<float4 *>(a.log_odds + c) = l4;
-    *reinterpret_cast<float4 *>(a.occupancy + c) = p4;
-    // data[G-1-cell] (data_entry, gv_types.hpp, of the linear cell): cells c..c+3 land at G-4-c .. G-1-c in reverse order
-    const uint32_t packed = ((uint32_t)(uint8_t)pack_i8(p4.w)) | ((uint32_t)(uint8_t)pack_i8(p4.z) << 8)
-                            | ((uint32_t)(uint8_t)pack_i8(p4.y) << 16) | ((uint32_t)(uint8_t)pack_i8(p4.x) << 24);
-    *reinterpret_cast<uint32_t *>(a.occ_i8 + ((int64_t)a.g.G - 4 - c)) = packed;
-    if (COUNTS && a.zero_counts) {
-      *reinterpret_cast<int4 *>(a.hits + c) = make_int4(0, 0, 0, 0);
-      *reinterpret_cast<uint32_t *>(a.miss + c) = 0u;
-      *reinterpret_cast<uint32_t *>(a.clip_end + c) = 0u;
-    }
-  }
-}
-
-template <bool COUNTS>
-__global__ void __launch_bounds__(256) k_finalize_scalar(FinalizeArgs a)
-{
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t c = a.cell_begin + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < a.cell_end; c += stride) {
-    const int iy = (int)(c / a.g.nx), ix = (int)(c - (int64_t)iy * a.g.nx);
-    int k = 0;
-    for (int r = 0; r < a.n_rects; ++r) {
-      const Rect R = a.rects[r];
-      k += (R.valid && iy >= R.y0 && iy <= R.y1 && ix >= R.x0 && ix <= R.x1);
-    }
-    const int h = COUNTS ? a.hits[c] : 0;
-    const int m = COUNTS ? (int)a.miss[c] : 0;
-    const float l = cell_update(a.log_odds[c], k, COUNTS, h, m);
-    const float p = sigmoid_ref(l);
-    a.log_odds[c] = l;
-    a.occupancy[c] = p;
-    a.occ_i8[(int64_t)a.g.G - 1 - c] = pack_i8(p);
-    if (COUNTS && a.zero_counts) {
-      a.hits[c] = 0;
-      a.miss[c] = 0;
-      a.clip_end[c] = 0;
-    }
-  }
-}
-
-void launch_finalize(const FinalizeArgs &a, hipStream_t s)
-{
-  const int64_t ncell = a.cell_end - a.cell_begin;
-  if (ncell <= 0) return;
-  const bool vec = (a.g.nx % 4 == 0) && (a.cell_begin % 4 == 0) && (a.cell_end % 4 == 0);
-  const bool counts = a.hits != nullptr;
-  if (vec) {
-    const uint32_t blocks = (uint32_t)std::min<int64_t>((ncell / 4 + 255) / 256, (int64_t)256 * 16);
-    if (counts) hipLaunchKernelGGL(k_finalize_vec4<true>, dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_finalize_vec4<false>, dim3(blocks), dim3(256), 0, s, a);
-  } else {
-    const uint32_t blocks = (uint32_t)std::min<int64_t>((ncell + 255) / 256, (int64_t)256 * 16);
-    if (counts) hipLaunchKernelGGL(k_finalize_scalar<true>, dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_finalize_scalar<false>, dim3(blocks), dim3(256), 0, s, a);
-  }
 }
 
 }  // namespace gv

@@ -415,15 +415,17 @@ struct SectorTuning {
 };
 
 struct SectorPlan {
-  // one bit per precondition of k_ray_sectors (line numbers: gv_raysector.hip)
+  // one bit per precondition of k_ray_sectors (names: the kernel's own lambdas and variables, gv_raysector.hip)
   enum : uint32_t {
-    kWideColumn = 1u << 0,      // a column of a sector is one 32-bit word of cell bits (w, line 381; wm, lines 396 and 418)
-    kSectorCount = 1u << 1,     // S <= 2^12: S << log2m stays in 32 bits (SM, line 461)
-    kWorkgroups = 1u << 2,      // wg_base[] is 16 bits wide (line 148); one statistics slot per workgroup (line 168)
-    kLog2m = 1u << 3,           // M = 1 << log2m <= 512 slope buckets: eight blocks of 64 (s_blkmax[8], line 195); 4 is the knob's least
-    kCap = 1u << 4,             // cap >= 2048: the ends of one wavefront's 64 columns fit a chunk (line 974); <= 65536: an
-                                // overflow entry holds a 16-bit index into raw (L.over, sector_lds_layout)
-    kMarksWords = 1u << 5,      // marks[]: one word per wedge column 0 .. imax (line 221); even: what follows it stays 8-byte aligned
+    kWideColumn = 1u << 0,      // a column of a sector is one 32-bit word of cell bits (w = bhi - blo + 1 of col_bounds and
+                                // the mask wm made of it, in scan_columns and in scan_row)
+    kSectorCount = 1u << 1,     // S <= 2^12: S << log2m stays in 32 bits (SM, the lattice-gap buckets)
+    kWorkgroups = 1u << 2,      // wg_base[] is 16 bits wide and there is one statistics slot per workgroup (bid and stat_slot in
+                                // the dispatch-order decode at the top of k_ray_sectors)
+    kLog2m = 1u << 3,           // M = 1 << log2m <= 512 slope buckets: eight blocks of 64 (s_blkmax[8]); 4 is the knob's least
+    kCap = 1u << 4,             // cap >= 2048: the ends of one wavefront's 64 columns fit a chunk (next_group's per-wavefront
+                                // groups); <= 65536: an overflow entry holds a 16-bit index into raw (L.over, sector_lds_layout)
+    kMarksWords = 1u << 5,      // marks[]: one word per wedge column 0 .. imax (cleared up to oc.imax); even: what follows it stays 8-byte aligned
     kLds = 1u << 6,             // sector_lds_layout fits the LDS of a CU
   };
   struct Workgroup {
@@ -557,8 +559,8 @@ struct SectorPlan {
                                 : "";
   }
 
-  // Host twin of the kernel's decode of its place in the dispatch order (k_ray_sectors, gv_raysector.hip lines 147-168,
-  // which stays a device copy): helpers first, then the octants with the longest wedges, and inside an octant the
+  // Host twin of the kernel's decode of its place in the dispatch order (the dispatch-order decode at the top of
+  // k_ray_sectors, gv_raysector.hip, which stays a device copy): helpers first, then the octants with the longest wedges, and inside an octant the
   // sectors next to the slopes 0, 1/2, 1 first.  idle: the odd helper of a one-sector octant, which returns at once.
   Workgroup workgroup(int bid_all) const
   {

@@ -1,6 +1,7 @@
 // gv_launch_frame.hpp -- launchers of the frame path's kernels: the generic path (gv_generic.hip), the rectangles
-// (gv_detections.hip), the tile path (gv_binning.hip, gv_raysector.hip), ego motion (gv_gridmove.hip), the shard helpers
-// (gv_shard.hip) and the cloud / layer movers (gv_cloudio.hip).  gv_api.hip, gv_api_frame.hip and gv_api_shard.hip call them.
+// (gv_detections.hip), the tile path (gv_binning.hip, gv_raysector.hip), the grid pass of both (gv_gridpass.hip), ego motion
+// (gv_gridmove.hip), the shard helpers (gv_shard.hip) and the cloud / layer movers (gv_cloudio.hip).  gv_api.hip,
+// gv_api_frame.hip and gv_api_shard.hip call them.
 // Every launcher only enqueues work on `s`; none allocates or synchronises.
 #pragma once
 
@@ -114,20 +115,6 @@ struct RayMarchArgs {
 };
 void launch_ray_march(const RayMarchArgs &a, hipStream_t s);
 
-struct FinalizeArgs {
-  GridParams g;
-  float *log_odds, *occupancy;
-  int8_t *occ_i8;          // OccupancyGrid.data order (reversed linear)
-  const Rect *rects;
-  int32_t n_rects;
-  int32_t *hits;           // null => no hit/miss rule (plain updateMap)
-  uint8_t *miss;
-  uint8_t *clip_end;
-  bool zero_counts;        // clear hits/miss/clip_end for the next frame
-  int64_t cell_begin, cell_end;   // band of cells to finalise ([0,G) on one GPU)
-};
-void launch_finalize(const FinalizeArgs &a, hipStream_t s);
-
 void launch_fill_f32(float *p, float v, size_t n, hipStream_t s);
 
 // [EXTENSION] X3 ego motion (gv_gridmove.hip): the three layers resampled under the planar transform S into a scratch
@@ -207,7 +194,7 @@ struct BinTileArgs {
 // n_helpers >= n / split_keys extra workgroups serve the shares 1.. of crowded tiles
 void launch_bin_tiles(const BinTileArgs &a, uint32_t n_helpers, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
-// ---- sector/gather ray stage + tile grid pass (gv_raysector.hip) ----
+// ---- sector/gather ray stage (gv_raysector.hip) ----
 struct SectorArgs {
   GridParams g;
   RayOrigin org;
@@ -241,6 +228,21 @@ struct SectorLaunch {
   int total_workgroups;
 };
 bool launch_ray_sectors(const SectorArgs &a, const SectorLaunch &l, hipStream_t s, hipEvent_t done = nullptr, hipEvent_t t0 = nullptr);
+
+// ---- grid pass: the map update rule over the cells, generic and tile form (gv_gridpass.hip) ----
+struct FinalizeArgs {
+  GridParams g;
+  float *log_odds, *occupancy;
+  int8_t *occ_i8;          // OccupancyGrid.data order (reversed linear)
+  const Rect *rects;
+  int32_t n_rects;
+  int32_t *hits;           // null => no hit/miss rule (plain updateMap)
+  uint8_t *miss;
+  uint8_t *clip_end;
+  bool zero_counts;        // clear hits/miss/clip_end for the next frame
+  int64_t cell_begin, cell_end;   // band of cells to finalise ([0,G) on one GPU)
+};
+void launch_finalize(const FinalizeArgs &a, hipStream_t s);
 
 struct FinalizeTileArgs {
   GridParams g;

@@ -1,5 +1,5 @@
-// gv_raysector.hip -- [EXTENSION] X2 free-space ray-march, sector/gather form,
-// plus the tile-based grid pass that consumes it.  gfx950, wave64.
+// gv_raysector.hip -- [EXTENSION] X2 free-space ray-march, sector/gather form.
+// gfx950, wave64.  (The tile grid pass that consumes its bitmaps: gv_gridpass.hip.)
 //
 // Why not march every ray: 1M rays x ~860 steps is ~6.5e8 cell visits per frame.
 // grid_map::LineIterator's integer stepping has a closed form: a ray from the
@@ -1042,170 +1042,6 @@ bool launch_ray_sectors(const SectorArgs &a, const SectorLaunch &l, hipStream_t 
   return l.ch == 4   ? launch_sectors_ch<4>(a, grid, l.lds_bytes, s, done, t0)
          : l.ch == 8 ? launch_sectors_ch<8>(a, grid, l.lds_bytes, s, done, t0)
                      : launch_sectors_ch<16>(a, grid, l.lds_bytes, s, done, t0);
-}
-
-// ------------------------------------------------------ tile grid pass -----
-__device__ __forceinline__ float sigmoid_ref_t(float l)
-{
-  // fp64 exp rounded once: the correctly rounded expf (glibc's, which the oracle calls, is one ulp off on 118,468
-  // fp32 inputs in [-3.6, 2]; tests/test_gpu_grid_pass.py).  An fp32 expf measured +2 % on the frame, round 3.
-  const float e = (float)exp((double)(-l));
-  return 1.0f / (1.0f + e);
-}
-
-__device__ __forceinline__ unsigned pack_i8_t(float p)
-{
-  float v = (p - 0.0f) / (1.0f - 0.0f);
-  if (isnan(v)) v = -1.0f;
-  else {
-    float c = v < 0.0f ? 0.0f : v;
-    c = c > 1.0f ? 1.0f : c;
-    v = 0.0f + c * 100.0f;
-  }
-  return (unsigned)(unsigned char)(signed char)v;
-}
-
-__device__ __forceinline__ float cell_update_t(float l, int k, bool counts, bool hit, bool miss)
-{
-  l = l + kLogOddsDecay;
-  for (int r = 0; r < k; ++r) l = l + kRectIncrement;
-  if (counts) {
-    if (hit) l = l + kLogOddsOccupied;
-    else if (miss) l = l + kLogOddsFree;
-  }
-  l = (l < kMinLogOdds) ? kMinLogOdds : l;
-  l = (l > kMaxLogOdds) ? kMaxLogOdds : l;
-  return l;
-}
-
-// One 64x64 tile per workgroup.  Requires nx % 4 == 0.  Per cell: 4 B log-odds in, 4 + 4 + 1 B out (nothing out
-// for a tile row that did not change, unless a.dense); hit and free-space flags come from the bitmaps (N: one word per 32 cells of a row; T: bits run
-// along y, a thread's four cells are four consecutive words = one 16-byte load).  Nothing is cleared
-// here: the binning tile pass rewrites / zeroes every bitmap word of the set it is about to use.
-#ifndef GV_FIN_ROWS
-#define GV_FIN_ROWS 64
-#endif
-template <bool COUNTS>
-__global__ void __launch_bounds__(256) k_finalize_tiles(FinalizeTileArgs a)
-{
-  __shared__ Rect s_rects[64];
-  __shared__ int s_nr;
-  constexpr int kRows = GV_FIN_ROWS;   // rows of the grid per workgroup (64 cells wide): 16 per pass
-  const int x0 = blockIdx.x * 64, y0 = a.y_begin + blockIdx.y * kRows;
-  const int tid = threadIdx.x;
-  GV_TL_BEGIN(a.tl);
-  if (tid == 0) s_nr = 0;
-  __syncthreads();
-  // rectangles that touch this tile (object order must be kept only for equal cells:
-  // all adds are the same constant, so the count is what matters)
-  for (int r = tid; r < a.n_rects; r += 256) {
-    const Rect R = a.rects[r];
-    if (R.valid && R.y1 >= y0 && R.y0 <= y0 + kRows - 1 && R.x1 >= x0 && R.x0 <= x0 + 63) {
-      const int k = atomicAdd(&s_nr, 1);
-      if (k < 64) s_rects[k] = R;
-    }
-  }
-  __syncthreads();
-  const int nr = min(s_nr, 64);
-  const bool overflow = s_nr > 64;
-  const int xq = tid & 15;        // which float4 of the row
-  const int x = x0 + xq * 4;
-#pragma unroll
-  for (int pass = 0; pass < kRows / 16; ++pass) {
-    const int yl = pass * 16 + (tid >> 4);
-    const int y = y0 + yl;
-    if (x >= a.g.nx || y >= a.y_end) continue;
-    const size_t c = (size_t)y * a.g.nx + x;
-    float4 l4 = *reinterpret_cast<const float4 *>(a.log_odds + c);
-    unsigned hb = 0, fb = 0;
-    if (COUNTS) {
-      const size_t wn = (size_t)(x >> 5) * a.ny_pad + y;
-      hb = (a.hitN[wn] >> (x & 31)) & 0xFu;
-      fb = (a.freeN[wn] >> (x & 31)) & 0xFu;
-      const uint4 ft = *reinterpret_cast<const uint4 *>(a.freeT + (size_t)(y >> 5) * a.nx_pad + x);
-      const int by = y & 31;
-      fb |= ((ft.x >> by) & 1u) | (((ft.y >> by) & 1u) << 1) | (((ft.z >> by) & 1u) << 2) | (((ft.w >> by) & 1u) << 3);
-    }
-    int k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-    if (!overflow) {
-      for (int r = 0; r < nr; ++r) {
-        const Rect R = s_rects[r];
-        if (y >= R.y0 && y <= R.y1) {
-          k0 += (x >= R.x0 && x <= R.x1);
-          k1 += (x + 1 >= R.x0 && x + 1 <= R.x1);
-          k2 += (x + 2 >= R.x0 && x + 2 <= R.x1);
-          k3 += (x + 3 >= R.x0 && x + 3 <= R.x1);
-        }
-      }
-    } else {
-      for (int r = 0; r < a.n_rects; ++r) {
-        const Rect R = a.rects[r];
-        if (R.valid && y >= R.y0 && y <= R.y1) {
-          k0 += (x >= R.x0 && x <= R.x1);
-          k1 += (x + 1 >= R.x0 && x + 1 <= R.x1);
-          k2 += (x + 2 >= R.x0 && x + 2 <= R.x1);
-          k3 += (x + 3 >= R.x0 && x + 3 <= R.x1);
-        }
-      }
-    }
-    const unsigned o0 = __float_as_uint(l4.x), o1 = __float_as_uint(l4.y), o2 = __float_as_uint(l4.z), o3 = __float_as_uint(l4.w);
-    l4.x = cell_update_t(l4.x, k0, COUNTS, hb & 1u, fb & 1u);
-    l4.y = cell_update_t(l4.y, k1, COUNTS, hb & 2u, fb & 2u);
-    l4.z = cell_update_t(l4.z, k2, COUNTS, hb & 4u, fb & 4u);
-    l4.w = cell_update_t(l4.w, k3, COUNTS, hb & 8u, fb & 8u);
-    // A tile row (16 lanes, 64 cells: 256 B of each float layer, 64 B of the packed one) whose log-odds all came
-    // back with the bits they had is left alone: with the layers in step (gv_context::layers_in_step) occupancy and
-    // the packed grid already hold what would be stored.  Bits, not ==: a NaN equals itself, -0.0 is not 0.0.
-    // A row with any changed cell is written whole, so every store stays a full 64-byte piece or more.
-    if (!a.dense) {
-      const bool changed = ((__float_as_uint(l4.x) ^ o0) | (__float_as_uint(l4.y) ^ o1) | (__float_as_uint(l4.z) ^ o2) |
-                            (__float_as_uint(l4.w) ^ o3)) != 0u;
-      const unsigned long long rows = __ballot(changed);   // lanes outside the grid are inactive here: no bit
-      if (((rows >> (tid & 48)) & 0xFFFFull) == 0ull) continue;
-    }
-    float4 p4;
-    p4.x = sigmoid_ref_t(l4.x); p4.y = sigmoid_ref_t(l4.y); p4.z = sigmoid_ref_t(l4.z); p4.w = sigmoid_ref_t(l4.w);
-    *reinterpret_cast<float4 *>(a.log_odds + c) = l4;   // read again by the next frame
-    // occupancy and the packed grid are outputs nobody reads on the device: streaming stores
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    v4f np4; np4.x = p4.x; np4.y = p4.y; np4.z = p4.z; np4.w = p4.w;
-    __builtin_nontemporal_store(np4, reinterpret_cast<v4f *>(a.occupancy + c));
-    const unsigned packed = pack_i8_t(p4.w) | (pack_i8_t(p4.z) << 8) | (pack_i8_t(p4.y) << 16) | (pack_i8_t(p4.x) << 24);
-    __builtin_nontemporal_store(packed, reinterpret_cast<unsigned *>(a.occ_i8 + ((size_t)a.g.G - 4 - c)));
-  }
-  GV_TL_END(a.tl);
-}
-
-// `done` (optional) completes with the kernel, on its own dispatch packet (see launch_ray_sectors);
-// false: nothing launched
-bool launch_finalize_tiles(const FinalizeTileArgs &a, hipStream_t s, hipEvent_t done, hipEvent_t t0)
-{
-  const int rows = a.y_end - a.y_begin;
-  if (rows <= 0) return false;
-  const dim3 grid((a.g.nx + 63) / 64, (rows + GV_FIN_ROWS - 1) / GV_FIN_ROWS);
-  if (a.counts) hipExtLaunchKernelGGL(k_finalize_tiles<true>, grid, dim3(256), 0, s, t0, done, 0, a);
-  else hipExtLaunchKernelGGL(k_finalize_tiles<false>, grid, dim3(256), 0, s, t0, done, 0, a);
-  return true;
-}
-
-// miss read-back: free-cell bitmaps N | T as int32 0/1 per cell
-__global__ void __launch_bounds__(256) k_miss_to_i32(const unsigned *__restrict__ fN, const unsigned *__restrict__ fT,
-                                                     int nx, int ny, int nx_pad, int ny_pad,
-                                                     int32_t *__restrict__ out)
-{
-  const size_t G = (size_t)nx * ny;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < G; c += stride) {
-    const int y = (int)(c / nx), x = (int)(c - (size_t)y * nx);
-    const unsigned n = fN[(size_t)(x >> 5) * ny_pad + y] >> (x & 31);
-    const unsigned t = fT[(size_t)(y >> 5) * nx_pad + x] >> (y & 31);
-    out[c] = (int32_t)((n | t) & 1u);
-  }
-}
-
-void launch_miss_to_i32(const MissToI32Args &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_miss_to_i32, dim3(2048), dim3(256), 0, s, a.freeN, a.freeT, a.nx, a.ny, a.nx_pad, a.ny_pad, a.out);
 }
 
 }  // namespace gv

@@ -46,7 +46,7 @@ def _bits(x):
 
 # ------------------------------------------------------------------------------------------- per-cell update --
 def cell_update(l0, k=0, hit=None, miss=None):
-    """fp32 restatement of gv_generic.hip cell_update: l0 array, k int or int array of covering rectangles,
+    """fp32 restatement of gv_gridpass.hip cell_update: l0 array, k int or int array of covering rectangles,
     hit / miss bool arrays (None: the no-counts form)"""
     l = np.asarray(l0, F32) + DECAY
     k = np.broadcast_to(np.asarray(k), l.shape)

@@ -1,5 +1,5 @@
 """Register budget of the frame kernels, read from the compiler's own resource remarks (tools/kernel_resources.py compiles
-gv_binning.hip and gv_raysector.hip device-only with the library's flags; no GPU).  A scalar register that does not fit
+gv_binning.hip, gv_raysector.hip and gv_gridpass.hip device-only with the library's flags; no GPU).  A scalar register that does not fit
 is spilled to a lane of a vector register, and every spill and reload is a VALU-class instruction in kernels that run
 short of vector issue slots: the partition pass carries none, and none may creep back; the ray stage
 and the grid pass are held to the figures on record; the vector budgets are what keeps one sector workgroup and two partition workgroups on a CU."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Register and code-size account of the frame kernels, from the compiler alone (no GPU).
 
-Compiles gv_binning.hip and gv_raysector.hip device-only for gfx950 with exactly gvamd/build.py's FLAGS plus
+Compiles gv_binning.hip, gv_raysector.hip and gv_gridpass.hip device-only for gfx950 with exactly gvamd/build.py's FLAGS plus
 -Rpass-analysis=kernel-resource-usage into a scratch directory and prints, per kernel instantiation: VGPRs, waves
 per SIMD, spilled SGPRs / VGPRs, scratch bytes, code bytes and the static counts of VALU instructions, lane moves
 (v_readlane_b32 + v_writelane_b32: a spilled scalar register lives in a lane of a vector register, and every spill
@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "grid-vision_amd"))
 from gvamd import build as gvbuild  # noqa: E402
 
-FILES = ["gv_binning.hip", "gv_raysector.hip"]
+FILES = ["gv_binning.hip", "gv_raysector.hip", "gv_gridpass.hip"]
 REMARK = "-Rpass-analysis=kernel-resource-usage"
 _FIELDS = {
     "TotalSGPRs": "sgprs", "SGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs",
@@ -180,7 +180,7 @@ def main() -> int:
     ap.add_argument("--out", help="scratch directory (default: a temporary one)")
     ap.add_argument("--keep", action="store_true", help="keep the scratch directory (code objects, remarks)")
     ap.add_argument("--label", default="", help="heading printed above the table")
-    ap.add_argument("--csrc", default=gvbuild.CSRC, help="compile the two files of another csrc directory (a parent checkout)")
+    ap.add_argument("--csrc", default=gvbuild.CSRC, help="compile FILES of another csrc directory (a parent checkout)")
     a = ap.parse_args()
     out_dir = a.out or tempfile.mkdtemp(prefix="gv_kres_")
     os.makedirs(out_dir, exist_ok=True)
