@@ -472,6 +472,7 @@ int gv_reset(gv_handle h)
   h->infl.have_cost = h->infl.have_dist2 = false;   // the costmap was a snapshot of the grid that is gone
   h->nav.have_field = false;                        // ... and so was the distance field over it
   h->path.have = false;                             // ... and the paths walked down that field
+  h->frontier.have = false;                         // ... and the frontier clusters of that grid (X19)
   return GV_OK;
   GV_CATCH
 }

@@ -18,6 +18,7 @@
 #include "gv_launch_pose.hpp"
 #include "gv_launch_planner.hpp"
 #include "gv_launch_match.hpp"
+#include "gv_launch_frontier.hpp"
 #include "gv_resources.hpp"
 
 using namespace gv;
@@ -397,6 +398,24 @@ struct __attribute__((visibility("hidden"))) gv_context {
     int32_t S = 0, cap = 0;                 // of the resident paths
     bool have = false;                      // a path call since gv_create / gv_reset
   } path;
+  // [EXTENSION] X19 frontier clusters (gvx_set_frontier_config / gvx_frontier* / gvx_nav_field_from_frontier,
+  // gv_api_frontier.hip).  The configuration is handle state and travels in the kernel arguments; gv_reset keeps it.  The
+  // buffers are made by the first call and grown by a larger one: the frontier bitmap (guard words zero since
+  // allocation), `parent` and `labels` (the two words per cell), `head` (four counters and one count per workgroup,
+  // zeroed on the stream by every call), the two keys per written cluster, and the resident records and info, which
+  // double as the landing places of results bound for pageable memory.  All of it is used on the public stream only.
+  // After a call `parent[label]` is a cluster's index among the written ones: what the seed kernel reads.
+  struct Frontier {
+    bool set = false;
+    gvx_frontier_config cfg{};
+    DevBuf<unsigned long long> bits;
+    DevBuf<uint32_t> parent, labels, head;
+    DevBuf<unsigned long long> keys;
+    DevBuf<gvx_frontier_record> rec;
+    DevBuf<gvx_frontier_info> info;
+    int32_t cap = 0;                        // of the resident records
+    bool have = false;                      // a frontier call since gv_create / gv_reset
+  } frontier;
   // [EXTENSION] X10 rollout and control step (gv_set_motion_model / gv_rollout* / gv_control_step*).  The motion model is
   // handle configuration, copied into the kernel arguments of every rollout at enqueue.  `poses` is the resident
   // rollout, a buffer of its own (d_poses below is the staging copy of host poses, which every scoring call

@@ -107,6 +107,21 @@ assert SEARCH_STATS_DTYPE.itemsize == 32
 # every symbol include/gridvision_hip_search.h declares
 SEARCH_SYMBOLS = ["gv_set_search_config", "gv_match_search_async", "gv_match_search", "gv_match_search_host"]
 
+# [EXTENSION] X19 frontier clusters (include/gridvision_hip_frontier.h; a second C namespace, gvx_: the gv_ set is frozen)
+FRONTIER_USE_FIELD = 1 << 0  # a call's flags
+FRONTIER_NONE = 0xFFFFFFFF   # labels[e] of a cell that is no frontier cell
+FRONTIER_MAX_CAP = 4096
+FRONTIER_DTYPE = np.dtype([("label", np.int32), ("n_cells", np.int32), ("min_x", np.int32), ("max_x", np.int32),
+                           ("min_y", np.int32), ("max_y", np.int32), ("sum_x", np.uint64), ("sum_y", np.uint64),
+                           ("centre_entry", np.int32), ("field_entry", np.int32), ("field_min", np.uint32),
+                           ("goal_entry", np.int32), ("goal_x", np.float32), ("goal_y", np.float32)])   # gvx_frontier
+FRONTIER_INFO_DTYPE = np.dtype([(n, np.int32) for n in ("n_frontier_cells", "n_components", "n_clusters", "n_written", "best",
+                                                        "largest")] + [("flags", np.uint32), ("reserved", np.uint32)])   # gvx_frontier_info
+assert FRONTIER_DTYPE.itemsize == 64 and FRONTIER_INFO_DTYPE.itemsize == 32
+# every symbol include/gridvision_hip_frontier.h declares
+FRONTIER_SYMBOLS = ["gvx_set_frontier_config", "gvx_frontier_async", "gvx_frontier", "gvx_frontier_host", "gvx_get_frontier_labels",
+                    "gvx_device_frontier", "gvx_nav_field_from_frontier"]
+
 # gv_test_wave_op (csrc/gv_test_hooks.h), GV_TEST_WAVE_ dropped, in the enum's order; and the hook's two sentinels
 WAVE_OPS = ["SCAN_ADD", "SCAN_MAX", "SCAN_MIN", "REDUCE_ADD", "REDUCE_MAX", "REDUCE_MIN",
             "SHIFT_DOWN_1", "SHIFT_DOWN_2", "SHIFT_DOWN_4", "SHIFT_DOWN_8", "GROUP_SUM_8", "GROUP_SUM_16", "MIN_KEY",
@@ -338,6 +353,17 @@ class SearchConfig(C.Structure):
     def shape(self):
         """(NT, NY, NX) of the window"""
         return 2 * self.wt + 1, 2 * self.wy + 1, 2 * self.wx + 1
+
+
+class FrontierConfig(C.Structure):
+    """gvx_frontier_config: FREE is 0..free_max, UNKNOWN unknown_min..unknown_max of the packed layer; a frontier cell's
+    cost is below max_cost (256: the costmap is not read); a cluster has min_cells cells at least"""
+    _fields_ = [("free_max", C.c_int32), ("unknown_min", C.c_int32), ("unknown_max", C.c_int32), ("max_cost", C.c_int32),
+                ("min_cells", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def of(cls, free_max=25, unknown_min=40, unknown_max=60, max_cost=256, min_cells=1, flags=0):
+        return cls(int(free_max), int(unknown_min), int(unknown_max), int(max_cost), int(min_cells), int(flags))
 
 
 class MatchGuess(C.Structure):
@@ -785,6 +811,26 @@ def nav_path_host(grid_x, grid_y, resolution, field, starts, cap, flags=0, keep_
     if rc:
         raise GVError(rc, "gv_nav_path_host")
     return info, entries.reshape(S, cap), xy.reshape(S, cap, 2) if keep_xy else None
+
+
+def frontier_host(grid_x, grid_y, resolution, occ_i8, cfg, cap, flags=0, cost=None, field=None, keep_labels=True):
+    """gvx_frontier_host, the library's host twin of frontier (needs no GPU): occ_i8 the packed int8 layer, cost the
+    uint8 costmap (None with max_cost 256), field the uint32 distance field (None without FRONTIER_USE_FIELD), all of G
+    values in data order.  Returns (info FRONTIER_INFO_DTYPE record, records FRONTIER_DTYPE (cap,), labels uint32 (G,) or
+    None); records past n_written are zero."""
+    occ = np.ascontiguousarray(occ_i8, np.int8).reshape(-1)
+    cost = np.ascontiguousarray(cost, np.uint8).reshape(-1) if cost is not None else None
+    field = np.ascontiguousarray(field, np.uint32).reshape(-1) if field is not None else None
+    cap = int(cap)
+    info = np.zeros(1, FRONTIER_INFO_DTYPE)
+    out = np.zeros(cap if 1 <= cap <= FRONTIER_MAX_CAP else 1, FRONTIER_DTYPE)
+    labels = np.zeros(len(occ), np.uint32) if keep_labels else None
+    rc = load().gvx_frontier_host(C.c_uint8(grid_x), C.c_uint8(grid_y), C.c_double(resolution), _ptr(occ), _ptr(cost), _ptr(field),
+                                  C.byref(cfg) if cfg is not None else None, C.c_int32(cap), C.c_uint32(flags), _ptr(info),
+                                  _ptr(out), _ptr(labels))
+    if rc:
+        raise GVError(rc, "gvx_frontier_host")
+    return info[0], out, labels
 
 
 def control_select_dyn(weights, traj, nav, dyn, cfg, keep_totals=False):
@@ -1464,6 +1510,46 @@ class GridVisionHIP:
         """nav_field() seeded by every cell of resident path s, on the device.  Returns dict(n_seeds_used, rounds)."""
         info = NavInfo()
         self._ck(self._lib.gv_nav_field_from_path(self._h, C.c_int32(s), C.byref(info)), "gv_nav_field_from_path")
+        return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
+
+    # ---- [EXTENSION] frontier clusters of the resident grid
+    def set_frontier_config(self, cfg):
+        """the FrontierConfig of the frontier() calls that follow; None turns it off"""
+        self._ck(self._lib.gvx_set_frontier_config(self._h, C.byref(cfg) if cfg is not None else None), "gvx_set_frontier_config")
+
+    def frontier_async(self, cap, info, out, flags=0):
+        """enqueue on stream(): info a FRONTIER_INFO_DTYPE array of 1, out a FRONTIER_DTYPE array of cap; pinned arrays
+        are written in place by the device; both complete after synchronize()"""
+        assert info.dtype == FRONTIER_INFO_DTYPE and info.size >= 1
+        assert out.dtype == FRONTIER_DTYPE and out.size >= int(cap)
+        self._ck(self._lib.gvx_frontier_async(self._h, C.c_int32(cap), C.c_uint32(flags), _ptr(info), _ptr(out)), "gvx_frontier_async")
+
+    def frontier(self, cap, flags=0):
+        """the frontier clusters of the packed layer, waited for.  Returns (info FRONTIER_INFO_DTYPE record, records
+        FRONTIER_DTYPE (cap,)); the labels stay resident (frontier_labels, nav_field_from_frontier)."""
+        cap = int(cap)
+        info = np.zeros(1, FRONTIER_INFO_DTYPE)
+        out = np.zeros(cap if 1 <= cap <= FRONTIER_MAX_CAP else 1, FRONTIER_DTYPE)
+        self._ck(self._lib.gvx_frontier(self._h, C.c_int32(cap), C.c_uint32(flags), _ptr(info), _ptr(out)), "gvx_frontier")
+        return info[0], out
+
+    def frontier_labels(self):
+        """the labels layer of the last frontier(): uint32 (G,) in OccupancyGrid.data order"""
+        out = np.empty(self.G, np.uint32)
+        self._ck(self._lib.gvx_get_frontier_labels(self._h, _ptr(out)), "gvx_get_frontier_labels")
+        return out
+
+    def device_frontier(self):
+        """dict(labels, records, info: device addresses; cap) of the resident frontier (read-only)"""
+        l, r, i, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._ck(self._lib.gvx_device_frontier(self._h, C.byref(l), C.byref(r), C.byref(i), C.byref(cap)), "gvx_device_frontier")
+        return dict(labels=l.value, records=r.value, info=i.value, cap=cap.value)
+
+    def nav_field_from_frontier(self, k=-1):
+        """nav_field() seeded by every cell of written cluster k (-1: of every written cluster), on the device.  Returns
+        dict(n_seeds_used, rounds)."""
+        info = NavInfo()
+        self._ck(self._lib.gvx_nav_field_from_frontier(self._h, C.c_int32(k), C.byref(info)), "gvx_nav_field_from_frontier")
         return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
 
     # ---- [EXTENSION] rollout and control step over the resident rollout
