@@ -473,6 +473,7 @@ int gv_reset(gv_handle h)
   h->nav.have_field = false;                        // ... and so was the distance field over it
   h->path.have = false;                             // ... and the paths walked down that field
   h->frontier.have = false;                         // ... and the frontier clusters of that grid (X19)
+  h->gain.have = false;                             // ... and the gain records of its candidates (X20)
   return GV_OK;
   GV_CATCH
 }

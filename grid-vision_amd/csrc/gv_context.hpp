@@ -19,6 +19,7 @@
 #include "gv_launch_planner.hpp"
 #include "gv_launch_match.hpp"
 #include "gv_launch_frontier.hpp"
+#include "gv_launch_gain.hpp"
 #include "gv_resources.hpp"
 
 using namespace gv;
@@ -416,6 +417,22 @@ struct __attribute__((visibility("hidden"))) gv_context {
     int32_t cap = 0;                        // of the resident records
     bool have = false;                      // a frontier call since gv_create / gv_reset
   } frontier;
+  // [EXTENSION] X20 information gain of exploration goals (gvx2_set_gain_config / gvx2_gain* / gvx2_frontier_gain* /
+  // gvx2_nav_field_from_gain, gv_api_gain.hip).  The configuration is handle state and travels in the kernel arguments;
+  // gv_reset keeps it.  The buffers are made by the first call, at their largest (4096 records, 4096 entries): the
+  // resident records and info, which double as the landing places of results bound for pageable memory, and the device
+  // copy of host entries, which come through `up`'s staging slots.  All of it is used on the public stream only.  A
+  // frontier call reads Frontier's resident records and info in place.
+  struct Gain {
+    bool set = false;
+    gvx2_gain_config cfg{};
+    DevBuf<gvx2_gain_record> rec;
+    DevBuf<gvx2_gain_info> info;
+    DevBuf<int32_t> d_entries;
+    StageSlots up;
+    int32_t n = 0;                          // record slots of the resident result: n of a list call, the cap of a frontier call
+    bool have = false;                      // a gain call since gv_create / gv_reset
+  } gain;
   // [EXTENSION] X10 rollout and control step (gv_set_motion_model / gv_rollout* / gv_control_step*).  The motion model is
   // handle configuration, copied into the kernel arguments of every rollout at enqueue.  `poses` is the resident
   // rollout, a buffer of its own (d_poses below is the staging copy of host poses, which every scoring call

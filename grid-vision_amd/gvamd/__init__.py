@@ -122,6 +122,26 @@ assert FRONTIER_DTYPE.itemsize == 64 and FRONTIER_INFO_DTYPE.itemsize == 32
 FRONTIER_SYMBOLS = ["gvx_set_frontier_config", "gvx_frontier_async", "gvx_frontier", "gvx_frontier_host", "gvx_get_frontier_labels",
                     "gvx_device_frontier", "gvx_nav_field_from_frontier"]
 
+# [EXTENSION] X20 information gain of exploration goals (include/gridvision_hip_gain.h; a header added after ABI 4 owns its
+# prefix: gvx2_)
+GAIN_USE_FIELD = 1 << 0        # a call's flags
+GAIN_DEVICE_ENTRIES = 1 << 1
+GAIN_INVALID = 1 << 0          # status bits of a record
+GAIN_UNREACHABLE = 1 << 1
+GAIN_BELOW_MIN = 1 << 2
+GAIN_MAX_N = 4096
+GAIN_MAX_RADIUS = 255
+GAIN_NO_OPAQUE = 0xFFFFFFFF    # nearest_opaque_d2 when no ray ended on an opaque cell
+GAIN_DTYPE = np.dtype([("entry", np.int32), ("status", np.uint32), ("n_unknown", np.int32), ("n_free", np.int32),
+                       ("n_opaque", np.int32), ("rays_opaque", np.int32), ("rays_off_map", np.int32), ("rays_range", np.int32),
+                       ("nearest_opaque_d2", np.uint32), ("dist", np.uint32), ("score", np.int64)])   # gvx2_gain_record
+GAIN_INFO_DTYPE = np.dtype([("n_candidates", np.int32), ("n_ranked", np.int32), ("best", np.int32), ("best_entry", np.int32),
+                            ("best_score", np.int64), ("flags", np.uint32), ("radius", np.int32)])   # gvx2_gain_info
+assert GAIN_DTYPE.itemsize == 48 and GAIN_INFO_DTYPE.itemsize == 32
+# every symbol include/gridvision_hip_gain.h declares
+GAIN_SYMBOLS = ["gvx2_set_gain_config", "gvx2_gain_async", "gvx2_gain", "gvx2_frontier_gain_async", "gvx2_frontier_gain",
+                "gvx2_gain_host", "gvx2_device_gain", "gvx2_nav_field_from_gain"]
+
 # gv_test_wave_op (csrc/gv_test_hooks.h), GV_TEST_WAVE_ dropped, in the enum's order; and the hook's two sentinels
 WAVE_OPS = ["SCAN_ADD", "SCAN_MAX", "SCAN_MIN", "REDUCE_ADD", "REDUCE_MAX", "REDUCE_MIN",
             "SHIFT_DOWN_1", "SHIFT_DOWN_2", "SHIFT_DOWN_4", "SHIFT_DOWN_8", "GROUP_SUM_8", "GROUP_SUM_16", "MIN_KEY",
@@ -364,6 +384,17 @@ class FrontierConfig(C.Structure):
     @classmethod
     def of(cls, free_max=25, unknown_min=40, unknown_max=60, max_cost=256, min_cells=1, flags=0):
         return cls(int(free_max), int(unknown_min), int(unknown_max), int(max_cost), int(min_cells), int(flags))
+
+
+class GainConfig(C.Structure):
+    """gvx2_gain_config: the classes as in FrontierConfig (everything neither FREE nor UNKNOWN is OPAQUE); rays of radius
+    cells; BELOW_MIN under min_gain unknown cells; score = w_gain * n_unknown - w_dist * dist"""
+    _fields_ = [("free_max", C.c_int32), ("unknown_min", C.c_int32), ("unknown_max", C.c_int32), ("radius", C.c_int32),
+                ("min_gain", C.c_int32), ("w_gain", C.c_int32), ("w_dist", C.c_int32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def of(cls, free_max=25, unknown_min=40, unknown_max=60, radius=32, min_gain=0, w_gain=1, w_dist=0, reserved=0):
+        return cls(int(free_max), int(unknown_min), int(unknown_max), int(radius), int(min_gain), int(w_gain), int(w_dist), int(reserved))
 
 
 class MatchGuess(C.Structure):
@@ -789,6 +820,14 @@ def match_search_host(grid_x, grid_y, resolution, cost, x, y, z, base_lidar, cfg
     return res[0], stats[0]
 
 
+def _gain_entries(entries, device_ptr, n, flags):
+    """(pointer, n, flags) of a gain call's candidates: a host int32 array, or a device address of n entries"""
+    if device_ptr is not None:
+        return C.c_void_p(device_ptr), int(n), int(flags) | GAIN_DEVICE_ENTRIES
+    e = np.ascontiguousarray(entries, np.int32).reshape(-1)
+    return _ptr(e), len(e), int(flags)
+
+
 def _starts(starts):
     s = _f32(starts).reshape(-1, 2)
     assert len(s) >= 1, "starts is (S, 2)"
@@ -831,6 +870,23 @@ def frontier_host(grid_x, grid_y, resolution, occ_i8, cfg, cap, flags=0, cost=No
     if rc:
         raise GVError(rc, "gvx_frontier_host")
     return info[0], out, labels
+
+
+def gain_host(grid_x, grid_y, resolution, occ_i8, cfg, entries, flags=0, field=None):
+    """gvx2_gain_host, the library's host twin of gain (needs no GPU): occ_i8 the packed int8 layer and field the uint32
+    distance field (None without GAIN_USE_FIELD), both of G values in data order; entries int32 (n,).  Returns (info
+    GAIN_INFO_DTYPE record, records GAIN_DTYPE (n,))."""
+    occ = np.ascontiguousarray(occ_i8, np.int8).reshape(-1)
+    field = np.ascontiguousarray(field, np.uint32).reshape(-1) if field is not None else None
+    e = np.ascontiguousarray(entries, np.int32).reshape(-1)
+    info = np.zeros(1, GAIN_INFO_DTYPE)
+    out = np.zeros(max(len(e), 1), GAIN_DTYPE)
+    rc = load().gvx2_gain_host(C.c_uint8(grid_x), C.c_uint8(grid_y), C.c_double(resolution), _ptr(occ), _ptr(field),
+                               C.byref(cfg) if cfg is not None else None, C.c_int32(len(e)), _ptr(e), C.c_uint32(flags), _ptr(info),
+                               _ptr(out))
+    if rc:
+        raise GVError(rc, "gvx2_gain_host")
+    return info[0], out[:len(e)]
 
 
 def control_select_dyn(weights, traj, nav, dyn, cfg, keep_totals=False):
@@ -1550,6 +1606,56 @@ class GridVisionHIP:
         dict(n_seeds_used, rounds)."""
         info = NavInfo()
         self._ck(self._lib.gvx_nav_field_from_frontier(self._h, C.c_int32(k), C.byref(info)), "gvx_nav_field_from_frontier")
+        return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
+
+    # ---- [EXTENSION] information gain of exploration goals
+    def set_gain_config(self, cfg):
+        """the GainConfig of the gain() and frontier_gain() calls that follow; None turns it off"""
+        self._ck(self._lib.gvx2_set_gain_config(self._h, C.byref(cfg) if cfg is not None else None), "gvx2_set_gain_config")
+
+    def gain_async(self, entries, info, out, flags=0, device_ptr=None, n=None):
+        """enqueue on stream(): entries int32 (n,) (copied before the call returns), or device_ptr the device address of n
+        entries; info a GAIN_INFO_DTYPE array of 1, out a GAIN_DTYPE array of n; pinned arrays are written in place by
+        the device; both complete after synchronize()"""
+        src, n, flags = _gain_entries(entries, device_ptr, n, flags)
+        assert info.dtype == GAIN_INFO_DTYPE and info.size >= 1
+        assert out.dtype == GAIN_DTYPE and out.size >= n
+        self._ck(self._lib.gvx2_gain_async(self._h, C.c_int32(n), src, C.c_uint32(flags), _ptr(info), _ptr(out)), "gvx2_gain_async")
+
+    def gain(self, entries, flags=0, device_ptr=None, n=None):
+        """the gain records of the candidate entries, waited for.  Returns (info GAIN_INFO_DTYPE record, records
+        GAIN_DTYPE (n,)); both stay resident (device_gain, nav_field_from_gain)."""
+        src, n, flags = _gain_entries(entries, device_ptr, n, flags)
+        info = np.zeros(1, GAIN_INFO_DTYPE)
+        out = np.zeros(n if 1 <= n <= GAIN_MAX_N else 1, GAIN_DTYPE)
+        self._ck(self._lib.gvx2_gain(self._h, C.c_int32(n), src, C.c_uint32(flags), _ptr(info), _ptr(out)), "gvx2_gain")
+        return info[0], out
+
+    def frontier_gain_async(self, info, out, flags=0):
+        """enqueue on stream(): the candidates are the goal cells of the resident frontier's written records; out a
+        GAIN_DTYPE array of that frontier's cap"""
+        assert info.dtype == GAIN_INFO_DTYPE and info.size >= 1 and out.dtype == GAIN_DTYPE
+        self._ck(self._lib.gvx2_frontier_gain_async(self._h, C.c_uint32(flags), _ptr(info), _ptr(out)), "gvx2_frontier_gain_async")
+
+    def frontier_gain(self, flags=0):
+        """the gain records of the resident frontier's goal cells, waited for.  Returns (info GAIN_INFO_DTYPE record,
+        records GAIN_DTYPE (cap of that frontier,)), zero records behind n_candidates."""
+        info = np.zeros(1, GAIN_INFO_DTYPE)
+        out = np.zeros(FRONTIER_MAX_CAP, GAIN_DTYPE)
+        self._ck(self._lib.gvx2_frontier_gain(self._h, C.c_uint32(flags), _ptr(info), _ptr(out)), "gvx2_frontier_gain")
+        return info[0], out[:self.device_gain()["n"]].copy()
+
+    def device_gain(self):
+        """dict(records, info: device addresses; n) of the resident gain result (read-only)"""
+        r, i, n = C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._ck(self._lib.gvx2_device_gain(self._h, C.byref(r), C.byref(i), C.byref(n)), "gvx2_device_gain")
+        return dict(records=r.value, info=i.value, n=n.value)
+
+    def nav_field_from_gain(self, k=-1):
+        """nav_field() seeded by the cell of resident gain record k (-1: of the resident best), on the device.  Returns
+        dict(n_seeds_used, rounds)."""
+        info = NavInfo()
+        self._ck(self._lib.gvx2_nav_field_from_gain(self._h, C.c_int32(k), C.byref(info)), "gvx2_nav_field_from_gain")
         return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
 
     # ---- [EXTENSION] rollout and control step over the resident rollout
