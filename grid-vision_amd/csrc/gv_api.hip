@@ -474,6 +474,7 @@ int gv_reset(gv_handle h)
   h->path.have = false;                             // ... and the paths walked down that field
   h->frontier.have = false;                         // ... and the frontier clusters of that grid (X19)
   h->gain.have = false;                             // ... and the gain records of its candidates (X20)
+  h->shortcut.have = false;                         // ... and the waypoints of those paths (X21)
   return GV_OK;
   GV_CATCH
 }

@@ -20,6 +20,7 @@
 #include "gv_launch_match.hpp"
 #include "gv_launch_frontier.hpp"
 #include "gv_launch_gain.hpp"
+#include "gv_launch_shortcut.hpp"
 #include "gv_resources.hpp"
 
 using namespace gv;
@@ -433,6 +434,22 @@ struct __attribute__((visibility("hidden"))) gv_context {
     int32_t n = 0;                          // record slots of the resident result: n of a list call, the cap of a frontier call
     bool have = false;                      // a gain call since gv_create / gv_reset
   } gain;
+  // [EXTENSION] X21 shortcuts and waypoints of the resident paths (gvx3_set_shortcut_config / gvx3_shortcut* /
+  // gvx3_nav_field_from_shortcut, gv_api_shortcut.hip).  The configuration is handle state and travels in the kernel
+  // arguments; gv_reset keeps it.  The resident waypoints of the last call -- entries[S][wcap], index[S][wcap],
+  // xy[S][wcap][2] and the S records -- are in buffers of their own, made by the first call and grown by a larger one, so
+  // NavPath's buffers, which the kernel reads in place, are left as they are; gv_reset invalidates them with the paths.
+  // All of it is used on the public stream only, and the buffers double as the landing places of results bound for
+  // pageable memory.
+  struct Shortcut {
+    bool set = false;
+    gvx3_shortcut_config cfg{};
+    DevBuf<int32_t> entries, index;
+    DevBuf<float> xy;
+    DevBuf<gvx3_shortcut_info> info;
+    int32_t S = 0, wcap = 0;                // of the resident waypoints
+    bool have = false;                      // a shortcut call since gv_create / gv_reset
+  } shortcut;
   // [EXTENSION] X10 rollout and control step (gv_set_motion_model / gv_rollout* / gv_control_step*).  The motion model is
   // handle configuration, copied into the kernel arguments of every rollout at enqueue.  `poses` is the resident
   // rollout, a buffer of its own (d_poses below is the staging copy of host poses, which every scoring call

@@ -142,6 +142,21 @@ assert GAIN_DTYPE.itemsize == 48 and GAIN_INFO_DTYPE.itemsize == 32
 GAIN_SYMBOLS = ["gvx2_set_gain_config", "gvx2_gain_async", "gvx2_gain", "gvx2_frontier_gain_async", "gvx2_frontier_gain",
                 "gvx2_gain_host", "gvx2_device_gain", "gvx2_nav_field_from_gain"]
 
+# [EXTENSION] X21 shortcuts and waypoints of the resident paths (include/gridvision_hip_shortcut.h; its prefix: gvx3_)
+SHORTCUT_NO_CORNER = 1 << 0    # a call's flags
+SHORTCUT_OK, SHORTCUT_TRUNCATED, SHORTCUT_EMPTY = range(3)   # gvx3_shortcut_info.status
+SHORTCUT_MAX_WINDOW = 4096
+SHORTCUT_MAX_SPACING = 65535
+SHORTCUT_MAX_WCAP = 65536
+SHORTCUT_MAX_CELLS = 1 << 20   # S * wcap
+SHORTCUT_INFO_DTYPE = np.dtype([("status", np.int32), ("n_waypoints", np.int32), ("n_anchors", np.int32), ("n_src", np.int32),
+                                ("n_steps", np.int32), ("n_diag_steps", np.int32), ("max_cost_seen", np.int32),
+                                ("end_entry", np.int32)])   # gvx3_shortcut_info
+assert SHORTCUT_INFO_DTYPE.itemsize == 32
+# every symbol include/gridvision_hip_shortcut.h declares
+SHORTCUT_SYMBOLS = ["gvx3_set_shortcut_config", "gvx3_shortcut_async", "gvx3_shortcut", "gvx3_shortcut_host", "gvx3_get_shortcut",
+                    "gvx3_device_shortcut", "gvx3_nav_field_from_shortcut"]
+
 # gv_test_wave_op (csrc/gv_test_hooks.h), GV_TEST_WAVE_ dropped, in the enum's order; and the hook's two sentinels
 WAVE_OPS = ["SCAN_ADD", "SCAN_MAX", "SCAN_MIN", "REDUCE_ADD", "REDUCE_MAX", "REDUCE_MIN",
             "SHIFT_DOWN_1", "SHIFT_DOWN_2", "SHIFT_DOWN_4", "SHIFT_DOWN_8", "GROUP_SUM_8", "GROUP_SUM_16", "MIN_KEY",
@@ -395,6 +410,16 @@ class GainConfig(C.Structure):
     @classmethod
     def of(cls, free_max=25, unknown_min=40, unknown_max=60, radius=32, min_gain=0, w_gain=1, w_dist=0, reserved=0):
         return cls(int(free_max), int(unknown_min), int(unknown_max), int(radius), int(min_gain), int(w_gain), int(w_dist), int(reserved))
+
+
+class ShortcutConfig(C.Structure):
+    """gvx3_shortcut_config: a cell is CLEAR iff its cost <= max_cost; a shortcut reaches at most window path cells ahead;
+    waypoints every spacing cells of a segment's line (0: anchors only)"""
+    _fields_ = [("max_cost", C.c_int32), ("window", C.c_int32), ("spacing", C.c_int32), ("reserved", C.c_uint32 * 5)]
+
+    @classmethod
+    def of(cls, max_cost=252, window=64, spacing=0):
+        return cls(int(max_cost), int(window), int(spacing))
 
 
 class MatchGuess(C.Structure):
@@ -887,6 +912,28 @@ def gain_host(grid_x, grid_y, resolution, occ_i8, cfg, entries, flags=0, field=N
     if rc:
         raise GVError(rc, "gvx2_gain_host")
     return info[0], out[:len(e)]
+
+
+def shortcut_host(grid_x, grid_y, resolution, cost, cfg, src_entries, src_n, wcap, flags=0):
+    """gvx3_shortcut_host, the library's host twin of shortcut (needs no GPU): cost ANY uint8 array of G values in data
+    order, src_entries int32 (S, cap) and src_n int32 (S,) the paths.  Returns (info SHORTCUT_INFO_DTYPE (S,), entries int32
+    (S, wcap), index int32 (S, wcap), xy float32 (S, wcap, 2)); slots past n_waypoints are zero."""
+    cost = np.ascontiguousarray(cost, np.uint8).reshape(-1)
+    src = np.ascontiguousarray(src_entries, np.int32)
+    assert src.ndim == 2, "src_entries is (S, cap)"
+    S, cap = src.shape
+    n = np.ascontiguousarray(src_n, np.int32).reshape(-1)
+    assert len(n) == S
+    wcap = int(wcap)
+    room = max(S * wcap, 1) if 1 <= wcap <= SHORTCUT_MAX_WCAP and S * wcap <= SHORTCUT_MAX_CELLS else 1
+    info = np.zeros(max(S, 1), SHORTCUT_INFO_DTYPE)
+    entries, index, xy = np.zeros(room, np.int32), np.zeros(room, np.int32), np.zeros(2 * room, np.float32)
+    rc = load().gvx3_shortcut_host(C.c_uint8(grid_x), C.c_uint8(grid_y), C.c_double(resolution), _ptr(cost),
+                                   C.byref(cfg) if cfg is not None else None, _ptr(src), _ptr(n), C.c_int32(S), C.c_int32(cap),
+                                   C.c_int32(wcap), C.c_uint32(flags), _ptr(info), _ptr(entries), _ptr(index), _ptr(xy))
+    if rc:
+        raise GVError(rc, "gvx3_shortcut_host")
+    return info[:S], entries.reshape(S, wcap), index.reshape(S, wcap), xy.reshape(S, wcap, 2)
 
 
 def control_select_dyn(weights, traj, nav, dyn, cfg, keep_totals=False):
@@ -1656,6 +1703,58 @@ class GridVisionHIP:
         dict(n_seeds_used, rounds)."""
         info = NavInfo()
         self._ck(self._lib.gvx2_nav_field_from_gain(self._h, C.c_int32(k), C.byref(info)), "gvx2_nav_field_from_gain")
+        return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
+
+    # ---- [EXTENSION] shortcuts and waypoints of the resident paths
+    def set_shortcut_config(self, cfg):
+        """the ShortcutConfig of the shortcut() calls that follow; None turns it off"""
+        self._ck(self._lib.gvx3_set_shortcut_config(self._h, C.byref(cfg) if cfg is not None else None), "gvx3_set_shortcut_config")
+
+    def shortcut_async(self, wcap, info, way_xy=None, flags=0):
+        """enqueue on stream(): info a SHORTCUT_INFO_DTYPE array of S (that of the resident paths), way_xy None (the
+        waypoints stay resident only) or a float32 array of S * wcap * 2; pinned arrays are written in place by the device;
+        both complete after synchronize()"""
+        assert info.dtype == SHORTCUT_INFO_DTYPE
+        assert way_xy is None or way_xy.dtype == np.float32
+        self._ck(self._lib.gvx3_shortcut_async(self._h, C.c_int32(wcap), C.c_uint32(flags), _ptr(info), _ptr(way_xy)),
+                 "gvx3_shortcut_async")
+
+    def shortcut(self, wcap, flags=0, keep_xy=True):
+        """the resident paths pulled tight and thinned to at most wcap waypoints each, waited for.  Returns (info
+        SHORTCUT_INFO_DTYPE (S,), xy float32 (S, wcap, 2) or None with keep_xy=False); the waypoints stay resident
+        (shortcut_get, device_shortcut, nav_field_from_shortcut)."""
+        wcap = int(wcap)
+        S = self.device_nav_path()["S"]
+        ok = 1 <= wcap <= SHORTCUT_MAX_WCAP and S * wcap <= SHORTCUT_MAX_CELLS
+        info = np.zeros(S, SHORTCUT_INFO_DTYPE)
+        xy = np.zeros((S, wcap, 2) if ok else (1,), np.float32) if keep_xy else None
+        self._ck(self._lib.gvx3_shortcut(self._h, C.c_int32(wcap), C.c_uint32(flags), _ptr(info), _ptr(xy)), "gvx3_shortcut")
+        return info, xy
+
+    def device_shortcut(self):
+        """dict(entries, index, xy, info: device addresses; S, wcap) of the resident waypoints (read-only)"""
+        e, i, x, r, S, wcap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        self._ck(self._lib.gvx3_device_shortcut(self._h, C.byref(e), C.byref(i), C.byref(x), C.byref(r), C.byref(S), C.byref(wcap)),
+                 "gvx3_device_shortcut")
+        return dict(entries=e.value, index=i.value, xy=x.value, info=r.value, S=S.value, wcap=wcap.value)
+
+    def shortcut_get(self, s, cap_out=None):
+        """resident shortcut s read back: (info record, entries int32 (n,), index int32 (n,), xy float32 (n, 2)),
+        n = min(n_waypoints, cap_out)"""
+        cap_out = self.device_shortcut()["wcap"] if cap_out is None else int(cap_out)
+        info = np.zeros(1, SHORTCUT_INFO_DTYPE)
+        room = max(cap_out, 1)
+        entries, index, xy = np.zeros(room, np.int32), np.zeros(room, np.int32), np.zeros((room, 2), np.float32)
+        self._ck(self._lib.gvx3_get_shortcut(self._h, C.c_int32(s), _ptr(entries), _ptr(index), _ptr(xy), C.c_int32(cap_out), _ptr(info)),
+                 "gvx3_get_shortcut")
+        n = min(int(info[0]["n_waypoints"]), cap_out)
+        return info[0], entries[:n].copy(), index[:n].copy(), xy[:n].copy()
+
+    def nav_field_from_shortcut(self, s):
+        """nav_field() seeded by the written waypoints of resident shortcut s, on the device.  Returns dict(n_seeds_used,
+        rounds)."""
+        info = NavInfo()
+        self._ck(self._lib.gvx3_nav_field_from_shortcut(self._h, C.c_int32(s), C.byref(info)), "gvx3_nav_field_from_shortcut")
         return dict(n_seeds_used=info.n_seeds_used, rounds=info.rounds)
 
     # ---- [EXTENSION] rollout and control step over the resident rollout

@@ -31,7 +31,7 @@ def _headers() -> list:
     inc = os.path.join(os.path.dirname(PKG), "include")
     return ([os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))] +
             [os.path.join(inc, f) for f in ("gridvision_hip.h", "gridvision_hip_match.h", "gridvision_hip_path.h", "gridvision_hip_search.h",
-                                               "gridvision_hip_frontier.h", "gridvision_hip_gain.h")])
+                                               "gridvision_hip_frontier.h", "gridvision_hip_gain.h", "gridvision_hip_shortcut.h")])
 
 
 def needs_build() -> bool:
